@@ -7,7 +7,13 @@ sub-frame is what one reference frame is, `NrcHpmRenderer::Render(queue, true)` 
 NRC inference for every pixel, train-ray generation, 16 384 train rays + one Adam step (configs[2]), compositing.
 `--train 0` drops the training step.  One sample = one pixel path.
 
-  python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5]
+  python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5] [--full] [--dump-outputs DIR]
+A plain run sets up, warms up, times the K steps and prints the headline line (metric / value / unit / ms_per_step / dtype, the
+stage times of the timed region, the loss and the schedule).  `--full` adds everything else, measured after the timed region: the
+GPU Monte-Carlo figure, the host's enqueue time, the density look-up counts and the two rooflines, the quality leg, the CPU baseline,
+the all-reduce and frame-assembly times and (N > 1) the strong-scaling figures.  `--dump-outputs DIR` writes what the timed path
+computed in its last step as DIR/<name>.npy (see Job.dump_outputs); the inputs are seeded, so runs with the same arguments compare
+output for output.
 N > 1: one rank per GPU under torch.distributed.run.  Started WITHOUT that launcher (`python bench.py --gpus 8`), this script
 launches it itself -- before anything touches the GPU -- relays rank 0's single JSON line and exits with the job's status; it never
 runs fewer ranks than it was asked for.  The frame is sharded by interleaved strips of 8 pixel columns and the MLP gradients are
@@ -36,7 +42,7 @@ sys.path.insert(0, ROOT)
 # before the HIP runtime initialises)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
-MFMA_F16_PEAK_TFLOPS = 2500.0      # dense fp16 MFMA, /opt/skills/guides/MI355X_MICROARCH.md "Chip-level parameters"
+MFMA_F16_PEAK_TFLOPS = 2500.0      # dense fp16 MFMA of the MI355X (chip-level peak)
 HBM_PEAK_GBS = 8000.0              # HBM3E spec (6.3 TB/s measured copy)
 MLP_FLOP_PER_SAMPLE = 51584.0      # 2*(80*64 + 5*64*64 + 64*3), SURVEY.md 8(d)
 MLP_BYTES_PER_SAMPLE = 32.0        # 20 B query + 12 B radiance
@@ -45,14 +51,14 @@ MLP_BYTES_PER_SAMPLE = 32.0        # 20 B query + 12 B radiance
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (4-spp frames); ms_per_step is their mean")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--train", type=int, default=1)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--spp", type=int, default=4)
     ap.add_argument("--volume", type=int, default=256)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     # model overrides (default = the north-star model of BASELINE.json: Frequency+OneBlob, 6x64)
     ap.add_argument("--pos-id", type=int, default=3)
     ap.add_argument("--dir-id", type=int, default=0)
@@ -66,12 +72,20 @@ def parse_args(argv=None):
     ap.add_argument("--exchange", choices=["f32", "f16"], default="f32",
                     help="N > 1: what the per-step gradient all-reduce carries (nrc_cache_set_exchange_dtype): the fp32 vector (103 KB, default) or "
                          "the gradients as fp16 numbers pre-scaled by loss_scale 128 (52 KB; BASELINE.json configs[3] words it so)")
-    ap.add_argument("--no-quality", action="store_true", help="skip the untimed quality leg (the trained frame against this build's own MC ground truth)")
+    ap.add_argument("--no-quality", action="store_true", help="--full: skip the untimed quality leg (the trained frame against this build's own MC ground truth)")
     ap.add_argument("--config", choices=["c2", "c4", "c5"], default="c2", help="BASELINE.json preset (see the module docstring)")
     ap.add_argument("--strong", action="store_true",
                     help="N > 1: the frame named by --config / --width / --height IS the global frame and the global train batch stays 16 384 "
                          "rays (strong scaling) instead of every rank keeping a 1080p share (weak)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure as well (Monte-Carlo / CPU baselines, rooflines, quality leg, exchange timings, "
+                         "strong-scaling figures): see the module docstring")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def apply_preset(args):
@@ -412,6 +426,27 @@ class Job:
         samples = float(sum(self.parallel.local_width(r, self.world, self.gw) for r in range(self.world))) * self.gh * self.args.spp * steps
         return dict(value=samples / dt / 1e6, ms_per_step=dt / steps * 1e3, seconds=dt)
 
+    DUMP_MAX_ELEMS = {"image": 10 << 20, "weights": 2 << 20, "ema_weights": 2 << 20, "loss": 1}      # float32: at most 56 MB in all
+
+    def dump_outputs(self, out_dir):
+        """--dump-outputs: what a caller of the timed path holds after its last step, as DIR/<name>.npy (float32) -- `image`: the frame
+        (NrcHpmRenderer::GetImage, height x width x RGBA; on N > 1 ranks rank 0's own column strips), `weights` / `ema_weights`: the cache's
+        master and EMA weights after the step's Adam updates (nrc_cache_get_params 0 / 1), `loss`: the loss of the last training step (with
+        --train 1).  An array larger than its DUMP_MAX_ELEMS entry is written as the same fixed sample of its flattened elements on every
+        run (seeded indices, ascending)."""
+        import numpy as np
+        self.torch.cuda.synchronize()
+        arrays = {"image": self.ren.GetImage().cpu().numpy(), "weights": self.nrc.GetParams(0), "ema_weights": self.nrc.GetParams(1)}
+        if self.args.train:
+            arrays["loss"] = np.array([self.nrc.GetLoss()], np.float32)
+        os.makedirs(out_dir, exist_ok=True)
+        for k, (name, a) in enumerate(sorted(arrays.items())):
+            a = np.ascontiguousarray(a, np.float32)
+            cap = self.DUMP_MAX_ELEMS[name]
+            if a.size > cap:
+                a = a.reshape(-1)[np.sort(np.random.default_rng(1000 + k).choice(a.size, cap, replace=False))]
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+
     def allreduce_us(self):
         """per-step all-reduce time of the native exchange (collective); None on the hook path"""
         if self.exchange["path"].startswith("native"):
@@ -490,49 +525,53 @@ def main():
     # renderer, drawing the random numbers) measures the ramp, not the renderer: 7 140-7 510 Msamples/s for `--steps 20 --warmup 5`
     # against 7 670-7 700 for `--steps 100 --warmup 10` or `--steps 20 --warmup 25`.  So everything the host needs is prepared
     # first, ~40 ms of untimed Monte-Carlo frames are enqueued behind the measured ones and not awaited, and the warm-up steps follow
-    # at once; the barrier in front of the timed region still drains all of it.
+    # at once; the barrier in front of the timed region still drains all of it.  (A plain run needs these Monte-Carlo frames as the
+    # timed region's pre-warming too; their figure, gpu_mc_baseline, is reported with --full.)
     job.prepare(args.steps, args.warmup)
     mc_baseline, mc_keep = gpu_mc_baseline(api, sc, scene, W, H, keep_warm_ms=float(os.environ.get("NRC_BENCH_KEEP_WARM_MS", "40")))
     res = job.timed(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        job.dump_outputs(args.dump_outputs)      # before anything else renders into the frame or trains the cache
     if mc_keep is not None:
         mc_keep.Destroy()
     stats = job.stats
     schedule = ren.GetSchedule()
     value, ms_per_step = res["value"], res["ms_per_step"]
     loss = nrc.GetLoss() if args.train else None
-    # what the host spends enqueueing one frame (through the Python mirror, queues empty, nothing awaited): the launch path is on
-    # the critical path only if this approaches the GPU's frame time
-    ren.SetBlend(True)
-    t_h = time.perf_counter()
-    for _ in range(2):
-        ren.RenderFrames(job.randoms[:4], bool(args.train))
-    host_enqueue_ms = (time.perf_counter() - t_h) / 8 * 1e3
-    torch.cuda.synchronize()
-    ren.StageStats(reset=True)
-    allreduce_us = job.allreduce_us() if use_dist and args.train else None
     nrc_dtype = nrc.GetExchangeDtype()
-    assembly = job.frame_assembly_ms()
-
-    # ---- integrator traffic model: density look-ups counted on the device for extra (untimed) sub-frames of the same seed --
-    # n_fetch: the ALGORITHM's look-ups (every camera ray walked, as the reference and the oracle do; empty-space early-out off),
-    # n_fetch_executed: what the timed kernel really issues (early-out on: rays through provably empty space skip their walk)
-    def count(skip):
-        ren.SetEmptySkip(skip)
-        ren.CountFetches(True)
-        ren.SetFrameRandom(job.randoms[0])
-        ren.Render(None, False)
+    if args.full:
+        # what the host spends enqueueing one frame (through the Python mirror, queues empty, nothing awaited): the launch path is on
+        # the critical path only if this approaches the GPU's frame time
+        ren.SetBlend(True)
+        t_h = time.perf_counter()
+        for _ in range(2):
+            ren.RenderFrames(job.randoms[:4], bool(args.train))
+        host_enqueue_ms = (time.perf_counter() - t_h) / 8 * 1e3
         torch.cuda.synchronize()
-        return ren.CountFetches(False)
+        ren.StageStats(reset=True)
+        allreduce_us = job.allreduce_us() if use_dist and args.train else None
+        assembly = job.frame_assembly_ms()
 
-    n_fetch = count(False)
-    n_fetch_executed = count(True)
-    n_px = local_w * gh
-    quality = None
-    if world == 1 and args.train and not args.no_quality:
-        quality = quality_leg(job, mc_baseline["ms_per_frame"], (args.steps + args.warmup) * spp + 8)
+        # ---- integrator traffic model: density look-ups counted on the device for extra (untimed) sub-frames of the same seed --
+        # n_fetch: the ALGORITHM's look-ups (every camera ray walked, as the reference and the oracle do; empty-space early-out off),
+        # n_fetch_executed: what the timed kernel really issues (early-out on: rays through provably empty space skip their walk)
+        def count(skip):
+            ren.SetEmptySkip(skip)
+            ren.CountFetches(True)
+            ren.SetFrameRandom(job.randoms[0])
+            ren.Render(None, False)
+            torch.cuda.synchronize()
+            return ren.CountFetches(False)
+
+        n_fetch = count(False)
+        n_fetch_executed = count(True)
+        n_px = local_w * gh
+        quality = None
+        if world == 1 and args.train and not args.no_quality:
+            quality = quality_leg(job, mc_baseline["ms_per_frame"], (args.steps + args.warmup) * spp + 8)
 
     out = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- per-launch figures.  k_infer: event-timed loop on the launch stream (same buffers the frame uses); k_gen_rays:
         # the renderer's own HIP events around the launch, averaged over the timed region.
         n_inf = n_px
@@ -556,7 +595,7 @@ def main():
 
         flop_scale = (args.nn_width / 64.0) ** 2 * args.nn_depth / 6.0      # rough cost of a launch relative to the 6x64 model's 0.1 ms
         # (a) dense pass over uniformly random queries (positions in the quirk-Q3 range): the conservative figure -- zero or
-        #     repetitive operands let the chip hold a higher clock (cdna_hip_programming.md rule 25);
+        #     repetitive operands let the chip hold a higher clock;
         # (b) dense pass over this frame's own query buffer (78 % all-zero queries of unscattered pixels)
         g = torch.Generator(device="cuda").manual_seed(1)
         rnd = torch.rand((n_inf, 5), device="cuda", generator=g)
@@ -579,7 +618,7 @@ def main():
         n_live = int((ren.Buffer("info") == 1.0).sum().item())
         gen_store_bytes = n_px * (16 + 4) + n_live * (20 + 4) + ren.VertexImageBytes()
         # `traffic`: HBM-side bytes per launch from the rocprofv3 PMC passes of the SAME command, committed under profiles/
-        # (FETCH_SIZE / WRITE_SIZE in passes of their own, gfx950 corrections of MI355X_MICROARCH.md) -- a constant read from that
+        # (FETCH_SIZE / WRITE_SIZE in passes of their own, with the gfx950 corrections) -- a constant read from that
         # file, not measured in this run; quoted only when this run is the profiled workload, and labelled with its source.
         traffic, traffic_source = {}, None
         def committed(name):      # profiles/rNN_<name>, newest round first
@@ -664,6 +703,7 @@ def main():
                         bytes_per_pixel="fetches x 1 B + 16 B framebuffer + 32 B query I/O (SURVEY 8d)", stored_bytes=gen_store_bytes,
                         ms_per_launch=gen_ms, fetches_per_pixel=n_fetch / n_px, fetches_executed_per_pixel=n_fetch_executed / n_px,
                         issue=issue_roofline(gen_ms) if (W, H, args.volume, world, args.config) == (1920, 1080, 256, 1, "c2") and north_star else None)
+    if rank == 0:
         model = "NRC %dx%d %s+%s" % (args.nn_depth, args.nn_width, {0: "HashGrid(16x2,2^19)", 1: "Identity", 2: "TriangleWave(12)", 3: "Frequency(12)"}[args.pos_id],
                                      {0: "OneBlob(4)", 1: "Identity", 2: "TriangleWave(4)"}[args.dir_id])
         volume = "%d^3 seeded %s" % (args.volume, "smoke plume" if args.smoke_volume else "fBm cloud")
@@ -682,14 +722,16 @@ def main():
             workload = ("%s: %s (global %dx%d, tiles of interleaved 8-column strips), %s, %d spp/step, %s, HDR sky env map, scene preset 4, "
                         "train=%d (%d train rays + 1 Adam step per sub-frame); %s"
                         % ("configs[4]" if args.config == "c5" else "configs[1]+[2]", per_gpu, gw, gh, volume, spp, model, args.train, train_rays, quirks))
-        exchange = dict(exchange, dtype=nrc_dtype, allreduce_us_per_step=allreduce_us, frame_assembly=assembly)
+        exchange = dict(exchange, dtype=nrc_dtype)
+        if args.full:
+            exchange.update(allreduce_us_per_step=allreduce_us, frame_assembly=assembly)
         if world > 1 and args.train:
             # an N-GPU line is a line about N ranks exchanging gradients: refuse to print one whose exchange saw another number of ranks
             assert exchange["rccl_ranks"] == world, "the gradient exchange ran over %r ranks, the line says %d GPUs" % (exchange["rccl_ranks"], world)
         out = {
             "metric": "Msamples/s + ms/frame at 1080p, 256^3 cloud (NRC path)", "value": value, "unit": "Msamples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "ms_per_frame": ms_per_step / spp, "host_enqueue_ms_per_frame": host_enqueue_ms, "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
+            "ms_per_frame": ms_per_step / spp, "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
             "dtype": "f16 (fp16 MFMA operands, fp32 accumulate; fp32 integrator)", "data": "synthetic",
             "config": {"workload": workload, "preset": args.config,
                        "width": W, "height": H, "spp": spp, "volume": args.volume, "train": args.train, "compat_fix": int(args.compat_fix),
@@ -699,17 +741,21 @@ def main():
             "loss": loss,
             "schedule": schedule,      # what the renderer's tuner chose on this run's own frames (nrc_schedule; placement only)
             "build_id": api.build_id(),
-            "roofline": roof_gen if dominant_is_gen else roof_mlp,
-            "roofline_mlp": roof_mlp,
-            "roofline_integrator": roof_gen,
-            "gpu_mc_baseline": mc_baseline,
-            "quality": quality,
         }
+        if args.full:
+            out.update({
+                "host_enqueue_ms_per_frame": host_enqueue_ms,
+                "roofline": roof_gen if dominant_is_gen else roof_mlp,
+                "roofline_mlp": roof_mlp,
+                "roofline_integrator": roof_gen,
+                "gpu_mc_baseline": mc_baseline,
+                "quality": quality,
+            })
     job.close()
 
     # ---- N > 1, default preset (weak scaling): the two STRONG-scaling figures beside it, same ranks, after the timed region -- the metric's
     # own 1920x1080 frame split over the N ranks, and configs[3] (one 3840x2160 frame, 8 spp)
-    if world > 1 and args.config == "c2" and (W, H) == (1920, 1080) and not strong:
+    if args.full and world > 1 and args.config == "c2" and (W, H) == (1920, 1080) and not strong:
         for key, preset, what in (("strong_scaling_1080p", "c2", "the metric's frame: ONE 1920x1080 frame, 4 spp/step"),
                                   ("strong_scaling_c4", "c4", "configs[3]: ONE 3840x2160 frame, 8 spp/step")):
             a4 = parse_args(sys.argv[1:])
@@ -727,14 +773,14 @@ def main():
                                          % (what, world, j4.local_w, 1 << j4.log2_train))
             j4.close()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # cpu_baseline runs the reference's ground-truth algorithm (mc/render.comp, PATH_LENGTH 32: the reference has no CPU
         # renderer); `value` is the NRC path (2 vertices + cache query).  gpu_mc_baseline is the same algorithm as the CPU
         # baseline on the GPU -- the like-for-like ratio is gpu_mc_vs_cpu, gpu_vs_cpu compares the two different estimators.
         out["cpu_baseline"] = cpu_baseline(scene, W, H)
         out["gpu_vs_cpu"] = value / out["cpu_baseline"]["value"]
         out["gpu_mc_vs_cpu"] = out["gpu_mc_baseline"]["value"] / out["cpu_baseline"]["value"]
-    elif rank == 0:
+    elif args.full and rank == 0:
         out["cpu_baseline"] = None
         out["cpu_baseline_reason"] = ("--no-cpu-baseline" if args.no_cpu_baseline else
                                       "reported on rank 0 at N=1 only (the contract's bounded host-core sample); this is an N=%d line" % world)

@@ -1,18 +1,28 @@
 #!/usr/bin/env python3
 """Generates the committed fixtures under tests/golden/ from the reference checkout's DATA files.
 
-Run in the authoring container only (needs /root/reference):  python tests/golden/make_golden.py
-Inputs  (data, not source):  /root/reference/data/volume/wdas_cloud_sixteenth.vdb
-                             /root/reference/reference/{0,1,2,4,5}/0.exr
-Outputs: cloud_sixteenth_u8.npz   density volume quantised like src/Texture3D.cpp:106 (texture memory order [k][j][i])
+Run where the reference checkout is present:  python tests/golden/make_golden.py <reference checkout>
+Inputs  (data, not source):  <reference>/data/volume/wdas_cloud_sixteenth.vdb
+                             <reference>/reference/{0,1,2,4,5}/0.exr
+Outputs: cloud_sixteenth_excerpt.vdb the reference's cloud file cut down to the leaves in VDB_BOX (crop_vdb): header, transform,
+                                  the four root children's topology and the kept leaves' buffers byte for byte, only the root's
+                                  child count, the dropped leaves' child-mask bits, the grid's offsets and file_bbox_min / _max /
+                                  file_voxel_count rewritten (CC BY-SA 3.0, see cloud_sixteenth_excerpt.LICENSE.txt) -- what
+                                  tests/test_io_vdb.py gives both VDB readers
+         cloud_sixteenth_u8.npz   density volume quantised like src/Texture3D.cpp:106 (texture memory order [k][j][i])
          exr_stats.json           per-image statistics
          exr_{0,4}_240x135.npz    8x8 box-filtered RGBA of the two EXRs whose estimator matches the checked-in shaders
          exr_{0,4}_1920x1080.npz  the same two EXRs at full size, lossless: the images are grey (R = G = B, asserted), so
                                   {L = R, A} in fp32 is every number they hold (3.5 MB each) -- what Reference::CompareNrc
                                   (src/Reference.cpp:72-107) compares a frame with; tools/convergence.py and the quality tests use them
+         exr_{0,4}_rows.exr       rows [EXR_ROW0, EXR_ROW0 + EXR_ROWS) of the same two EXRs as files of their own: the header and the
+                                  ZIP-compressed chunks of the reference's files byte for byte, only the data window, the chunks'
+                                  y and the offset table rewritten -- what tests/test_io_vdb.py gives both EXR readers
+         exr_{0,4}_tail.exr       the same for rows [EXR_TAIL0, 1080): one full chunk and the frame's short last one (8 lines)
 """
 import json
 import os
+import struct
 import sys
 
 import numpy as np
@@ -21,16 +31,153 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 import nrc_hpm_renderer_amd.io_exr as io_exr  # noqa: E402
 import nrc_hpm_renderer_amd.io_vdb as io_vdb  # noqa: E402
+from nrc_hpm_renderer_amd.io_vdb import _R, _mask, _values  # noqa: E402
 from nrc_hpm_renderer_amd import scene  # noqa: E402
 
-REF = "/root/reference"
 OUT = os.path.dirname(os.path.abspath(__file__))
+EXR_ROW0, EXR_ROWS = 528, 32          # two 16-line ZIP chunks through the middle of the frame (row 540 is its centre)
+EXR_TAIL0 = 1056                      # the last full chunk and the 8-line chunk that ends the 1080-row frame
+# the VDB excerpt: the leaves in this box -- four root children (all at negative y, two at negative x, two at negative z), voxels on both
+# sides of 0 in x and z, and the value 1.0 that Texture3D::FromVDB requires (src/Texture3D.cpp:74)
+VDB_BOX = ((-16, -24, -16), (32, 0, 24))
+
+
+def crop_exr(src, dst, row0, rows):
+    """a ZIP-compressed scan-line EXR of `rows` rows cut out of `src` without re-encoding a chunk: row0 a multiple of 16, and rows too
+    unless the window ends on the file's last row (then the last chunk is the file's own short one)"""
+    d = open(src, "rb").read()
+    p, window = 8, None
+    while d[p] != 0:
+        name_end = d.index(b"\0", p)
+        type_end = d.index(b"\0", name_end + 1)
+        name = d[p:name_end]
+        size = struct.unpack("<i", d[type_end + 1:type_end + 5])[0]
+        if name == b"compression":
+            assert d[type_end + 5] == 3, "ZIP (16 lines per chunk) expected"
+        if name in (b"dataWindow", b"displayWindow"):
+            xmin, ymin, xmax, ymax = struct.unpack("<4i", d[type_end + 5:type_end + 21])
+            assert ymin == 0 and row0 % 16 == 0 and (rows % 16 == 0 or row0 + rows == ymax + 1) and row0 + rows <= ymax + 1
+            window = window or (xmin, xmax, ymax)
+            d = d[:type_end + 5] + struct.pack("<4i", xmin, 0, xmax, rows - 1) + d[type_end + 21:]
+        p = type_end + 5 + size
+    header = d[:p + 1]
+    n_chunks = (window[2] + 16) // 16
+    offs = struct.unpack("<%dQ" % n_chunks, d[p + 1:p + 1 + 8 * n_chunks])
+    chunks = []
+    for c in range(row0 // 16, (row0 + rows + 15) // 16):
+        y, size = struct.unpack("<ii", d[offs[c]:offs[c] + 8])
+        assert y == 16 * c
+        chunks.append(struct.pack("<ii", y - row0, size) + d[offs[c] + 8:offs[c] + 8 + size])
+    table, o = [], len(header) + 8 * len(chunks)
+    for ch in chunks:
+        table.append(o)
+        o += len(ch)
+    with open(dst, "wb") as f:
+        f.write(header + struct.pack("<%dQ" % len(table), *table) + b"".join(chunks))
+
+
+def crop_vdb(src, dst, lo, hi):
+    """the one-grid FloatGrid file `src` cut down to the leaf nodes whose origins lie in the leaf-aligned box [lo, hi): the root keeps
+    every child that holds such a leaf, the internal nodes' child masks lose the dropped leaves' bits, everything else of the kept
+    topology and the kept leaves' buffers are copied byte for byte; the grid offsets and file_bbox_min / _max / file_voxel_count are
+    rewritten.  Returns (bbox_min, bbox_max, active voxels, root children kept)."""
+    d = open(src, "rb").read()
+    lo, hi = np.array(lo), np.array(hi)
+    assert (lo % 8 == 0).all() and (hi % 8 == 0).all()
+    r = _R(d)
+    r.i64(), r.u32(), r.u32(), r.u32(), r.u8(), r.take(36), r.meta()
+    assert r.u32() == 1
+    r.string(), r.string(), r.string()
+    offsets_at = r.p
+    grid_pos, block_pos, end_pos = r.i64(), r.i64(), r.i64()
+    assert end_pos == len(d)
+    r.p = grid_pos
+    flags = r.u32()
+    meta_at = {}                     # name -> (payload offset, size)
+    for _ in range(r.u32()):
+        name, _typ = r.string(), r.string()
+        size = r.u32()
+        meta_at[name] = (r.p, size)
+        r.take(size)
+    r.string(), r.take(120)
+    assert r.u32() == 1
+    background = r.f32()
+    root_at = r.p
+    n_tiles, n_children = r.u32(), r.u32()
+    assert n_tiles == 0
+    children = []                    # per root child: (topology with the dropped leaves taken out, [leaf origin or None if dropped])
+    for _ in range(n_children):
+        start = r.p
+        o5 = np.array([r.i32(), r.i32(), r.i32()])
+        cm5, vm5 = _mask(r, 32768), _mask(r, 32768)
+        _values(r, 32768, vm5, flags, background)
+        assert not (vm5 & ~cm5).any()
+        topo, leaves = [d[start:r.p]], []
+        for n in np.nonzero(cm5)[0]:
+            o4 = o5 + 128 * np.array([n >> 10, (n >> 5) & 31, n & 31])
+            cm4_at = r.p
+            cm4, vm4 = _mask(r, 4096), _mask(r, 4096)
+            _values(r, 4096, vm4, flags, background)
+            values_end = r.p
+            kept, masks = cm4.copy(), []
+            for k in np.nonzero(cm4)[0]:
+                o3 = o4 + 8 * np.array([k >> 8, (k >> 4) & 15, k & 15])
+                inside = bool((o3 >= lo).all() and (o3 < hi).all())
+                m = r.take(64)
+                leaves.append(o3 if inside else None)
+                kept[k] = inside
+                if inside:
+                    masks.append(m)
+            if kept.any():
+                assert not (vm4 & ~cm4).any(), "active tiles beside kept leaves: not handled"
+            topo.append(np.packbits(kept, bitorder="little").tobytes() + d[cm4_at + 512:values_end] + b"".join(masks))
+        children.append((b"".join(topo), leaves))
+    assert r.p == block_pos
+    out_topo, out_buf, pts = [], [], []
+    for topo, leaves in children:
+        bufs = []
+        for o3 in leaves:
+            start = r.p
+            vm = _mask(r, 512)
+            _values(r, 512, vm, flags, background)
+            if o3 is not None:
+                bufs.append(d[start:r.p])
+                n = np.nonzero(vm)[0]
+                pts.append(o3 + np.stack([n >> 6, (n >> 3) & 7, n & 7], 1))
+        if bufs:
+            out_topo.append(topo)
+            out_buf.append(b"".join(bufs))
+    assert r.p == end_pos
+    pts = np.concatenate(pts)
+    bmin, bmax, count = pts.min(0), pts.max(0), len(pts)
+    head = bytearray(d[:root_at])
+    for name, payload in (("file_bbox_min", struct.pack("<3i", *bmin)), ("file_bbox_max", struct.pack("<3i", *bmax)),
+                          ("file_voxel_count", struct.pack("<q", count))):
+        at, size = meta_at[name]
+        assert size == len(payload)
+        head[at:at + size] = payload
+    topology = bytes(head) + struct.pack("<II", 0, len(out_topo)) + b"".join(out_topo)
+    out = topology + b"".join(out_buf)
+    head[offsets_at + 8:offsets_at + 24] = struct.pack("<qq", len(topology), len(out))
+    with open(dst, "wb") as f:
+        f.write(bytes(head) + out[len(head):])
+    return tuple(int(v) for v in bmin), tuple(int(v) for v in bmax), count, len(out_topo)
 
 
 def main():
+    REF = sys.argv[1]
+    crop = os.path.join(OUT, "cloud_sixteenth_excerpt.vdb")
+    bmin, bmax, count, n_children = crop_vdb(os.path.join(REF, "data/volume/wdas_cloud_sixteenth.vdb"), crop, *VDB_BOX)
+    print("cloud_sixteenth_excerpt.vdb: %d root children, bbox %s..%s, %d active voxels" % (n_children, bmin, bmax, count))
+    assert n_children == 4 and min(bmin) < 0
     vol, info = io_vdb.from_vdb(os.path.join(REF, "data/volume/wdas_cloud_sixteenth.vdb"))
     assert info["active_voxels"] == info["file_voxel_count"] == 415642
     u8 = scene.quantize_density(vol)
+    cvol, cinfo = io_vdb.from_vdb(crop)
+    assert cinfo["active_voxels"] == cinfo["file_voxel_count"] == count
+    lo = np.array(bmin) - np.array(info["bbox_min"])
+    hi = lo + np.array(bmax) - np.array(bmin) + 1
+    assert np.array_equal(scene.quantize_density(cvol), u8[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]])
     np.savez_compressed(os.path.join(OUT, "cloud_sixteenth_u8.npz"), density=u8,
                         bbox_min=np.array(info["bbox_min"]), bbox_max=np.array(info["bbox_max"]))
     stats = {}
@@ -50,6 +197,12 @@ def main():
             np.savez_compressed(os.path.join(OUT, "exr_%d_240x135.npz" % sid), rgba=ds)
             assert (img[..., 0] == img[..., 1]).all() and (img[..., 0] == img[..., 2]).all()
             np.savez_compressed(os.path.join(OUT, "exr_%d_1920x1080.npz" % sid), L=img[..., 0].copy(), A=img[..., 3].copy())
+            crop = os.path.join(OUT, "exr_%d_rows.exr" % sid)
+            crop_exr(os.path.join(REF, "reference/%d/0.exr" % sid), crop, EXR_ROW0, EXR_ROWS)
+            assert np.array_equal(io_exr.read_exr(crop).view(np.uint32), img[EXR_ROW0:EXR_ROW0 + EXR_ROWS].view(np.uint32))
+            tail = os.path.join(OUT, "exr_%d_tail.exr" % sid)
+            crop_exr(os.path.join(REF, "reference/%d/0.exr" % sid), tail, EXR_TAIL0, img.shape[0] - EXR_TAIL0)
+            assert np.array_equal(io_exr.read_exr(tail).view(np.uint32), img[EXR_TAIL0:].view(np.uint32))
     with open(os.path.join(OUT, "exr_stats.json"), "w") as f:
         json.dump(stats, f, indent=1, sort_keys=True)
     print(json.dumps(stats, indent=1))

@@ -1,6 +1,6 @@
 """bench.py prints ONE JSON line with the fields the driver reads (task contract): metric / value / unit / n_gpus / steps /
-warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload, plus `roofline` for the
-dominant kernel and `cpu_baseline`."""
+warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload, plus (--full) `roofline` for the
+dominant kernel and `cpu_baseline`; a plain run prints the headline only and --dump-outputs writes what its last step computed."""
 import json
 import os
 import subprocess
@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_json_line(torch_gpu):
     env = dict(os.environ, NRC_BENCH_CPU_BUDGET_S="2")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"],
                        capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -46,3 +46,48 @@ def test_bench_json_line(torch_gpu):
     cpu = d["cpu_baseline"]
     assert cpu["kind"] == "port" and cpu["cores"] >= 1 and cpu["value"] > 0 and cpu["unit"] == "Msamples/s" and cpu["sample"]
     assert d["value"] / cpu["value"] >= 10        # north star: >= 10x the CPU McHpmRenderer path
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(torch_gpu, tmp_path):
+    """a plain run (no --full): the headline fields with their meaning, none of the --full figures, at most 30 s of the process's wall
+    time outside its steps; --dump-outputs writes the last timed step's frame, weights and loss as float32 .npy files (at most 64 MB in
+    all).  The same arguments give bit-identical outputs (seeded inputs); 2 timed + 2 warm-up steps give what 3 + 1 give (exactly
+    --steps + --warmup steps run); one more timed step moves the weights (--steps sets the number of timed steps)"""
+    import time
+    import numpy as np
+
+    def run(name, steps, warmup):
+        out = tmp_path / name
+        t0 = time.perf_counter()
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=280, cwd=ROOT)
+        wall = time.perf_counter() - t0
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == steps and d["warmup"] == warmup
+        assert wall - (steps + warmup) * d["ms_per_step"] * 1e-3 < 30.0, (wall, d["ms_per_step"])
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["ema_weights.npy", "image.npy", "loss.npy", "weights.npy"], files
+        arrays = {f[:-4]: np.load(out / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        return d, arrays
+
+    def same(x, y):
+        return all(np.array_equal(x[k].view(np.uint32), y[k].view(np.uint32)) for k in x)
+
+    d, a = run("a", 3, 1)
+    assert d["unit"] == "Msamples/s" and d["value"] > 100 and d["higher_is_better"] is True and d["metric"].startswith("Msamples/s")
+    assert d["dtype"].startswith("f16")
+    assert abs(d["ms_per_step"] - 1920 * 1080 * 4 / d["value"] / 1e3) < 1e-6 * d["ms_per_step"] + 1e-9
+    for k in ("roofline", "roofline_mlp", "gpu_mc_baseline", "quality", "cpu_baseline", "host_enqueue_ms_per_frame"):
+        assert k not in d, k
+    assert a["image"].shape == (1080, 1920, 4) and a["image"][..., :3].max() > 0
+    assert abs(float(a["loss"][0]) - d["loss"]) <= 1e-6 * abs(d["loss"])
+    assert same(a, run("a2", 3, 1)[1])                       # same arguments, same outputs
+    assert same(a, run("b", 2, 2)[1])                        # 4 steps in all, split differently
+    c = run("c", 4, 1)[1]                                    # one timed step more: one more frame of training
+    assert not np.array_equal(a["weights"], c["weights"]) and not np.array_equal(a["ema_weights"], c["ema_weights"])

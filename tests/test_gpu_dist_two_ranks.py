@@ -92,7 +92,7 @@ def test_bench_self_launches_its_ranks(torch_gpu):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "NRC_BENCH_SHARED_GPU"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     if torch.cuda.device_count() < 2:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
         assert r.returncode != 0 and r.stdout.strip() == "" and "refusing" in r.stderr

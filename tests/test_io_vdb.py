@@ -1,24 +1,28 @@
 """The from-scratch VDB reader (nrc-hpm-renderer_amd/io_vdb.py; Texture3D::FromVDB semantics, src/Texture3D.cpp:12-82) on the
-reference's own file: data/volume/wdas_cloud_sixteenth.vdb -- 415 642 active voxels (= the file's `file_voxel_count` metadata),
-bounding box (-66,-21,-90)..(59,64,63), and, quantised like src/Texture3D.cpp:106, a dense R8 volume equal to the committed fixture
-byte for byte.  Skipped where the reference checkout is absent (the GPU box); tests/golden/make_golden.py wrote the fixture."""
+reference's own file, cut down: tests/golden/cloud_sixteenth_excerpt.vdb holds the leaves of data/volume/wdas_cloud_sixteenth.vdb in
+the box (-16,-24,-16)..(32,0,24), four root children (origins (-4096,-4096,-4096), (-4096,-4096,0), (0,-4096,-4096), (0,-4096,0)), the
+kept nodes' bytes unchanged (tests/golden/make_golden.py) -- 31 241 active voxels (= the `file_voxel_count` metadata make_golden.py
+wrote), bounding box (-16,-19,-16)..(31,-1,23), and, quantised like src/Texture3D.cpp:106, a dense R8 volume equal byte for byte to
+that block of the committed fixture of the whole file (cloud_sixteenth_u8.npz, 415 642 active voxels over (-66,-21,-90)..(59,64,63))."""
+import json
 import os
 
 import numpy as np
 import pytest
 
-VDB = "/root/reference/data/volume/wdas_cloud_sixteenth.vdb"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+VDB = os.path.join(GOLDEN, "cloud_sixteenth_excerpt.vdb")
+BLOCK = (slice(74, 114), slice(2, 21), slice(50, 98))         # its block of cloud16 ([z][y][x], from (-66,-21,-90))
 
 
-@pytest.mark.skipif(not os.path.exists(VDB), reason="reference checkout not present")
 def test_vdb_reader_reproduces_the_fixture_and_the_files_voxel_count(sc, cloud16):
     from nrc_hpm_renderer_amd import io_vdb
     vol, info = io_vdb.from_vdb(VDB)
-    assert info["active_voxels"] == 415642 == info["file_voxel_count"]
-    assert tuple(info["bbox_min"]) == (-66, -21, -90) and tuple(info["bbox_max"]) == (59, 64, 63) and info["extent"] == (126, 86, 154)
-    assert vol.dtype == np.float32 and vol.shape == (126, 86, 154) and float(vol.max()) == 1.0      # src/Texture3D.cpp:74
+    assert info["active_voxels"] == 31241 == info["file_voxel_count"]
+    assert tuple(info["bbox_min"]) == (-16, -19, -16) and tuple(info["bbox_max"]) == (31, -1, 23) and info["extent"] == (48, 19, 40)
+    assert vol.dtype == np.float32 and vol.shape == (48, 19, 40) and float(vol.max()) == 1.0      # src/Texture3D.cpp:74
     u8 = sc.quantize_density(vol)
-    assert u8.shape == cloud16.shape == (154, 86, 126) and np.array_equal(u8, cloud16)
+    assert cloud16.shape == (154, 86, 126) and u8.shape == (40, 19, 48) and np.array_equal(u8, cloud16[BLOCK])
 
 
 def _build(name):
@@ -31,10 +35,10 @@ def _build(name):
     return exe
 
 
-@pytest.mark.skipif(not os.path.exists(VDB), reason="reference checkout not present")
 def test_cpp_vdb_reader_equals_the_fixture(cloud16, tmp_path):
     """include/nrc_vdb.hpp -- the reader behind en::HpmScene(appConfig, "file.vdb") (src/HpmScene.cpp:44 -> Texture3D::FromVDB) -- on
-    the reference's file: the file's voxel count, its bounding box, and the dense R8 volume of the committed fixture byte for byte"""
+    the reference's file cut down to four root children: the file's voxel count, its bounding box, and the dense R8 volume of that block
+    of the committed fixture byte for byte"""
     import json
     import subprocess
     exe = _build("vdb_main")
@@ -42,25 +46,34 @@ def test_cpp_vdb_reader_equals_the_fixture(cloud16, tmp_path):
     r = subprocess.run([exe, VDB, str(out)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     info = json.loads(r.stdout)
-    assert info["active_voxels"] == 415642 == info["file_voxel_count"] and info["max"] == 1.0 and info["grid"] == "density"
-    assert (info["nx"], info["ny"], info["nz"]) == (126, 86, 154) and info["bbox_min"] == [-66, -21, -90] and info["bbox_max"] == [59, 64, 63]
-    assert np.array_equal(np.fromfile(out, np.uint8), cloud16.reshape(-1))
+    assert info["active_voxels"] == 31241 == info["file_voxel_count"] and info["max"] == 1.0 and info["grid"] == "density"
+    assert (info["nx"], info["ny"], info["nz"]) == (48, 19, 40) and info["bbox_min"] == [-16, -19, -16] and info["bbox_max"] == [31, -1, 23]
+    assert np.array_equal(np.fromfile(out, np.uint8), cloud16[BLOCK].reshape(-1))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/reference/0/0.exr"), reason="reference checkout not present")
 def test_cpp_exr_reader_equals_the_python_reader(tmp_path):
     """include/nrc_exr.hpp -- what en::Reference loads its ground truth with (tinyexr's LoadEXR in src/Reference.cpp:617-631) -- on the
-    reference's own ZIP-compressed 1920x1080 images: bit-identical to io_exr.read_exr, whose statistics tests/golden/exr_stats.json pins"""
+    reference's own ZIP-compressed images, the reference's compressed chunks byte for byte (tests/golden/make_golden.py): exr_{0,4}_rows.exr,
+    32 rows through the middle of reference/{0,4}/0.exr, and exr_{0,4}_tail.exr, its last 24 rows -- one full 16-line chunk and the
+    frame's short 8-line last chunk.  Bit-identical to io_exr.read_exr, and both equal to those rows of the full-size fixtures
+    (exr_{0,4}_1920x1080.npz, whose statistics tests/golden/exr_stats.json pins)"""
     import subprocess
     from nrc_hpm_renderer_amd import io_exr
     exe = _build("exr_main")
     for sid in (0, 4):
-        src = "/root/reference/reference/%d/0.exr" % sid
-        out = tmp_path / ("ref%d.f32" % sid)
-        r = subprocess.run([exe, src, str(out)], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stderr
-        a = np.fromfile(out, np.float32).reshape(1080, 1920, 4)
-        assert np.array_equal(a.view(np.uint32), io_exr.read_exr(src).view(np.uint32))
+        full = np.load(os.path.join(GOLDEN, "exr_%d_1920x1080.npz" % sid))
+        for name, row0, rows in (("rows", 528, 32), ("tail", 1056, 24)):      # make_golden.py: EXR_ROW0, EXR_ROWS / EXR_TAIL0
+            src = os.path.join(GOLDEN, "exr_%d_%s.exr" % (sid, name))
+            out = tmp_path / ("ref%d_%s.f32" % (sid, name))
+            r = subprocess.run([exe, src, str(out)], capture_output=True, text=True, timeout=120)
+            assert r.returncode == 0, r.stderr
+            assert json.loads(r.stdout) == {"width": 1920, "height": rows}
+            a = np.fromfile(out, np.float32).reshape(rows, 1920, 4)
+            py = io_exr.read_exr(src)
+            assert py.shape == (rows, 1920, 4) and np.array_equal(a.view(np.uint32), py.view(np.uint32))
+            for c in range(3):
+                assert np.array_equal(py[..., c].view(np.uint32), full["L"][row0:row0 + rows].view(np.uint32))
+            assert np.array_equal(py[..., 3].view(np.uint32), full["A"][row0:row0 + rows].view(np.uint32))
 
 
 def _build_asan(name):
@@ -115,8 +128,6 @@ def test_cpp_readers_reject_malformed_files_without_reading_out_of_bounds(tmp_pa
         assert r.returncode == 0 or "SkyRenderer ERROR" in r.stderr, r.stderr[-500:]
         seen[r.returncode] += 1
     assert seen[1] > 20
-    if not os.path.exists(VDB):
-        return
     exe = _build_asan("vdb_main")
     data = open(VDB, "rb").read()
     seen = {0: 0, 1: 0}

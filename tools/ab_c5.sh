@@ -3,7 +3,7 @@
 TAG=$1; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for L in "$@"; do
-  NRC_HPM_LIB=$PWD/nrc-hpm-renderer_amd/$L/libnrc_hpm.so timeout -k 10 300 python3 bench.py --config c5 --no-cpu-baseline > $OUT/c5_$L.json 2> $OUT/c5_$L.err || { tail -5 $OUT/c5_$L.err; exit 1; }
+  NRC_HPM_LIB=$PWD/nrc-hpm-renderer_amd/$L/libnrc_hpm.so timeout -k 10 300 python3 bench.py --full --config c5 --no-cpu-baseline > $OUT/c5_$L.json 2> $OUT/c5_$L.err || { tail -5 $OUT/c5_$L.err; exit 1; }
   python3 -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); m=d['roofline_mlp']

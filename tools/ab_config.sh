@@ -4,7 +4,7 @@ TAG=$1; ARGS=$2; shift 2
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for L in "$@"; do
   export NRC_HPM_LIB=$PWD/nrc-hpm-renderer_amd/$L/libnrc_hpm.so
-  timeout -k 10 300 python3 bench.py $ARGS --no-cpu-baseline > $OUT/bench_$L.json 2> $OUT/bench_$L.err || { tail -5 $OUT/bench_$L.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full $ARGS --no-cpu-baseline > $OUT/bench_$L.json 2> $OUT/bench_$L.err || { tail -5 $OUT/bench_$L.err; exit 1; }
   python3 -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

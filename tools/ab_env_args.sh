@@ -6,7 +6,7 @@ i=0
 for E in "$@"; do
   i=$((i+1))
   [ "$E" = "-" ] && E=""
-  env $E timeout -k 10 200 python3 bench.py $ARGS --no-cpu-baseline > $OUT/env_$i.json 2> $OUT/env_$i.err || { tail -5 $OUT/env_$i.err; exit 1; }
+  env $E timeout -k 10 200 python3 bench.py --full $ARGS --no-cpu-baseline > $OUT/env_$i.json 2> $OUT/env_$i.err || { tail -5 $OUT/env_$i.err; exit 1; }
   python3 -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

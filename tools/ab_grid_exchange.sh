@@ -6,7 +6,7 @@ show() { python3 -c "
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])
 print('%-28s %7.1f Msamples/s frame %.4f' % (sys.argv[2], d['value'], d['ms_per_frame']), {k: round(v,3) for k,v in d['stage_ms'].items()}, d.get('exchange'))" $1 "$2"; }
-ARGS="bench.py --gpus 1 --pos-id 0 --steps 30 --warmup 5 --no-cpu-baseline"
+ARGS="bench.py --full --gpus 1 --pos-id 0 --steps 30 --warmup 5 --no-cpu-baseline"
 timeout -k 10 250 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29561 $ARGS > $OUT/sparse.json 2> $OUT/sparse.err || { tail -5 $OUT/sparse.err; exit 1; }
 show $OUT/sparse.json "lists (default)"
 NRC_DEBUG=dense_grid_exchange timeout -k 10 250 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29562 $ARGS > $OUT/dense.json 2> $OUT/dense.err || { tail -5 $OUT/dense.err; exit 1; }

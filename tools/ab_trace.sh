@@ -8,7 +8,7 @@ REPO=$PWD
 export TMPDIR=/tmp
 for L in "$@"; do
   export NRC_HPM_LIB=$REPO/nrc-hpm-renderer_amd/$L/libnrc_hpm.so
-  (cd /tmp && timeout -k 10 300 rocprofv3 -f csv --kernel-trace --stats -d $OUT/prof_$L -o b -- $PY $REPO/bench.py --steps 25 --warmup 2 --no-cpu-baseline ${BENCH_ARGS}) > $OUT/prof_$L.log 2>&1 || { tail -5 $OUT/prof_$L.log; exit 1; }
+  (cd /tmp && timeout -k 10 300 rocprofv3 -f csv --kernel-trace --stats -d $OUT/prof_$L -o b -- $PY $REPO/bench.py --full --steps 25 --warmup 2 --no-cpu-baseline ${BENCH_ARGS}) > $OUT/prof_$L.log 2>&1 || { tail -5 $OUT/prof_$L.log; exit 1; }
   find $OUT/prof_$L -name "*.db" -delete
   python3 - $OUT/prof_$L $L $OUT/prof_$L.log <<'PYEOF'
 import csv, glob, json, sys

@@ -5,7 +5,7 @@ TAG=$1; STEPS=${2:-200}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for P in "c2:" "c5:--config c5" "hashgrid:--pos-id 0"; do
   N=${P%%:*}; A=${P#*:}
-  timeout -k 10 400 python3 bench.py $A --steps $STEPS --warmup 10 --no-cpu-baseline > $OUT/$N.json 2> $OUT/$N.err || { tail -5 $OUT/$N.err; exit 1; }
+  timeout -k 10 400 python3 bench.py --full $A --steps $STEPS --warmup 10 --no-cpu-baseline > $OUT/$N.json 2> $OUT/$N.err || { tail -5 $OUT/$N.err; exit 1; }
   python3 -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

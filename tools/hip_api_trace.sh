@@ -2,7 +2,7 @@
 REPO=$PWD; OUT=$REPO/gpurun_out/r05_hiptrace; mkdir -p $OUT
 export TMPDIR=/tmp
 PY=$(readlink -f $(which python3))
-(cd /tmp && timeout -k 10 400 rocprofv3 -f csv --hip-runtime-trace --stats -d "$OUT/prof" -o t -- "$PY" "$REPO/bench.py" --steps 40 --warmup 5 --no-cpu-baseline) > "$OUT/prof.log" 2>&1 || { tail -5 $OUT/prof.log; exit 1; }
+(cd /tmp && timeout -k 10 400 rocprofv3 -f csv --hip-runtime-trace --stats -d "$OUT/prof" -o t -- "$PY" "$REPO/bench.py" --full --steps 40 --warmup 5 --no-cpu-baseline) > "$OUT/prof.log" 2>&1 || { tail -5 $OUT/prof.log; exit 1; }
 ls $OUT/prof
 python3 - "$OUT" <<PYEOF
 import csv, glob, sys

@@ -9,7 +9,7 @@ i=0
 for E in "$@"; do
   i=$((i+1)); [ "$E" = "-" ] && E=""
   for kv in $E; do export "$kv"; done
-  B="$PY $REPO/bench.py $ARGS --steps 12 --warmup 6 --no-cpu-baseline"
+  B="$PY $REPO/bench.py --full $ARGS --steps 12 --warmup 6 --no-cpu-baseline"
   (cd /tmp && timeout -k 10 300 rocprofv3 -f csv --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum -d "$OUT/e${i}_tcc" -o b -- $B) > "$OUT/e${i}_tcc.log" 2>&1 || exit 1
   (cd /tmp && timeout -k 10 300 rocprofv3 -f csv --pmc FETCH_SIZE -d "$OUT/e${i}_fetch" -o b -- $B) > "$OUT/e${i}_fetch.log" 2>&1 || exit 1
   for kv in $E; do unset "${kv%%=*}"; done

@@ -45,7 +45,7 @@ def main():
                       "TCC_EA0_RDREQ_sum": m.get("TCC_EA0_RDREQ_sum", m.get("TCC_EA0_RDREQ")),
                       "TCC_HIT_sum": hit, "TCC_MISS_sum": miss, "bytes_read": rd, "bytes_written": wr,
                       "traffic_bytes": rd + wr, "l2_hit_rate": hit / (hit + miss) if hit + miss else None}
-    note = ("rocprofv3 --pmc, separate passes (FETCH_SIZE | WRITE_SIZE | TCC_*), per-launch means over `python3 bench.py --steps 3 "
+    note = ("rocprofv3 --pmc, separate passes (FETCH_SIZE | WRITE_SIZE | TCC_*), per-launch means over `python3 bench.py --full --steps 3 "
             "--warmup 1 --no-cpu-baseline` (1920x1080, 256^3 cloud, train on), MI355X. FETCH_SIZE/WRITE_SIZE in KB as reported; on "
             "gfx950 FETCH_SIZE reports 1/2 of a wide coalesced streaming read (MI355X_MICROARCH.md HBM section) -> bytes_read doubles "
             "it for the streaming kernels (k_infer, k_composite); for the integrator's 1-byte gathers it is left uncorrected.")

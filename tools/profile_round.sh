@@ -30,36 +30,36 @@ if has mlp; then
   unset NRC_BENCH_MLP_WARM
 fi
 if has bench; then
-  echo "== bench (plain)" && timeout -k 10 400 "$PY" bench.py --steps 100 --warmup 10 > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
+  echo "== bench (plain)" && timeout -k 10 400 "$PY" bench.py --full --steps 100 --warmup 10 > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
   echo "== bench kernel trace"
-  (cd /tmp && timeout -k 10 400 rocprofv3 -f csv --kernel-trace --stats -d "$OUT/prof_bench" -o bench -- "$PY" "$REPO/bench.py" --steps 25 --warmup 2 --no-cpu-baseline) > "$OUT/prof_bench.log" 2>&1 || exit 1
+  (cd /tmp && timeout -k 10 400 rocprofv3 -f csv --kernel-trace --stats -d "$OUT/prof_bench" -o bench -- "$PY" "$REPO/bench.py" --full --steps 25 --warmup 2 --no-cpu-baseline) > "$OUT/prof_bench.log" 2>&1 || exit 1
 fi
 if has pmc; then
-  B="$PY $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline"
+  B="$PY $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline"
   echo "== pmc FETCH_SIZE";  (cd /tmp && timeout -k 10 300 rocprofv3 -f csv --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o b -- $B) > "$OUT/pmc_fetch.log" 2>&1 || exit 1
   echo "== pmc WRITE_SIZE";  (cd /tmp && timeout -k 10 300 rocprofv3 -f csv --pmc WRITE_SIZE -d "$OUT/pmc_write" -o b -- $B) > "$OUT/pmc_write.log" 2>&1 || exit 1
   echo "== pmc TCC";         (cd /tmp && timeout -k 10 300 rocprofv3 -f csv --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_HIT_sum TCC_MISS_sum -d "$OUT/pmc_tcc" -o b -- $B) > "$OUT/pmc_tcc.log" 2>&1 || exit 1
   echo "== pmc SQ";          (cd /tmp && timeout -k 10 300 rocprofv3 -f csv --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAVES SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE -d "$OUT/pmc_sq" -o b -- $B) > "$OUT/pmc_sq.log" 2>&1 || exit 1
 fi
 if has c5; then
-  echo "== configs[4] bench (plain)" && timeout -k 10 400 "$PY" bench.py --config c5 > "$OUT/c5_bench.json" 2> "$OUT/c5_bench.err" || exit 1
+  echo "== configs[4] bench (plain)" && timeout -k 10 400 "$PY" bench.py --full --config c5 > "$OUT/c5_bench.json" 2> "$OUT/c5_bench.err" || exit 1
   echo "== configs[4] kernel trace"
-  (cd /tmp && timeout -k 10 400 rocprofv3 -f csv --kernel-trace --stats -d "$OUT/prof_c5" -o c5 -- "$PY" "$REPO/bench.py" --config c5 --steps 12 --warmup 2 --no-cpu-baseline) > "$OUT/prof_c5.log" 2>&1 || exit 1
+  (cd /tmp && timeout -k 10 400 rocprofv3 -f csv --kernel-trace --stats -d "$OUT/prof_c5" -o c5 -- "$PY" "$REPO/bench.py" --full --config c5 --steps 12 --warmup 2 --no-cpu-baseline) > "$OUT/prof_c5.log" 2>&1 || exit 1
   echo "== dense 8x128 inference kernel trace"
   (cd /tmp && timeout -k 10 300 rocprofv3 -f csv --kernel-trace --stats -d "$OUT/prof_mlp128" -o mlp128 -- "$PY" "$REPO/tools/bench_mlp.py" 2073600 20 128 8) > "$OUT/prof_mlp128.log" 2>&1 || exit 1
   python3 tools/trace_tail.py "$(find "$OUT/prof_mlp128" -name "*kernel_trace.csv" | head -1)" k_infer_gen 100 > "$OUT/mlp128_trace_tail.txt" 2>&1
 fi
 if has hash; then
-  echo "== HashGrid model (the reference's default posID 0) bench (plain)" && timeout -k 10 400 "$PY" bench.py --pos-id 0 --steps 60 --warmup 10 --no-cpu-baseline > "$OUT/hashgrid_bench.json" 2> "$OUT/hashgrid_bench.err" || exit 1
+  echo "== HashGrid model (the reference's default posID 0) bench (plain)" && timeout -k 10 400 "$PY" bench.py --full --pos-id 0 --steps 60 --warmup 10 --no-cpu-baseline > "$OUT/hashgrid_bench.json" 2> "$OUT/hashgrid_bench.err" || exit 1
   echo "== HashGrid kernel trace"
-  (cd /tmp && timeout -k 10 400 rocprofv3 -f csv --kernel-trace --stats -d "$OUT/prof_hash" -o hash -- "$PY" "$REPO/bench.py" --pos-id 0 --steps 12 --warmup 2 --no-cpu-baseline) > "$OUT/prof_hash.log" 2>&1 || exit 1
+  (cd /tmp && timeout -k 10 400 rocprofv3 -f csv --kernel-trace --stats -d "$OUT/prof_hash" -o hash -- "$PY" "$REPO/bench.py" --full --pos-id 0 --steps 12 --warmup 2 --no-cpu-baseline) > "$OUT/prof_hash.log" 2>&1 || exit 1
 fi
 if has issue; then
   echo "== issue-mix micro" && timeout -k 10 60 tools/_build/issue_mix > "$OUT/issue_mix.txt" 2>&1 || exit 1
 fi
 if has c4; then
   echo "== configs[3]: one rank's share of the 4K frame" && timeout -k 10 300 "$PY" tools/c4_rank_emulation.py > "$OUT/c4_rank_emulation.txt" 2>&1 || exit 1
-  echo "== configs[3] on one GPU" && timeout -k 10 400 "$PY" bench.py --config c4 --steps 30 --warmup 5 --no-cpu-baseline > "$OUT/c4_bench.json" 2> "$OUT/c4_bench.err" || exit 1
+  echo "== configs[3] on one GPU" && timeout -k 10 400 "$PY" bench.py --full --config c4 --steps 30 --warmup 5 --no-cpu-baseline > "$OUT/c4_bench.json" 2> "$OUT/c4_bench.err" || exit 1
 fi
 if has train; then
   echo "== training step alone, kernel traces (6x64, 8x128)"

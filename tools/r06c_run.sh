@@ -7,6 +7,6 @@ timeout -k 10 200 python tools/xcd_balance.py --config c5 > $O/xcd_c5.txt 2>&1 |
 unset NRC_HPM_LIB
 timeout -k 10 400 python tools/grad_drift.py --seeds 12 > $O/grad_drift.txt 2>&1 || exit 1
 timeout -k 10 300 python -m pytest tests/test_gpu_quality.py -x -q > $O/pytest_quality.log 2>&1; tail -3 $O/pytest_quality.log
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || exit 1
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 --compat-fix 2 --no-cpu-baseline > $O/bench_q2.json 2> $O/bench_q2.err || exit 1
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || exit 1
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --compat-fix 2 --no-cpu-baseline > $O/bench_q2.json 2> $O/bench_q2.err || exit 1
 echo done
