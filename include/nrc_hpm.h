@@ -264,8 +264,25 @@ int nrc_renderer_set_blend(nrc_renderer_t* r, int blend);
 /* The uniform-buffer half of the scene -- DirLight / PointLight / VolumeData / HdrEnvMap strength (src/DirLight.cpp:31-49,
  * src/HpmScene.cpp:56-76 `HpmScene::Update`, the ImGui light editors): takes effect with the next Render and does not reset
  * blending (only a camera change does, src/NrcHpmRenderer.cu:561-604).  The density volume and the environment map of `scene`
- * are ignored (textures are fixed at creation). */
+ * are ignored: the environment map is fixed at creation, a new density volume goes in with nrc_renderer_set_volume. */
 int nrc_renderer_set_scene_params(nrc_renderer_t* r, const nrc_scene* scene);
+/* Replace the density volume of a live renderer (animated media; the reference has no equivalent).  density: nx*ny*nz voxels, index
+ * i + nx*(j + ny*k) (a [nz][ny][nx] array), the dims the renderer was created with (otherwise NRC_ERR_INVALID and the renderer is
+ * unchanged).  format NRC_VOLUME_U8: R8 UNORM, taken as is; NRC_VOLUME_F32: float, quantised as the reference does, uint8(v * 255)
+ * truncated, with v <= 0 and NaN -> 0 and v >= 1 -> 255.  The density, the occupancy bits and the empty-space boxes are rebuilt on the
+ * device; world size, density factor, lights and the environment map stay as they are.
+ *   on_device = 1: density is device memory, read on the stream given at creation -- the call does not wait for the GPU, and the caller
+ *     may overwrite the buffer with work it enqueues on that stream afterwards.
+ *   on_device = 0: density is host memory; the call copies it and returns when the copy is done (it waits for that stream).
+ * Frames enqueued before the call render the old volume, frames enqueued after it the new one.  Progressive blending resets (as
+ * set_camera); the cache's weights, optimizer state and training ring are kept: following the change is the online training's job.
+ * In a sharded run every rank calls it, with the whole volume, before the same frame. */
+#define NRC_VOLUME_U8 0
+#define NRC_VOLUME_F32 1
+int nrc_renderer_set_volume(nrc_renderer_t* r, const void* density, uint32_t nx, uint32_t ny, uint32_t nz, int format, int on_device);
+/* diagnostics: the current volume's device buffers after synchronising the renderer -- which 0: density [nz][ny][nx] u8, 1: occupancy
+ * bits (uint32 words), 2: empty-space boxes float[6 * n] {lo.xyz, hi.xyz}; *bytes = their size (NULL, bytes 0: no boxes) */
+const void* nrc_renderer_volume_buffer(nrc_renderer_t* r, int which, size_t* bytes);
 /* UniformData.showNrc (include/engine/graphics/renderer/NrcHpmRenderer.hpp:70-75) */
 int nrc_renderer_set_show_nrc(nrc_renderer_t* r, int show);
 /* UniformData.random: by default drawn per frame from std::mt19937(seed) (the reference uses glm::linearRand,
@@ -414,6 +431,9 @@ int nrc_mc_renderer_set_empty_skip(nrc_mc_renderer_t* r, int on);   /* see nrc_r
 int nrc_mc_renderer_set_cost_order(nrc_mc_renderer_t* r, int on);   /* see nrc_renderer_set_cost_order */
 int nrc_mc_renderer_is_blending(nrc_mc_renderer_t* r);          /* include/engine/graphics/renderer/McHpmRenderer.hpp */
 int nrc_mc_renderer_set_scene_params(nrc_mc_renderer_t* r, const nrc_scene* scene);   /* see nrc_renderer_set_scene_params */
+/* see nrc_renderer_set_volume / nrc_renderer_volume_buffer (one stream: the volume is rewritten in stream order behind the frames) */
+int nrc_mc_renderer_set_volume(nrc_mc_renderer_t* r, const void* density, uint32_t nx, uint32_t ny, uint32_t nz, int format, int on_device);
+const void* nrc_mc_renderer_volume_buffer(nrc_mc_renderer_t* r, int which, size_t* bytes);
 int nrc_mc_renderer_set_frame_random(nrc_mc_renderer_t* r, const float random4[4]);
 const float* nrc_mc_renderer_framebuffer(nrc_mc_renderer_t* r);   /* RGBA32F, alpha = blended didScatter */
 int nrc_mc_renderer_export_exr(nrc_mc_renderer_t* r, const char* path);

@@ -436,6 +436,11 @@ public:
     void SetBlend(bool blend) { nrc_check(nrc_renderer_set_blend(h_, blend ? 1 : 0)); }
     void SetSceneParams(const nrc_scene& scene) { nrc_check(nrc_renderer_set_scene_params(h_, &scene)); }   // HpmScene::Update
     void SetSceneParams(const HpmScene& scene) { SetSceneParams(scene.Scene()); }
+    // a new density volume with the creation dims (nrc_renderer_set_volume: NRC_VOLUME_U8 / NRC_VOLUME_F32, device or host memory)
+    void SetVolume(const void* density, uint32_t nx, uint32_t ny, uint32_t nz, int format = NRC_VOLUME_U8, bool onDevice = true)
+    {
+        nrc_check(nrc_renderer_set_volume(h_, density, nx, ny, nz, format, onDevice ? 1 : 0));
+    }
     nrc_renderer_t* Handle() const { return h_; }
 
 private:
@@ -478,6 +483,10 @@ public:
     bool IsBlending() const { return nrc_mc_renderer_is_blending(h_) != 0; }
     void SetSceneParams(const nrc_scene& scene) { nrc_check(nrc_mc_renderer_set_scene_params(h_, &scene)); }
     void SetSceneParams(const HpmScene& scene) { SetSceneParams(scene.Scene()); }
+    void SetVolume(const void* density, uint32_t nx, uint32_t ny, uint32_t nz, int format = NRC_VOLUME_U8, bool onDevice = true)
+    {
+        nrc_check(nrc_mc_renderer_set_volume(h_, density, nx, ny, nz, format, onDevice ? 1 : 0));
+    }
     nrc_mc_renderer_t* Handle() const { return h_; }
 
 private:

@@ -79,6 +79,7 @@ ABI_SYMBOLS = [
     "nrc_cache_save_checkpoint", "nrc_cache_load_checkpoint", "nrc_cache_comm_status", "nrc_cache_set_comm_timeout_ms",
     "nrc_renderer_create", "nrc_renderer_render", "nrc_renderer_render_frames", "nrc_renderer_set_stage_events", "nrc_renderer_set_camera", "nrc_renderer_set_blend",
     "nrc_renderer_set_scene_params", "nrc_mc_renderer_set_scene_params",
+    "nrc_renderer_set_volume", "nrc_mc_renderer_set_volume", "nrc_renderer_volume_buffer", "nrc_mc_renderer_volume_buffer",
     "nrc_renderer_set_show_nrc", "nrc_renderer_set_frame_random", "nrc_renderer_framebuffer", "nrc_renderer_framebuffer_on",
     "nrc_renderer_export_exr",
     "nrc_renderer_frame_time_ms", "nrc_renderer_stage_stats", "nrc_renderer_frame_timeline", "nrc_set_wave_priority_raise", "nrc_renderer_destroy", "nrc_renderer_buffer", "nrc_renderer_count_fetches",
@@ -140,6 +141,13 @@ def load_library():
     L.nrc_renderer_tile_order.restype = C.c_size_t
     L.nrc_renderer_tile_order.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.nrc_mc_renderer_framebuffer.restype = C.c_void_p
+    for name in ("nrc_renderer_set_volume", "nrc_mc_renderer_set_volume"):
+        if hasattr(L, name):      # (an older build loaded through NRC_HPM_LIB has no volume swap)
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int]
+    for name in ("nrc_renderer_volume_buffer", "nrc_mc_renderer_volume_buffer"):
+        if hasattr(L, name):
+            getattr(L, name).restype = C.c_void_p
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
     L.nrc_mc_renderer_frame_time_ms.restype = C.c_float
     for name in ("nrc_cache_get_loss", "nrc_cache_get_loss_blocking", "nrc_renderer_is_blending", "nrc_mc_renderer_is_blending",
                  "nrc_cache_get_infer_batch_count", "nrc_cache_get_train_batch_count",
@@ -284,6 +292,46 @@ def _wrap_device(ptr, nbytes, dtype, shape):
     a.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
     t = torch.as_tensor(a, device="cuda")
     return t.view(dtype).view(*shape)
+
+
+VOLUME_U8, VOLUME_F32 = 0, 1      # NRC_VOLUME_U8 / NRC_VOLUME_F32
+VOLUME_BUF = dict(density=0, occ_bits=1, boxes=2)
+
+
+def _set_volume(fn, h, vol):
+    """SetVolume of both renderers: a C-contiguous numpy uint8 [nz][ny][nx] array (host memory: the call copies it and waits for the copy)
+    or a contiguous CUDA torch tensor, uint8 or float32 [nz][ny][nx] (read on the renderer's stream; the call does not wait)"""
+    if isinstance(vol, np.ndarray):
+        if vol.dtype != np.uint8 or vol.ndim != 3 or not vol.flags.c_contiguous:
+            raise RuntimeError("SkyRenderer ERROR: SetVolume takes a C-contiguous uint8 numpy array [nz][ny][nx] (got %s %s)" % (vol.dtype, vol.shape))
+        nz, ny, nx = vol.shape
+        _check(fn(h, C.c_void_p(vol.ctypes.data), nx, ny, nz, VOLUME_U8, 0))
+        return
+    import torch
+    if not isinstance(vol, torch.Tensor) or not vol.is_cuda or vol.dim() != 3 or not vol.is_contiguous() \
+            or vol.dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError("SkyRenderer ERROR: SetVolume takes a contiguous CUDA tensor, uint8 or float32 [nz][ny][nx], or a uint8 numpy array")
+    nz, ny, nx = vol.shape
+    _check(fn(h, _dev_ptr(vol), nx, ny, nz, VOLUME_F32 if vol.dtype == torch.float32 else VOLUME_U8, 1))
+
+
+def _volume_buffer(fn, h, name, dims):
+    """the current volume's device buffers (synchronises the renderer): density uint8 [nz][ny][nx], occ_bits int32 words, boxes float32 [n][6]"""
+    import torch
+    if name not in VOLUME_BUF:
+        raise RuntimeError("SkyRenderer ERROR: VolumeBuffer name must be one of %s" % sorted(VOLUME_BUF))
+    nbytes = C.c_size_t(0)
+    p = fn(h, C.c_int(VOLUME_BUF[name]), C.byref(nbytes))
+    if not p:
+        if name == "boxes" and not load_library().nrc_last_error():
+            return torch.zeros((0, 6), dtype=torch.float32, device="cuda")
+        _check(-1)
+    if name == "density":
+        nx, ny, nz = dims
+        return _wrap_device(p, nbytes.value, torch.uint8, (nz, ny, nx))
+    if name == "occ_bits":
+        return _wrap_device(p, nbytes.value, torch.int32, (nbytes.value // 4,))
+    return _wrap_device(p, nbytes.value, torch.float32, (nbytes.value // 24, 6))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -614,6 +662,15 @@ class NrcHpmRenderer:
         sc_ = make_c_scene(scene.scene if hasattr(scene, "scene") else scene)
         _check(self.L.nrc_renderer_set_scene_params(self.h, C.byref(sc_)))
 
+    def SetVolume(self, vol):
+        """a new density volume with the creation dims (include/nrc_hpm.h, nrc_renderer_set_volume): frames rendered from now on see it,
+        blending restarts, the cache keeps its weights"""
+        _set_volume(self.L.nrc_renderer_set_volume, self.h, vol)
+
+    def VolumeBuffer(self, name):
+        """device view of the current volume's 'density', 'occ_bits' or 'boxes' (after synchronising the renderer)"""
+        return _volume_buffer(self.L.nrc_renderer_volume_buffer, self.h, name, (self._scene.nx, self._scene.ny, self._scene.nz))
+
     def SetShowNrc(self, show):
         _check(self.L.nrc_renderer_set_show_nrc(self.h, C.c_int(int(show))))
 
@@ -819,6 +876,14 @@ class McHpmRenderer:
     def SetSceneParams(self, scene):
         sc_ = make_c_scene(scene.scene if hasattr(scene, "scene") else scene)
         _check(self.L.nrc_mc_renderer_set_scene_params(self.h, C.byref(sc_)))
+
+    def SetVolume(self, vol):
+        """see NrcHpmRenderer.SetVolume"""
+        _set_volume(self.L.nrc_mc_renderer_set_volume, self.h, vol)
+
+    def VolumeBuffer(self, name):
+        """see NrcHpmRenderer.VolumeBuffer"""
+        return _volume_buffer(self.L.nrc_mc_renderer_volume_buffer, self.h, name, (self._scene.nx, self._scene.ny, self._scene.nz))
 
     def SetFrameRandom(self, r4):
         r = (C.c_float * 4)(*[float(x) for x in r4])

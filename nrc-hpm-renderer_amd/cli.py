@@ -1,6 +1,6 @@
 """Headless counterpart of the reference's main loop (src/main.cu:152-419) for the hot path.
 
-    python -m nrc_hpm_renderer_amd.cli [17 positional AppConfig args] [--frames N] [--vdb FILE | --volume N] ...
+    python -m nrc_hpm_renderer_amd.cli [17 positional AppConfig args] [--frames N] [--vdb FILE [FILE ...] | --volume N] ...
 
 The 17 positional arguments are the reference's (src/AppConfig.cpp:154-182); without any, the reference's own defaults apply
 (src/main.cu:428-439: HashGrid position encoding, OneBlob direction encoding, 6x64, 4 train batches of 2^14).  Every frame is `NrcHpmRenderer::Render(queue, true)` (src/main.cu:287); with
@@ -13,6 +13,10 @@ Multi-GPU (new): `--gpus N` starts N ranks (python -m torc
 launcher yourself).  The frame is sharded by interleaved strips of 8 pixel columns, the MLP gradients are all-reduced every training
 step, the per-frame metrics are reduced over the ranks (five fp64 sums, nrc_compare_images_sharded) and `--export` writes the WHOLE
 frame from rank 0 (nrc_renderer_gather_frame).  Rank 0 owns the log.  NRC_CLI_SHARED_GPU=1 rehearses the ranks on one device (gloo).
+
+Animated media (new): `--vdb` with several files is a sequence.  Every file is densified over the union of their bboxes (one grid),
+uploaded once, and the renderer steps through them with NrcHpmRenderer.SetVolume, a new file every `--frames-per-volume` frames (the
+cache keeps training across the swaps).  `--benchmark` needs a single volume: there is no reference image of a moving medium.
 """
 import argparse
 import math
@@ -30,7 +34,8 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--vdb", default=None, help="OpenVDB FloatGrid file (Texture3D::FromVDB semantics)")
+    ap.add_argument("--vdb", nargs="+", default=None, help="OpenVDB FloatGrid file(s) (Texture3D::FromVDB semantics); several = a sequence")
+    ap.add_argument("--frames-per-volume", type=int, default=1, help="frames rendered with each volume of a --vdb sequence")
     ap.add_argument("--volume", type=int, default=256, help="edge of the procedural fBm cloud when no --vdb is given")
     ap.add_argument("--env", choices=["white", "black", "sky"], default="white")
     ap.add_argument("--benchmark", action="store_true")
@@ -40,6 +45,10 @@ def main(argv=None):
     ap.add_argument("--export", default=None, help="write the final NRC image to this EXR")
     ap.add_argument("--gpus", type=int, default=1, help="ranks the frame is sharded over (one GPU each)")
     args = ap.parse_args(argv)
+    if args.benchmark and args.vdb and len(args.vdb) > 1:
+        raise SystemExit("SkyRenderer ERROR: --benchmark needs a single --vdb volume (there is no reference image of a moving medium)")
+    if args.frames_per_volume < 1:
+        raise SystemExit("SkyRenderer ERROR: --frames-per-volume must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # start the ranks before anything touches the GPU in this process (a process that has initialised HIP must not spawn them)
@@ -63,9 +72,11 @@ def main(argv=None):
     if args.config and len(args.config) != 17:
         raise SystemExit("SkyRenderer ERROR: Argument count does not match requirements for AppConfig")
     cfg = api.AppConfig(["NRC-HPM-Renderer"] + (args.config or DEFAULT_ARGV))
+    sequence = []
     if args.vdb:
-        vol, _ = io_vdb.from_vdb(args.vdb)
-        density = sc.quantize_density(vol)
+        bbox = io_vdb.union_bbox(args.vdb) if len(args.vdb) > 1 else None
+        sequence = [sc.quantize_density(io_vdb.from_vdb(p, bbox)[0]) for p in args.vdb]
+        density = sequence[0]
     else:
         density = sc.quantize_density(sc.fbm_cloud_volume(args.volume, seed=1337))
     env = {"white": None, "black": sc.black_env(), "sky": sc.procedural_sky()}[args.env]
@@ -90,6 +101,8 @@ def main(argv=None):
         if shared_gpu:
             nrc.SetCollectiveHooks(rank, world)      # (with the native communicator the gather / metric reduction use RCCL too)
     nrc_renderer = api.NrcHpmRenderer(lw, H, False, camera, cfg, scene, nrc, tile=tile)
+    # a sequence: every volume uploaded once, swapped in on the device (every rank swaps the whole volume before the same frame)
+    seq_dev = [torch.from_numpy(np.ascontiguousarray(v)).cuda() for v in sequence] if len(sequence) > 1 else []
     out_dir = os.path.join(args.output, " " + cfg.GetName())
     log = None
     if rank == 0:
@@ -119,6 +132,8 @@ def main(argv=None):
     kStopEvery = 8
     bad, failed = False, False
     for frame in range(args.frames):
+        if seq_dev and frame > 0 and frame % args.frames_per_volume == 0:
+            nrc_renderer.SetVolume(seq_dev[(frame // args.frames_per_volume) % len(seq_dev)])
         nrc_renderer.Render(None, True)
         loss = nrc.GetLoss(wait=False)          # src/main.cu:376: polled every frame, never blocks the frame pipeline
         if math.isnan(loss) or math.isinf(loss):                    # src/main.cu:380-384

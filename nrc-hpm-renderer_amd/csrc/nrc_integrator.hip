@@ -1406,12 +1406,9 @@ __global__ __launch_bounds__(1024) void k_tile_order_xcd(uint32_t* __restrict__ 
 // corners are projected with the camera's forward transform; the screen rectangle around them, grown by a pixel, covers every
 // pixel whose camera ray can pass through the box (a pixel's ray consists of the points that project onto the pixel).  The 8x8
 // tiles the rectangle touches are marked.  A box with a corner at or behind the eye plane switches the mask off for this camera.
-__global__ __launch_bounds__(256) void k_tile_mask(const float* __restrict__ boxes, uint32_t n_boxes, DevProjView pv, DevFrame fr,
-                                                  uint32_t* __restrict__ mask)
+__device__ __forceinline__ void tile_mask_box(const float* __restrict__ boxes, uint32_t i, const DevProjView& pv, const DevFrame& fr,
+                                              uint32_t* __restrict__ mask)
 {
-    NRC_RAISE_WAVE_PRIORITY(16);
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_boxes) return;
     const uint32_t tiles_x = (fr.w + 7u) >> 3, tiles_y = (fr.h + 7u) >> 3;
     const uint32_t n_words = (tiles_x * tiles_y + 31u) >> 5;
     const float* b = boxes + 6u * (size_t)i;
@@ -1451,6 +1448,25 @@ __global__ __launch_bounds__(256) void k_tile_mask(const float* __restrict__ box
             const uint32_t bit = 1u << (id & 31u);
             if ((mask[id >> 5] & bit) == 0u) atomicOr(&mask[id >> 5], bit);
         }
+}
+
+__global__ __launch_bounds__(256) void k_tile_mask(const float* __restrict__ boxes, uint32_t n_boxes, DevProjView pv, DevFrame fr,
+                                                  uint32_t* __restrict__ mask)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_boxes) return;
+    tile_mask_box(boxes, i, pv, fr, mask);
+}
+
+// the same with the box count in device memory (a volume rebuilt on the device, k_vol_rows): the grid covers the box capacity
+__global__ __launch_bounds__(256) void k_tile_mask_dev(const float* __restrict__ boxes, const uint32_t* __restrict__ n_boxes, DevProjView pv,
+                                                      DevFrame fr, uint32_t* __restrict__ mask)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= *n_boxes) return;
+    tile_mask_box(boxes, i, pv, fr, mask);
 }
 
 // ------------------------------------------------------------------------------------------------ nrc/clear.comp + ring ordering
@@ -1875,6 +1891,217 @@ __global__ void k_test_rng(float u, float v, float r0, float r1, float r2, float
     }
 }
 
+// ------------------------------------------------------------------------------------------------ volume rebuild (set_volume)
+// What renderer creation builds on the host (SceneDev::upload / build_occupancy / build_occupancy_bits in nrc_api.hip), built on the
+// device from a volume already in device memory: the R8 density, the exact occupancy bits and the dilated 8^3-cell boxes, bit for bit.
+// Three launches: k_vol_ingest (one streaming pass over the voxels), k_vol_cells (the dilation per 8^3 cell + the occupancy words),
+// k_vol_rows (one workgroup: runs per cell row, an exclusive scan, the boxes in the host builder's order and their count).
+//
+// Neighbour sets of a voxel along one axis: bit 0 = the cell below is touched (the voxel is its cell's first and has a voxel below it),
+// bit 1 = its own cell, bit 2 = the cell above (the cell's last voxel with a voxel above it): build_occupancy marks the cells of
+// [v - 1, v + 1] clamped to the volume.
+__device__ __forceinline__ uint32_t vol_axis_set(uint32_t v, uint32_t n)
+{
+    return 2u | ((v & 7u) == 0u && v > 0u ? 1u : 0u) | ((v & 7u) == 7u && v + 1u < n ? 4u : 0u);
+}
+// the 27-bit mask of the cells (cell + (dx, dy, dz), d in -1..1) a set of voxels touches: bit (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1)
+__device__ __forceinline__ uint32_t vol_touch_mask(uint32_t xs, uint32_t ys, uint32_t zs)
+{
+    uint32_t m = 0u;
+#pragma unroll
+    for (uint32_t dz = 0; dz < 3u; dz++)
+#pragma unroll
+        for (uint32_t dy = 0; dy < 3u; dy++)
+            if (((zs >> dz) & 1u) && ((ys >> dy) & 1u)) m |= xs << (dz * 9u + dy * 3u);
+    return m;
+}
+// NRC_VOLUME_F32 -> R8: uint8(v * 255) truncated (the reference's quantisation, src/Texture3D.cpp:106); v <= 0 and NaN -> 0, v >= 1 -> 255
+__device__ __forceinline__ uint32_t vol_quantize(float v)
+{
+    if (!(v > 0.0f)) return 0u;
+    if (v >= 1.0f) return 255u;
+    return (uint32_t)(v * 255.0f);
+}
+
+// One workgroup per (32 cells along x) x (one 8x8 row of cells in y, z): 256 lanes, a lane owns four consecutive voxels of x (in one
+// cell) in 16 of the 64 voxel rows.  Writes the density and every cell's 27-bit touch mask (the workgroup owns its cells: no global atomics).
+// vec: nx % 4 == 0 and the source aligned to 4 elements (one 4- / 16-byte load per lane and row).
+template <bool F32, bool VEC>
+__global__ __launch_bounds__(256) void k_vol_ingest(const void* __restrict__ src, uint8_t* __restrict__ density, uint32_t* __restrict__ cell_mask,
+                                                   uint32_t nx, uint32_t ny, uint32_t nz, uint32_t gx, uint32_t gy, uint32_t n_chunks)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    __shared__ uint32_t lmask[32];
+    const uint32_t t = threadIdx.x;
+    if (t < 32u) lmask[t] = 0u;
+    __syncthreads();
+    const uint32_t chunk = blockIdx.x % n_chunks, crow = blockIdx.x / n_chunks;
+    const uint32_t cy = crow % gy, cz = crow / gy;
+    const uint32_t x = chunk * 256u + 4u * (t & 63u);
+    uint32_t m = 0u;
+    if (x < nx) {
+        uint32_t xs_q[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) xs_q[k] = x + k < nx ? vol_axis_set(x + k, nx) : 0u;
+        for (uint32_t r = t >> 6; r < 64u; r += 4u) {
+            const uint32_t y = cy * 8u + (r & 7u), z = cz * 8u + (r >> 3);
+            if (y >= ny || z >= nz) continue;
+            const size_t idx = ((size_t)z * ny + y) * nx + x;
+            uint32_t q[4];
+            if (VEC) {
+                if (F32) {
+                    const float4 f = *(const float4*)((const float*)src + idx);
+                    q[0] = vol_quantize(f.x); q[1] = vol_quantize(f.y); q[2] = vol_quantize(f.z); q[3] = vol_quantize(f.w);
+                } else {
+                    const uint32_t w = *(const uint32_t*)((const uint8_t*)src + idx);
+                    q[0] = w & 255u; q[1] = (w >> 8) & 255u; q[2] = (w >> 16) & 255u; q[3] = w >> 24;
+                }
+                *(uint32_t*)(density + idx) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; k++) {
+                    q[k] = 0u;
+                    if (x + k < nx) {
+                        q[k] = F32 ? vol_quantize(((const float*)src)[idx + k]) : (uint32_t)((const uint8_t*)src)[idx + k];
+                        density[idx + k] = (uint8_t)q[k];
+                    }
+                }
+            }
+            const uint32_t xs = (q[0] ? xs_q[0] : 0u) | (q[1] ? xs_q[1] : 0u) | (q[2] ? xs_q[2] : 0u) | (q[3] ? xs_q[3] : 0u);
+            if (xs) m |= vol_touch_mask(xs, vol_axis_set(y, ny), vol_axis_set(z, nz));
+        }
+    }
+    if (m) atomicOr(&lmask[(t & 63u) >> 1], m);
+    __syncthreads();
+    const uint32_t cx = chunk * 32u + t;
+    if (t < 32u && cx < gx) cell_mask[((size_t)cz * gy + cy) * gx + cx] = lmask[t];
+}
+
+// Blocks [0, n_cell_blocks): one lane per 8^3 cell -- occupied (build_occupancy's dilation) when a neighbour's touch mask, or its own,
+// names it.  Blocks from n_cell_blocks on: one lane per bit of the exact occupancy table (cells of 2^occ_shift voxels, occ_shift >= 3:
+// the OR of the own-cell bits of the 8^3 cells inside), a 64-bit ballot per wave = two whole words (occ_words is a multiple of four).
+__global__ __launch_bounds__(256) void k_vol_cells(const uint32_t* __restrict__ cell_mask, uint8_t* __restrict__ cell_occ, uint32_t* __restrict__ occ_bits,
+                                                  uint32_t gx, uint32_t gy, uint32_t gz, uint32_t n_cell_blocks, uint32_t occ_shift,
+                                                  uint32_t occ_gx, uint32_t occ_gy, uint32_t occ_gz, uint32_t occ_words)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    if (blockIdx.x < n_cell_blocks) {
+        const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+        if (i >= gx * gy * gz) return;
+        const uint32_t cx = i % gx, cy = (i / gx) % gy, cz = i / (gx * gy);
+        bool occ = false;
+        for (int dz = -1; dz <= 1; dz++)
+            for (int dy = -1; dy <= 1; dy++)
+                for (int dx = -1; dx <= 1; dx++) {
+                    const int nx_ = (int)cx + dx, ny_ = (int)cy + dy, nz_ = (int)cz + dz;
+                    if (nx_ < 0 || ny_ < 0 || nz_ < 0 || nx_ >= (int)gx || ny_ >= (int)gy || nz_ >= (int)gz) continue;
+                    // the neighbour at +d touches this cell when it names the offset -d
+                    const uint32_t bit = (uint32_t)((1 - dz) * 9 + (1 - dy) * 3 + (1 - dx));
+                    occ = occ || ((cell_mask[((size_t)nz_ * gy + ny_) * gx + nx_] >> bit) & 1u);
+                }
+        cell_occ[i] = occ ? 1u : 0u;
+        return;
+    }
+    const uint32_t j = (blockIdx.x - n_cell_blocks) * 256u + threadIdx.x;      // bit j of the occupancy table
+    if (j >= occ_words * 32u) return;      // (whole waves: occ_words * 32 is a multiple of 128)
+    bool set = false;
+    if (j < occ_gx * occ_gy * occ_gz) {
+        const uint32_t ox = j % occ_gx, oy = (j / occ_gx) % occ_gy, oz = j / (occ_gx * occ_gy);
+        const uint32_t s = occ_shift - 3u;
+        const uint32_t x1 = min((ox + 1u) << s, gx), y1 = min((oy + 1u) << s, gy), z1 = min((oz + 1u) << s, gz);
+        for (uint32_t z = oz << s; z < z1 && !set; z++)
+            for (uint32_t y = oy << s; y < y1 && !set; y++)
+                for (uint32_t x = ox << s; x < x1; x++)
+                    if ((cell_mask[((size_t)z * gy + y) * gx + x] >> 13) & 1u) { set = true; break; }
+    }
+    const unsigned long long b = __ballot(set);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (lane == 0u) occ_bits[j >> 5] = (uint32_t)b;
+    if (lane == 32u) occ_bits[j >> 5] = (uint32_t)(b >> 32);
+}
+
+// occupancy of the cells cx0 .. cx0 + 31 of a row of k_vol_cells' flags (bytes 0 / 1) as bits; cells past gx read 0.  words: gx % 4 == 0
+// (rows start on 4-byte boundaries: eight independent word loads instead of 32 byte loads)
+__device__ __forceinline__ uint32_t vol_row_bits(const uint8_t* __restrict__ row, uint32_t cx0, uint32_t gx, bool words)
+{
+    uint32_t m = 0u;
+    if (words && cx0 + 32u <= gx) {
+        const uint32_t* w = (const uint32_t*)(row + cx0);
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; k++) {
+            const uint32_t v = w[k];
+            m |= ((v & 1u) | ((v >> 7) & 2u) | ((v >> 14) & 4u) | ((v >> 21) & 8u)) << (4u * k);
+        }
+    } else {
+        for (uint32_t k = 0; k < 32u && cx0 + k < gx; k++) m |= (row[cx0 + k] ? 1u : 0u) << k;
+    }
+    return m;
+}
+
+// One workgroup: the cell rows (cy, cz) in chunks of 1024, a lane per row counts its runs of occupied cells, an exclusive scan over the
+// chunk places them, and each lane writes its boxes -- z, then y, then x: build_occupancy's order, deterministically.  World coordinates
+// with build_occupancy's fp64 expression (lo = -0.5 * size, vs = size / n: computed by the host the same way).
+__global__ __launch_bounds__(1024) void k_vol_rows(const uint8_t* __restrict__ cell_occ, float* __restrict__ boxes, uint32_t* __restrict__ n_boxes,
+                                                  uint32_t nx, uint32_t ny, uint32_t nz, uint32_t gx, uint32_t gy, uint32_t gz,
+                                                  double lo_x, double lo_y, double lo_z, double vs_x, double vs_y, double vs_z)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    __shared__ uint32_t scan[1024];
+    const uint32_t t = threadIdx.x, rows = gy * gz;
+    const bool words = (gx & 3u) == 0u;
+    uint32_t base = 0u;
+    for (uint32_t r0 = 0; r0 < rows; r0 += 1024u) {
+        const uint32_t r = r0 + t;
+        const uint8_t* row = cell_occ + (size_t)r * gx;
+        uint32_t cnt = 0u;
+        if (r < rows) {
+            uint32_t carry = 0u;      // the previous cell (bit 31 of the previous word)
+            for (uint32_t cx0 = 0; cx0 < gx; cx0 += 32u) {
+                const uint32_t m = vol_row_bits(row, cx0, gx, words);
+                cnt += __builtin_popcount(m & ~((m << 1) | carry));      // run starts
+                carry = m >> 31;
+            }
+        }
+        scan[t] = cnt;
+        __syncthreads();
+        for (uint32_t off = 1u; off < 1024u; off <<= 1) {      // inclusive Hillis-Steele scan
+            const uint32_t v = t >= off ? scan[t - off] : 0u;
+            __syncthreads();
+            scan[t] += v;
+            __syncthreads();
+        }
+        const uint32_t total = scan[1023];
+        if (cnt) {
+            uint32_t k = base + scan[t] - cnt;
+            const uint32_t cy = r % gy, cz = r / gy;
+            const float y0 = (float)(lo_y + vs_y * (double)(8u * cy)), y1 = (float)(lo_y + vs_y * (double)min(8u * (cy + 1u), ny));
+            const float z0 = (float)(lo_z + vs_z * (double)(8u * cz)), z1 = (float)(lo_z + vs_z * (double)min(8u * (cz + 1u), nz));
+            uint32_t carry = 0u, run = 0u;
+            for (uint32_t cx0 = 0; cx0 < gx; cx0 += 32u) {
+                const uint32_t m = vol_row_bits(row, cx0, gx, words);
+                uint32_t starts = m & ~((m << 1) | carry), ends = m & ~(m >> 1);
+                // (bit 31 ends a run only when the next word's first cell is empty)
+                if ((ends >> 31) && cx0 + 32u < gx && row[cx0 + 32u]) ends &= 0x7fffffffu;
+                carry = m >> 31;
+                while (starts | ends) {
+                    const uint32_t b = __builtin_ctz(starts | ends), bit = 1u << b;
+                    if (starts & bit) run = cx0 + b;
+                    if (ends & bit) {
+                        const uint32_t e = cx0 + b;
+                        float* o = boxes + 6u * (size_t)k++;
+                        o[0] = (float)(lo_x + vs_x * (double)(8u * run)); o[1] = y0; o[2] = z0;
+                        o[3] = (float)(lo_x + vs_x * (double)min(8u * (e + 1u), nx)); o[4] = y1; o[5] = z1;
+                    }
+                    starts &= ~bit; ends &= ~bit;
+                }
+            }
+        }
+        base += total;
+        __syncthreads();      // (scan[] is rewritten by the next chunk)
+    }
+    if (t == 0u) *n_boxes = base;
+}
+
 }  // namespace
 
 // ================================================================================================ launchers
@@ -1932,6 +2159,49 @@ void launch_tile_mask(const float* boxes, uint32_t n_boxes, const DevProjView& p
     NRC_HIP(hipMemsetAsync(mask, 0, (size_t)tile_mask_words(fr.w, fr.h) * 4, s));
     if (n_boxes == 0) return;
     hipLaunchKernelGGL(k_tile_mask, dim3(ceil_div(n_boxes, 256)), dim3(256), 0, s, boxes, n_boxes, pv, fr, mask);
+    NRC_HIP(hipGetLastError());
+}
+
+void launch_tile_mask_dev(const float* boxes, const uint32_t* n_boxes, uint32_t capacity, const DevProjView& pv, const DevFrame& fr, uint32_t* mask,
+                         hipStream_t s)
+{
+    NRC_HIP(hipMemsetAsync(mask, 0, (size_t)tile_mask_words(fr.w, fr.h) * 4, s));
+    if (capacity == 0) return;
+    hipLaunchKernelGGL(k_tile_mask_dev, dim3(ceil_div(capacity, 256)), dim3(256), 0, s, boxes, n_boxes, pv, fr, mask);
+    NRC_HIP(hipGetLastError());
+}
+
+uint32_t volume_box_capacity(uint32_t nx, uint32_t ny, uint32_t nz)
+{
+    const uint32_t gx = ceil_div(nx, 8), gy = ceil_div(ny, 8), gz = ceil_div(nz, 8);
+    return gy * gz * ceil_div(gx, 2);      // runs are separated by at least one empty cell
+}
+
+size_t volume_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t nz)
+{
+    return (size_t)ceil_div(nx, 8) * ceil_div(ny, 8) * ceil_div(nz, 8) * 5;
+}
+
+void launch_volume_rebuild(const void* src, int format, const VolumeRebuild& v, void* scratch, hipStream_t s)
+{
+    const uint32_t gx = ceil_div(v.nx, 8), gy = ceil_div(v.ny, 8), gz = ceil_div(v.nz, 8);
+    const size_t cells = (size_t)gx * gy * gz;
+    uint32_t* cell_mask = (uint32_t*)scratch;
+    uint8_t* cell_occ = (uint8_t*)(cell_mask + cells);
+    const uint32_t n_chunks = ceil_div(gx, 32);
+    const dim3 grid(n_chunks * gy * gz);
+    const size_t align = format == NRC_VOLUME_F32 ? 16 : 4;
+    const bool vec = v.nx % 4 == 0 && (uintptr_t)src % align == 0;
+    auto ingest = format == NRC_VOLUME_F32 ? (vec ? k_vol_ingest<true, true> : k_vol_ingest<true, false>)
+                                           : (vec ? k_vol_ingest<false, true> : k_vol_ingest<false, false>);
+    hipLaunchKernelGGL(ingest, grid, dim3(256), 0, s, src, v.density, cell_mask, v.nx, v.ny, v.nz, gx, gy, n_chunks);
+    NRC_HIP(hipGetLastError());
+    const uint32_t cell_blocks = ceil_div((uint32_t)cells, 256), occ_blocks = ceil_div(v.occ_words * 32u, 256);
+    hipLaunchKernelGGL(k_vol_cells, dim3(cell_blocks + occ_blocks), dim3(256), 0, s, (const uint32_t*)cell_mask, cell_occ, v.occ_bits, gx, gy, gz,
+                       cell_blocks, v.occ_shift, v.occ_gx, v.occ_gy, v.occ_gz, v.occ_words);
+    NRC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_vol_rows, dim3(1), dim3(1024), 0, s, (const uint8_t*)cell_occ, v.boxes, v.n_boxes, v.nx, v.ny, v.nz, gx, gy, gz,
+                       v.lo[0], v.lo[1], v.lo[2], v.vs[0], v.vs[1], v.vs[2]);
     NRC_HIP(hipGetLastError());
 }
 

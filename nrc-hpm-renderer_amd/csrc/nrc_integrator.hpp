@@ -113,6 +113,26 @@ void launch_query_layout(const DevFrame& fr, uint32_t floats_per_query, const fl
 uint32_t query_count(uint32_t w, uint32_t h);      // queries in tile-major order: whole 8x8 tiles
 void launch_tile_mask(const float* boxes, uint32_t n_boxes, const DevProjView& pv, const DevFrame& fr, uint32_t* mask, hipStream_t s);
 uint32_t tile_mask_words(uint32_t w, uint32_t h);
+// the same with the box count in device memory (*n_boxes <= capacity), as launch_volume_rebuild leaves it
+void launch_tile_mask_dev(const float* boxes, const uint32_t* n_boxes, uint32_t capacity, const DevProjView& pv, const DevFrame& fr, uint32_t* mask,
+                         hipStream_t s);
+
+// ---- device-side volume rebuild (nrc_renderer_set_volume): from a density volume in device memory (NRC_VOLUME_U8 / NRC_VOLUME_F32,
+// index i + nx*(j + ny*k)) the R8 density, the exact occupancy bits (DevScene::occ_bits) and the dilated 8^3-cell boxes of the tile mask,
+// bit-identical to what renderer creation builds on the host.  The box count stays in device memory (launch_tile_mask_dev).
+struct VolumeRebuild {
+    uint8_t* density;             // nx*ny*nz bytes
+    uint32_t* occ_bits;           // occ_words words
+    float* boxes;                 // 6 * volume_box_capacity floats
+    uint32_t* n_boxes;            // one word
+    uint32_t nx, ny, nz;
+    uint32_t occ_shift, occ_gx, occ_gy, occ_gz, occ_words;   // the table's geometry (a function of the dims: SceneDev::build_occupancy_bits)
+    double lo[3], vs[3];          // -0.5 * size, size / n (build_occupancy's fp64 world coordinates)
+};
+uint32_t volume_box_capacity(uint32_t nx, uint32_t ny, uint32_t nz);
+size_t volume_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+// scratch: volume_scratch_bytes; src must stay unchanged until the launches on s have run.  Three launches.
+void launch_volume_rebuild(const void* src, int format, const VolumeRebuild& v, void* scratch, hipStream_t s);
 // table[m] = optical distance covered by the 128 free flights a delta walk draws from RNG state m when it rejects every collision
 constexpr uint32_t kFlightStates = 1u << 23;
 constexpr uint32_t kFlightListMax = 8;

@@ -91,10 +91,8 @@ def _values(r, count, mask, flags, background):
     return out
 
 
-def read_vdb_dense(path):
-    """Returns (volume float32 indexed [x][y][z] over file_bbox, info dict)."""
-    with open(path, "rb") as f:
-        r = _R(f.read())
+def _grid_header(r):
+    """reads the file header and the first grid's metadata: (version, grid name, grid type, grid / block / end positions, flags, metadata)"""
     magic = r.i64()
     assert magic == 0x56444220, "not a VDB file"
     version = r.u32()
@@ -112,7 +110,38 @@ def read_vdb_dense(path):
     r.p = grid_pos
     flags = r.u32()
     gmeta = r.meta()
-    bmin, bmax = np.array(gmeta["file_bbox_min"]), np.array(gmeta["file_bbox_max"])
+    return version, name, gtype, grid_pos, block_pos, end_pos, flags, gmeta
+
+
+def vdb_bbox(path):
+    """the file's active-voxel bounding box: (min xyz, max xyz), inclusive integer index coordinates"""
+    with open(path, "rb") as f:
+        gmeta = _grid_header(_R(f.read()))[7]
+    return tuple(int(v) for v in gmeta["file_bbox_min"]), tuple(int(v) for v in gmeta["file_bbox_max"])
+
+
+def union_bbox(paths):
+    """the smallest bbox holding every file's bbox: densify all frames of a sequence over it (read_vdb_dense(path, bbox)) and they share
+    one grid -- what a renderer whose volume is replaced frame by frame (NrcHpmRenderer.SetVolume) needs"""
+    boxes = [vdb_bbox(p) for p in paths]
+    if not boxes:
+        raise ValueError("union_bbox: no files")
+    return (tuple(int(min(b[0][k] for b in boxes)) for k in range(3)), tuple(int(max(b[1][k] for b in boxes)) for k in range(3)))
+
+
+def read_vdb_dense(path, bbox=None):
+    """Returns (volume float32 indexed [x][y][z], info dict).  The volume covers the file's bbox, or `bbox` = (min xyz, max xyz)
+    (inclusive integer index coordinates) when given: data outside it is cropped, voxels inside it but outside the file's bbox are zero."""
+    with open(path, "rb") as f:
+        r = _R(f.read())
+    version, name, gtype, grid_pos, block_pos, end_pos, flags, gmeta = _grid_header(r)
+    fmin, fmax = np.array(gmeta["file_bbox_min"]), np.array(gmeta["file_bbox_max"])
+    if bbox is None:
+        bmin, bmax = fmin, fmax
+    else:
+        bmin, bmax = np.array(bbox[0], np.int64), np.array(bbox[1], np.int64)
+        if bmin.shape != (3,) or bmax.shape != (3,) or (bmax < bmin).any():
+            raise ValueError("read_vdb_dense: bbox must be ((x0, y0, z0), (x1, y1, z1)) with x1 >= x0 ...")
     ext = bmax - bmin + 1
     vol = np.zeros(tuple(ext), np.float32)
     r.string()              # transform type (UniformScaleMap etc.); payload skipped by seeking via topology parse below
@@ -169,14 +198,15 @@ def read_vdb_dense(path):
                 if (p >= 0).all() and (p < ext).all():
                     vol[tuple(p)] = vals[n]
     assert r.p == end_pos, (r.p, end_pos)
-    info = dict(version=version, name=name, bbox_min=tuple(bmin), bbox_max=tuple(bmax), extent=tuple(int(e) for e in ext),
+    info = dict(version=version, name=name, bbox_min=tuple(fmin), bbox_max=tuple(fmax), extent=tuple(int(e) for e in ext),
+                dense_bbox_min=tuple(int(v) for v in bmin), dense_bbox_max=tuple(int(v) for v in bmax),
                 file_voxel_count=gmeta.get("file_voxel_count"), active_voxels=active_voxels, flags=flags)
     return vol, info
 
 
-def from_vdb(path):
-    """Texture3D::FromVDB semantics: dense volume + the max==1 normalisation check (src/Texture3D.cpp:74)."""
-    vol, info = read_vdb_dense(path)
+def from_vdb(path, bbox=None):
+    """Texture3D::FromVDB semantics: dense volume + the max==1 normalisation check (src/Texture3D.cpp:74); bbox: see read_vdb_dense."""
+    vol, info = read_vdb_dense(path, bbox)
     mx = float(vol.max())
     if mx != 0.0 and mx != 1.0:
         raise RuntimeError("SkyRenderer ERROR: VDB is not normalized")
