@@ -60,7 +60,23 @@ typedef struct nrc_config {
     uint32_t seed;                 /* weight-init seed (tiny-cuda-nn default 1337) */
     uint32_t compat_fix;           /* bit 0: fix quirk Q1 (TRAIN_Y_DIST), bit 1: fix quirk Q2 (trainRayLength); 0 = faithful */
     uint32_t hashgrid_log2_size;   /* posID 0: log2_hashmap_size; 0 = the reference's 19 (src/AppConfig.cpp:24) */
+    uint32_t self_train;           /* NRC renderer only, read at creation: 0 (default) = the reference's training targets; 1 = self-training, below */
 } nrc_config;
+/* ABI note: self_train is new in nrc_version() "0.3" (the struct grew by 4 bytes); a caller built against an older header must be
+ * recompiled (the library would read self_train past the end of its struct).
+ *
+ * Self-training (Mueller et al. 2021, "Real-time Neural Radiance Caching for Path Tracing"; the reference has none).  The train-path loop
+ * (prep_train_rays.comp:80-95) runs L vertices per sample: L = 1 in the faithful mode (quirk Q2), L = train_ray_length with
+ * NRC_FIX_Q2_TRAIN_RAY_LEN.  Sample s of train ray i ends with light_s (the sum it adds without self-training) and factor_s = 0.5^L when the
+ * loop ran all L vertices without leaving the medium; the walk then stands at its last scatter point cur with the direction after its last
+ * new_ray_dir, dir.  With self_train = 1:
+ *   tail    only a sample that completed all L vertices has one: the query nrc_query(cur, dir), normalised as gen_rays' NRC query (quirk Q5,
+ *           NaN phi, included).  A sample whose walk left the medium has no tail term (skipped, not multiplied by 0: 0 * Inf is NaN).
+ *   weights the tail's radiance y_s is the cache's inference with the EMA weights that frame N's render inference reads -- those after
+ *           frame N-1's last optimizer step (quirk Q13 ordering) -- for every train batch of the frame.
+ *   target  per channel, fp32, no contraction, in this order: t_s = factor_s * fmaxf(0, y_s) (NaN -> 0); u_s = light_s + t_s;
+ *           acc = ((0 + u_0) + u_1) + ...; target = fminf(8, acc / spp).  With y = 0 this is the target without self-training, bit for bit.
+ * Training inputs, the ring buffer, the render path and compositing are unchanged; frames rendered with train = 0 infer no tails. */
 
 #define NRC_FIX_Q1_TRAIN_Y_DIST 1u
 #define NRC_FIX_Q2_TRAIN_RAY_LEN 2u
@@ -317,7 +333,7 @@ int nrc_renderer_gather_frame(nrc_renderer_t* r, float* d_global_rgba, void* str
 int nrc_renderer_export_exr_gathered(nrc_renderer_t* r, const char* path, int root);
 /* EvaluateTimestampQueries + GetFrameTimeMS (src/NrcHpmRenderer.cu:495-530,556-559): synchronises; stage_ms may be
  * NULL or float[8] = {clear(0), gen_rays, prep_infer(0: fused into gen_rays), train, prep_train, inference, composite,
- * total}.  The renderer pipelines frames over four streams (train-ray generation, training, inference + compositing of
+ * total}; with self-training, "train" includes the tail inference and the target combine in front of the backward pass.  The renderer pipelines frames over four streams (train-ray generation, training, inference + compositing of
  * frame N run beside gen_rays of frame N+1; DESIGN.md section 4 "Frame graph"), so the stages overlap, include the time they
  * wait for each other, and do not add up; total = latency of the frame, which exceeds the frame interval. */
 float nrc_renderer_frame_time_ms(nrc_renderer_t* r, float* stage_ms);
@@ -340,7 +356,10 @@ int nrc_renderer_destroy(nrc_renderer_t* r);
 /* intermediate device buffers of the most recent frame, after synchronising all of the renderer's streams (tests /
  * multi-GPU; the sets rotate, so ask again after every Render): 0 primary colour+throughput [h][w][4], 1 primary info [h][w],
  * 2 nrc ray origin [h][w][4], 3 nrc ray dir [h][w][4] (train-grid pixels only unless set_full_vertex_images), 4 infer input [w*h][5], 5 infer output [w*h][3],
- * 6 train input [T][5], 7 train target [T][3], 8 train ring {head, tail, RayInfo[ring]}.  Buffers 4 and 5 are handed out in the
+ * 6 train input [T][5], 7 train target [T][3], 8 train ring {head, tail, RayInfo[ring]}; self-training (nrc_config.self_train) of the
+ * latest TRAINING frame, one entry per (ray i, sample s) at i * spp + s: 9 tail queries [T*spp][5] (zeros where there is no tail),
+ * 10 {light.rgb, factor} [T*spp][4] (factor 0: no tail), 11 tail inference outputs [T*spp][3] (defined where there is a tail) --
+ * NRC_ERR_INVALID for a renderer without self-training.  Buffers 4 and 5 are handed out in the
  * reference's order, query x*H+y (nrc/prep_infer_rays.comp:31), as a COPY made by this call: inside the renderer they are
  * tile-major (the 64 queries of an 8x8 pixel tile contiguous), and the cache's own API (nrc_cache_init / infer) speaks x*H+y
  * whatever its caller's order is.  Entries of pixels that did not scatter (info != 1) are zeros in both copies: the reference's zero-filled
@@ -376,7 +395,7 @@ int nrc_renderer_set_schedule(nrc_renderer_t* r, const nrc_schedule* schedule);
 int nrc_renderer_get_schedule(nrc_renderer_t* r, nrc_schedule* current, int* tuning_done);
 /* Schedules survive the process.  What the tuner settles on is remembered in a process-wide table under a key that names everything the
  * choice depends on -- "<arch>:<CUs>cu:<XCDs>xcd|<model>|vol2^<log2 voxels>|<w>x<h>.of<global w>x<global h>|train<batches>x<rays>.len<train ray length>"
- * (nrc_renderer_schedule_key) -- and a renderer created while its key is in the table starts on that schedule and skips the trials, so a run
+ * (nrc_renderer_schedule_key; a self-training renderer appends ".st": its frame graph has more work on the training stream) -- and a renderer created while its key is in the table starts on that schedule and skips the trials, so a run
  * shorter than the tuner's ~400 frames is a tuned run all the same.  nrc_schedule_cache_save writes the table (text: one "<key> <pri> <lag>
  * <window>" line per entry), nrc_schedule_cache_load merges a file into it (damaged lines are skipped; entries of other devices or models
  * simply never match); *n_entries (may be NULL) = entries read / written.  nrc_renderer_schedule_source says where the schedule in use came

@@ -66,8 +66,10 @@ struct AppConfig {
         }
     };
 
-    nrc_config c;
+    nrc_config c;      // c.self_train: self-training (include/nrc_hpm.h); 0 from both constructors, SetSelfTrain switches it
     HpmSceneConfig scene;
+
+    AppConfig& SetSelfTrain(bool on) { c.self_train = on ? 1u : 0u; return *this; }
 
     AppConfig() { nrc_config_default(&c); scene = HpmSceneConfig(c.scene_id); }
 

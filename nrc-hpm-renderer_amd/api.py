@@ -32,6 +32,7 @@ class NrcConfig(C.Structure):
         ("scene_id", C.c_uint32), ("train_ring_buf_size", C.c_float), ("train_spp", C.c_uint32),
         ("primary_ray_length", C.c_uint32), ("primary_ray_prob", C.c_float), ("train_ray_length", C.c_uint32),
         ("seed", C.c_uint32), ("compat_fix", C.c_uint32), ("hashgrid_log2_size", C.c_uint32),
+        ("self_train", C.c_uint32),      # since nrc_version() 0.3 (include/nrc_hpm.h: self-training)
     ]
 
 
@@ -619,7 +620,8 @@ class NeuralRadianceCache:
 # ------------------------------------------------------------------------------------------------------------------
 class NrcHpmRenderer:
     """en::NrcHpmRenderer (src/NrcHpmRenderer.cu).  `queue` arguments of the reference become the HIP stream."""
-    BUF = dict(primary=0, info=1, origin=2, dir=3, infer_input=4, infer_output=5, train_input=6, train_target=7, ring=8)
+    BUF = dict(primary=0, info=1, origin=2, dir=3, infer_input=4, infer_output=5, train_input=6, train_target=7, ring=8,
+               tail_query=9, tail_record=10, tail_output=11)
 
     def __init__(self, width, height, blend, camera, appConfig, hpmScene, nrc, tile=None, stream=None):
         self.L = load_library()
@@ -814,7 +816,7 @@ class NrcHpmRenderer:
         if name == "ring":
             return _wrap_device(p, nbytes.value, torch.int32, (nbytes.value // 4,))
         inner = {"primary": 4, "info": 1, "origin": 4, "dir": 4, "infer_input": 5, "infer_output": 3,
-                 "train_input": 5, "train_target": 3}[name]
+                 "train_input": 5, "train_target": 3, "tail_query": 5, "tail_record": 4, "tail_output": 3}[name]
         return _wrap_device(p, nbytes.value, torch.float32, (nbytes.value // (4 * inner), inner))
 
     def TrainGrid(self):

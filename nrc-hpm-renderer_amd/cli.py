@@ -44,6 +44,8 @@ def main(argv=None):
     ap.add_argument("--output", default="output")
     ap.add_argument("--export", default=None, help="write the final NRC image to this EXR")
     ap.add_argument("--gpus", type=int, default=1, help="ranks the frame is sharded over (one GPU each)")
+    ap.add_argument("--self-train", action="store_true",
+                    help="self-training: train paths end with the cache's own estimate (include/nrc_hpm.h, nrc_config.self_train)")
     args = ap.parse_args(argv)
     if args.benchmark and args.vdb and len(args.vdb) > 1:
         raise SystemExit("SkyRenderer ERROR: --benchmark needs a single --vdb volume (there is no reference image of a moving medium)")
@@ -72,6 +74,8 @@ def main(argv=None):
     if args.config and len(args.config) != 17:
         raise SystemExit("SkyRenderer ERROR: Argument count does not match requirements for AppConfig")
     cfg = api.AppConfig(["NRC-HPM-Renderer"] + (args.config or DEFAULT_ARGV))
+    if args.self_train:
+        cfg.c.self_train = 1
     sequence = []
     if args.vdb:
         bbox = io_vdb.union_bbox(args.vdb) if len(args.vdb) > 1 else None

@@ -1542,12 +1542,24 @@ __global__ __launch_bounds__(1024) void k_train_scan(DevFrame fr, TrainGrid tg, 
 // splits it: MODE 1 (k_train_start's work: tiny) takes the rays' start vertices from the images or the ring, writes them to `start`
 // ([T][6] floats) and the training INPUT they determine; MODE 2 traces from `start` and writes the TARGET -- it touches neither the
 // images nor the ring, so frame N's trace can run beside frame N + 1's on another stream.  Same arithmetic, same results, bit for bit.
-template <int MODE>
+//
+// ST (self-training, include/nrc_hpm.h: nrc_config.self_train; MODE 0 and 2): every sample also writes its tail record at i * spp + s --
+// the query at its last vertex (zeros: no tail) and {light.rgb, factor} (factor 0: the walk left the medium) -- for the tail inference
+// and k_self_train_combine; the targets written here stay those without a tail.  The records' pointers are the one trailing argument
+// `tail` of an ST instantiation; without ST the pack is empty, so k_prep_train<0|1|2> keep today's signature and code.
+struct TailOut {
+    float* query;        // [T * spp][5]
+    float4* rec;         // [T * spp]: light.rgb, factor
+};
+
+template <int MODE, bool ST = false, class... Tail>
 __global__ __launch_bounds__(256) void k_prep_train(DevScene sc, DevFrame fr, TrainGrid tg, const float4* __restrict__ origin,
                                                    const float4* __restrict__ dirs, const uint32_t* __restrict__ ring,
                                                    const uint32_t* __restrict__ scratch, float* __restrict__ train_in,
-                                                   float* __restrict__ train_target, uint32_t rays_per_wave, float* __restrict__ start)
+                                                   float* __restrict__ train_target, uint32_t rays_per_wave, float* __restrict__ start,
+                                                   Tail... tail)
 {
+    static_assert(sizeof...(Tail) == (ST ? 1u : 0u), "k_prep_train: the tail records are the one trailing argument of ST");
     NRC_RAISE_WAVE_PRIORITY(4);
     __shared__ uint32_t s_occ[kOccMaxWords];
     const uint32_t* occ = load_occupancy(sc, s_occ);
@@ -1631,6 +1643,18 @@ __global__ __launch_bounds__(256) void k_prep_train(DevScene sc, DevFrame fr, Tr
                 dir = new_ray_dir(c, dir, true);
             }
         }
+        if constexpr (ST) {
+            // a lane still walking has run all L vertices: it stands at its last scatter point with the direction after new_ray_dir
+            if (in_grid && tg.ring_size > 0) {
+                const TailOut to{tail...};
+                const size_t r = (size_t)i * tg.spp + s;
+                float q[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                if (walking) nrc_query(sc, cur, dir, q);
+#pragma unroll
+                for (int k = 0; k < 5; k++) to.query[5 * r + k] = q[k];
+                to.rec[r] = make_float4(light.x, light.y, light.z, walking ? factor : 0.0f);
+            }
+        }
         target = add(target, light);
     }
     const float fs = (float)tg.spp;
@@ -1646,6 +1670,28 @@ __global__ __launch_bounds__(256) void k_prep_train(DevScene sc, DevFrame fr, Tr
         train_target[3 * (size_t)i + 1] = fminf(8.0f, target.y);
         train_target[3 * (size_t)i + 2] = fminf(8.0f, target.z);
     }
+}
+
+// Self-training's training targets (include/nrc_hpm.h, nrc_config.self_train): the tail records of k_prep_train<MODE, true> and the cache's
+// inference at the tails -> the targets, in the specified order and without contraction (this file is compiled with -ffp-contract=off).
+// One thread per (train ray, channel).
+__global__ __launch_bounds__(256) void k_self_train_combine(uint32_t T, uint32_t spp, const float4* __restrict__ rec, const float* __restrict__ y,
+                                                           float* __restrict__ train_target)
+{
+    NRC_RAISE_WAVE_PRIORITY(4);
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 3u * T) return;
+    const uint32_t i = t / 3u, ch = t - 3u * i;
+    float acc = 0.0f;
+    for (uint32_t s = 0; s < spp; s++) {
+        const size_t r = (size_t)i * spp + s;
+        const float4 e = rec[r];
+        const float light = ch == 0u ? e.x : (ch == 1u ? e.y : e.z);
+        float u = light;
+        if (e.w != 0.0f) u = light + e.w * fmaxf(0.0f, y[3 * r + ch]);      // (no tail: nothing added -- 0 * Inf would be NaN)
+        acc = acc + u;
+    }
+    train_target[t] = fminf(8.0f, acc / (float)spp);
 }
 
 __global__ void k_ring_push(DevFrame fr, TrainGrid tg, const float4* __restrict__ origin, const float4* __restrict__ dirs,
@@ -2232,7 +2278,7 @@ void launch_mc_render(const DevScene& sc, const DevCamera& cam, const DevFrame& 
 
 void launch_prep_train(const DevScene& sc, const DevFrame& fr, const TrainGrid& tg, const float* info, const float* origin,
                        const float* dir, uint32_t* ring, uint32_t* scratch, float* train_in, float* train_target,
-                       hipStream_t s, float* start)
+                       hipStream_t s, float* start, float* tail_query, float* tail_rec)
 {
     const uint32_t T = tg.tw * tg.th;
     hipLaunchKernelGGL(k_train_scan, dim3(1), dim3(1024), 0, s, fr, tg, info, ring, scratch);
@@ -2241,7 +2287,10 @@ void launch_prep_train(const DevScene& sc, const DevFrame& fr, const TrainGrid& 
     // (measured on the bench frame with train ray length 32: 64 / 32 / 16 / 8 rays per wave -> 2 309 / 2 412 / 2 367 / 2 347 Msamples/s)
     const uint32_t rpw = train_paths_are_long(tg) ? 32u : 64u;
     const dim3 grid = rpw >= 64u ? pixel_grid(tg.tw, tg.th) : dim3(ceil_div(T, 4u * rpw), 1);
-    if (start == nullptr)
+    if (start == nullptr && tail_query != nullptr)      // self-training: the same launch, plus the tail records
+        hipLaunchKernelGGL((k_prep_train<0, true, TailOut>), grid, dim3(256), 0, s, sc, fr, tg, (const float4*)origin, (const float4*)dir, (const uint32_t*)ring,
+                           (const uint32_t*)scratch, train_in, train_target, rpw, (float*)nullptr, TailOut{tail_query, (float4*)tail_rec});
+    else if (start == nullptr)
         hipLaunchKernelGGL(k_prep_train<0>, grid, dim3(256), 0, s, sc, fr, tg, (const float4*)origin, (const float4*)dir, (const uint32_t*)ring,
                            (const uint32_t*)scratch, train_in, train_target, rpw, (float*)nullptr);
     else      // the split frame graph: start vertices + inputs here, the trace by launch_train_trace on a stream of its own
@@ -2256,12 +2305,26 @@ void launch_prep_train(const DevScene& sc, const DevFrame& fr, const TrainGrid& 
 bool train_paths_are_long(const TrainGrid& tg) { return tg.ray_length * tg.spp >= 4u; }
 
 // the trace of the split frame graph (k_prep_train<2>): from the start vertices launch_prep_train(..., start) left, to the training targets
-void launch_train_trace(const DevScene& sc, const DevFrame& fr, const TrainGrid& tg, const float* start, float* train_target, hipStream_t s)
+void launch_train_trace(const DevScene& sc, const DevFrame& fr, const TrainGrid& tg, const float* start, float* train_target, hipStream_t s,
+                        float* tail_query, float* tail_rec)
 {
     const uint32_t T = tg.tw * tg.th;
     const uint32_t rpw = 32u;
+    if (tail_query != nullptr) {
+        launch_last((k_prep_train<2, true, TailOut>), dim3(ceil_div(T, 4u * rpw), 1), dim3(256), 0u, s, sc, fr, tg, (const float4*)nullptr, (const float4*)nullptr,
+                    (const uint32_t*)nullptr, (const uint32_t*)nullptr, (float*)nullptr, train_target, rpw, const_cast<float*>(start),
+                    TailOut{tail_query, (float4*)tail_rec});
+        NRC_HIP(hipGetLastError());
+        return;
+    }
     launch_last(k_prep_train<2>, dim3(ceil_div(T, 4u * rpw), 1), dim3(256), 0u, s, sc, fr, tg, (const float4*)nullptr, (const float4*)nullptr,
                 (const uint32_t*)nullptr, (const uint32_t*)nullptr, (float*)nullptr, train_target, rpw, const_cast<float*>(start));
+    NRC_HIP(hipGetLastError());
+}
+
+void launch_self_train_combine(uint32_t T, uint32_t spp, const float* tail_rec, const float* tail_y, float* train_target, hipStream_t s)
+{
+    launch_last(k_self_train_combine, dim3(ceil_div(3u * T, 256u)), dim3(256), 0u, s, T, spp, (const float4*)tail_rec, tail_y, train_target);
     NRC_HIP(hipGetLastError());
 }
 

@@ -150,10 +150,15 @@ void launch_mc_render(const DevScene& sc, const DevCamera& cam, const DevFrame& 
 // ring: {uint head, uint tail, RayInfo[ring_size]}; scratch: uint32[2*T + 4]
 // start == nullptr: the whole of prep_train_rays.comp (scan, pop / trace / write, ring push).  start != nullptr (long train paths, the split
 // frame graph): scan, the rays' start vertices -> start ([T][6] floats) + the training inputs, ring push; launch_train_trace does the rest
+// tail_query / tail_rec (self-training, include/nrc_hpm.h): also write every sample's tail record -- [T*spp][5] queries, [T*spp][4]
+// {light.rgb, factor} -- (one-launch path and the trace; nullptr: none, the kernels of the reference's targets)
 void launch_prep_train(const DevScene& sc, const DevFrame& fr, const TrainGrid& tg, const float* info,
                        const float* origin, const float* dir, uint32_t* ring, uint32_t* scratch, float* train_in,
-                       float* train_target, hipStream_t s, float* start = nullptr);
-void launch_train_trace(const DevScene& sc, const DevFrame& fr, const TrainGrid& tg, const float* start, float* train_target, hipStream_t s);
+                       float* train_target, hipStream_t s, float* start = nullptr, float* tail_query = nullptr, float* tail_rec = nullptr);
+void launch_train_trace(const DevScene& sc, const DevFrame& fr, const TrainGrid& tg, const float* start, float* train_target, hipStream_t s,
+                        float* tail_query = nullptr, float* tail_rec = nullptr);
+// self-training's targets from the tail records and the cache's outputs at the tails (tail_y [T*spp][3]) -> train_target [T][3]
+void launch_self_train_combine(uint32_t T, uint32_t spp, const float* tail_rec, const float* tail_y, float* train_target, hipStream_t s);
 bool train_paths_are_long(const TrainGrid& tg);      // train ray length x spp >= 4 (quirk Q2 fixed, or a reference build with longer paths)
 
 void integrator_set_wave_priority_raise(int on);      // nrc_common.hpp: NRC_RAISE_WAVE_PRIORITY's run-time switch, this file's kernels

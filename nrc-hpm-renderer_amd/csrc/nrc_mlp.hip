@@ -2677,7 +2677,7 @@ Mlp::~Mlp()
     if (d_src_inf_ != d_src_fwd_ && d_src_inf_) dev_free(d_src_inf_);
     if (d_dst_) dev_free(d_dst_);
     void* ptrs[] = {d_w_, d_ema_, d_m_, d_v_, d_grad_, d_pk_infer_[0], d_pk_infer_[1], d_pk_fwd_, d_pk_bwd_, d_src_fwd_,
-                    d_src_bwd_, d_acts_, d_deltas_, d_slabs_, d_loss_part_, d_tiles_, d_tasks_, d_feat_[0], d_feat_[1], d_feat_[2], d_feat_[3], d_t16_train_,
+                    d_src_bwd_, d_acts_, d_deltas_, d_slabs_, d_loss_part_, d_tiles_, d_tasks_, d_feat_[0], d_feat_[1], d_feat_[2], d_feat_[3], d_feat_[4], d_t16_train_,
                     d_t16_ema_[0], d_t16_ema_[1], d_denc_, d_grad16_, d_grid_lists_, d_grid_counters_, d_grid_bin_entry0_, d_grid_fix_};
     for (void* p : ptrs)
         if (p) dev_free(p);
@@ -2732,7 +2732,8 @@ void Mlp::repack(hipStream_t s)
 }
 
 // generic-path encoding launch: HashGrid gathers from the fp16 table copy that belongs to the weight set in use
-// `slot` 0 = inference, 1 = training: the two may run concurrently on different streams and own separate feature buffers
+// `slot` 0 = inference, 1 = training, 4 = side inference (kSideSlot): they may run concurrently on different streams and own separate
+// feature buffers
 void Mlp::launch_features(const float* d_in, uint32_t n, bool use_ema, int slot, hipStream_t s, bool skip_zero, const uint32_t* live_list,
                           const uint32_t* live_count)
 {
@@ -2758,7 +2759,7 @@ void Mlp::launch_features(const float* d_in, uint32_t n, bool use_ema, int slot,
         else hipLaunchKernelGGL(k_encode_hash_list<2>, g, dim3(256), 0, s, d_in, tab, (uint32_t*)feat, n, lv, live_list, live_count, xc);
         return;
     }
-    if (slot == 0) {         // inference: level-major gathers and feature layout (k_encode_hash_lm / k_infer_gen<..., true>)
+    if (slot == kInferSlot || slot == kSideSlot) {      // inference: level-major gathers and feature layout (k_encode_hash_lm / k_infer_gen<..., true>)
         const dim3 g(ceil_div(n, 256), enc_dims_ / 2);
         const int sk = skip_zero ? 1 : 0;
         if (cfg_.dir_id == 0) hipLaunchKernelGGL(k_encode_hash_lm<0>, g, dim3(256), 0, s, d_in, tab, (uint32_t*)feat, n, lv, sk);
@@ -2825,19 +2826,20 @@ void Mlp::ensure_features(uint32_t n, int slot)
 }
 
 void Mlp::infer(const float* d_in, float* d_out, uint32_t n, bool use_ema, hipStream_t s, bool skip_zero_queries, const CompositeArgs* composite,
-                const uint32_t* live_list, const uint32_t* live_count)
+                const uint32_t* live_list, const uint32_t* live_count, int feat_slot)
 {
     if (n == 0) return;
+    if (feat_slot != kInferSlot && feat_slot != kSideSlot) throw std::logic_error("SkyRenderer ERROR: bad inference feature slot");
     if (composite != nullptr && !fused_) throw std::logic_error("SkyRenderer ERROR: compositing epilogue asked of a generic model");
     const uint4* img = (const uint4*)(use_ema ? d_pk_infer_[infer_set_] : d_pk_fwd_);
     if (!fused_) {
         // EMA inference of a Frequency(12) + OneBlob(4) model encodes inside the MLP kernel (image in the encoder's input order);
         // everything else runs the encoding kernel first
         const bool enc80 = enc80_generic_ && use_ema;
-        if (!enc80) launch_features(d_in, n, use_ema, 0, s, skip_zero_queries, live_list, live_count);
+        if (!enc80) launch_features(d_in, n, use_ema, feat_slot, s, skip_zero_queries, live_list, live_count);
         const float* skip_in = skip_zero_queries ? d_in : nullptr;
         const uint32_t* list = skip_zero_queries ? live_list : nullptr;      // renderer inference with the frame's live-query list (k_infer_gen)
-        const half_t* feat = enc80 ? nullptr : (const half_t*)d_feat_[0];
+        const half_t* feat = enc80 ? nullptr : (const half_t*)d_feat_[feat_slot];
         const int ks0 = (int)enc_dims_ / 16;
         uint32_t blocks = ceil_div(ceil_div(n, 32), 8);
         auto launch = [&](auto kernel, uint32_t threads, size_t lds, uint32_t per_cu) {

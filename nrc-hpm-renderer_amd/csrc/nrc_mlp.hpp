@@ -38,8 +38,14 @@ public:
     // skip_zero_queries (renderer only): 32-sample tiles whose queries are all exactly zero store 0 without running the network
     // live_list / live_count (renderer only, with skip_zero_queries): the indices of the queries that are not all zero, in any order
     // (k_gen_rays writes them); a model whose encoder gathers from a table walks the list instead of testing every query
+    // feat_slot: the generic models' feature buffer -- kInferSlot, or kSideSlot for a second inference caller that runs concurrently with
+    // the first on another stream (the renderer's self-training tails on the training stream beside its render inference)
+    static constexpr int kInferSlot = 0, kSideSlot = 4;
     void infer(const float* d_in, float* d_out, uint32_t n, bool use_ema, hipStream_t s, bool skip_zero_queries = false,
-               const CompositeArgs* composite = nullptr, const uint32_t* live_list = nullptr, const uint32_t* live_count = nullptr);
+               const CompositeArgs* composite = nullptr, const uint32_t* live_list = nullptr, const uint32_t* live_count = nullptr,
+               int feat_slot = kInferSlot);
+    // sizes kSideSlot's feature buffer for n EMA queries now (a buffer that grows later synchronises the device)
+    void reserve_side_slot(uint32_t n) { if (!encodes_in_kernel()) ensure_features(n, kSideSlot); }
     // the fused 6x64 inference kernel can composite in its epilogue (nrc/render.comp); the generic kernels cannot
     bool can_composite() const { return fused_; }
     // EMA inference encodes the raw queries inside the MLP kernel (no feature buffer sized by the launch)
@@ -108,8 +114,8 @@ private:
     bool sgd_ = false;           // nested optimizer: Adam (default) or SGD
     bool fused_ = false;         // north-star model (Frequency+OneBlob, 6x64): fully fused kernels; otherwise the generic path
     std::vector<MlpLayer> layers_;
-    void* d_feat_[4] = {nullptr, nullptr, nullptr, nullptr};     // generic path: fp16 features [n][enc_dims]; [0] inference, [1] training (encoded by backward), [2] [3] training (pre_encode, by parity)
-    uint32_t feat_n_[4] = {0, 0, 0, 0};
+    void* d_feat_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};     // generic path: fp16 features [n][enc_dims]; [0] inference, [1] training (encoded by backward), [2] [3] training (pre_encode, by parity), [4] side inference (kSideSlot)
+    uint32_t feat_n_[5] = {0, 0, 0, 0, 0};
     int infer_set_ = 0;          // which of the double-buffered inference (EMA) image / table sets is current
     uint32_t n_mlp_ = 0;         // matrix parameters; (posID 0) the hash-grid table [entry][2] follows them in every vector
     bool hash_ = false;
