@@ -11,12 +11,9 @@
 #include <string>
 
 #include "../../include/nrc_hpm.h"
+#include "nrc_fail.hpp"      // fail(): the error convention, shared with the device-free headers
 
 namespace nrc {
-
-// Reference error convention: Log::Error(msg, true) throws std::runtime_error("SkyRenderer ERROR: " + msg)
-// (src/Log.cpp:16-20); ASSERT_CUDA does the same (include/engine/cuda_common.hpp:14).
-[[noreturn]] inline void fail(const std::string& msg) { throw std::runtime_error("SkyRenderer ERROR: " + msg); }
 
 struct HipError : std::runtime_error {
     explicit HipError(const std::string& m) : std::runtime_error("SkyRenderer ERROR: " + m) {}

@@ -1,0 +1,577 @@
+// host_logic_main.cpp -- the library's device-free host logic (csrc/nrc_schedule.hpp, nrc_checkpoint.hpp, nrc_occupancy.hpp) driven on
+// the CPU; tests/test_host_logic_asan.py builds this with AddressSanitizer + UndefinedBehaviorSanitizer and runs it.
+//   host_logic_main <scratch directory> <path of nrc-hpm-renderer_amd/schedules.txt>
+// Every CHECK compares a value; the last line printed is "host_logic: <n> cases, <m> checks" (exit status 1 if any check failed).
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "../../nrc-hpm-renderer_amd/csrc/nrc_checkpoint.hpp"
+#include "../../nrc-hpm-renderer_amd/csrc/nrc_occupancy.hpp"
+#include "../../nrc-hpm-renderer_amd/csrc/nrc_schedule.hpp"
+
+using namespace nrc;
+
+static int g_cases = 0, g_checks = 0, g_failed = 0;
+static const char* g_case = "";
+#define CHECK(cond)                                                                                          \
+    do {                                                                                                     \
+        g_checks++;                                                                                          \
+        if (!(cond)) { g_failed++; std::printf("FAILED %s:%d [%s] %s\n", __FILE__, __LINE__, g_case, #cond); } \
+    } while (0)
+static void begin_case(const char* name) { g_case = name; g_cases++; }
+
+static std::string g_dir;
+static std::string write_file(const std::string& name, const std::string& bytes)
+{
+    const std::string path = g_dir + "/" + name;
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f || std::fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size()) { std::printf("cannot write %s\n", path.c_str()); std::exit(2); }
+    std::fclose(f);
+    return path;
+}
+template <class F>
+static std::string message_of(F f)
+{
+    try { f(); } catch (const std::exception& e) { return e.what(); }
+    return "";
+}
+static bool has(const std::string& s, const char* part) { return s.find(part) != std::string::npos; }
+
+// ======================================================================================== 1. schedule-cache text
+using Table = std::map<std::string, ScheduleEntry>;
+static bool same_table(const Table& a, const Table& b)
+{
+    if (a.size() != b.size()) return false;
+    for (const auto& kv : a) {
+        auto it = b.find(kv.first);
+        if (it == b.end() || it->second.pri != kv.second.pri || it->second.lag != kv.second.lag || it->second.window != kv.second.window) return false;
+    }
+    return true;
+}
+// the table a fresh cache holds after load(text), and the count load returned
+static Table loaded(const std::string& text, int* n = nullptr)
+{
+    ScheduleCache c;
+    const int got = c.load(write_file("sched_in.txt", text).c_str());
+    if (n) *n = got;
+    return c.table;
+}
+static void schedule_cache_cases()
+{
+    begin_case("schedule cache: round trip");
+    {
+        ScheduleCache c;
+        const Table want = {{"gfx950:256cu:8xcd|a", {0, 2, 2}}, {"gfx950:256cu:8xcd|b.st", {1, 64, 32}}, {"k", {1, 1, 0}}};
+        for (const auto& kv : want) c.put(kv.first, kv.second);
+        const std::string path = g_dir + "/sched_rt.txt";
+        CHECK(c.save(path.c_str()) == 3);
+        c.table.clear();
+        ScheduleEntry e;
+        CHECK(!c.find("k", &e));
+        CHECK(c.load(path.c_str()) == 3);      // (the comment line save writes first is not an entry)
+        CHECK(same_table(c.table, want));
+        CHECK(c.find("k", &e) && e.pri == 1 && e.lag == 1 && e.window == 0);
+    }
+    begin_case("schedule cache: damaged and odd input");
+    {
+        int n = -1;
+        CHECK(loaded("", &n).empty() && n == 0);
+        CHECK(same_table(loaded("# a comment\nfree text here\n\n   \nk 0 2 2\n# k2 1 2 2\n", &n), {{"k", {0, 2, 2}}}) && n == 1);
+        // four fields make an entry: three do not, and what follows the fourth is not looked at
+        CHECK(same_table(loaded("k3 0 2\nk5 1 3 16 99\n", &n), {{"k5", {1, 3, 16}}}) && n == 1);
+        // nrc_schedule's ranges: cost_order_lag 1..64, xcd_window 0..32
+        CHECK(same_table(loaded("a 0 0 2\nb 0 65 2\nc 0 2 -1\nd 0 2 33\ne 0 1 0\nf 0 64 32\n", &n), {{"e", {0, 1, 0}}, {"f", {0, 64, 32}}}) && n == 2);
+        CHECK(same_table(loaded("k 7 2 2\n"), {{"k", {1, 2, 2}}}));      // camera_priority_low is a flag
+        const std::string k767(767, 'k'), k768(768, 'k'), k900(900, 'k');
+        CHECK(same_table(loaded(k767 + " 1 2 2\n"), {{k767, {1, 2, 2}}}));
+        CHECK(loaded(k768 + " 1 2 2\n").empty());      // (a key the reader cannot hold is no entry: never a truncated key)
+        CHECK(loaded(k900 + " 1 2 2\nk 0 2 2\n").size() == 1);
+        CHECK(same_table(loaded("a 0 2 2\nlast 1 3 16"), {{"a", {0, 2, 2}}, {"last", {1, 3, 16}}}));      // no newline at the end
+        const std::string hi = "k\xc3\xa9\xff|x";
+        CHECK(same_table(loaded(hi + " 0 2 2\n"), {{hi, {0, 2, 2}}}));      // bytes >= 0x80 are key bytes like any other
+        // an embedded NUL ends what the reader sees of its line: that line is damaged, the next one is not
+        CHECK(same_table(loaded(std::string("bad", 3) + std::string(1, '\0') + "key 0 2 2\nk 1 2 2\n"), {{"k", {1, 2, 2}}}));
+        CHECK(same_table(loaded(std::string("k0 1 2", 6) + std::string(1, '\0') + " 2\nk 1 2 2\n"), {{"k", {1, 2, 2}}}));
+        CHECK(has(message_of([] { ScheduleCache c; c.load((g_dir + "/no_such_file").c_str()); }), "SkyRenderer ERROR: cannot read schedule cache "));
+    }
+    begin_case("schedule cache: a line longer than the read buffer");
+    {
+        // One line is one entry at most.  The reader takes lines in pieces of 1 023 bytes; as moved out of nrc_api.hip it parsed every
+        // further piece of an over-long line as a line of its own: the first text below gave {head, key} (count 2), the second {head}.
+        // Now the head of the line is read as any line is and the rest of it is dropped.
+        int n = -1;
+        const std::string pad(1023 - 11, ' ');      // "head 1 3 16" + blanks fill the first piece exactly
+        CHECK(same_table(loaded("head 1 3 16" + pad + "key 0 2 2\nafter 0 2 0\n", &n), {{"head", {1, 3, 16}}, {"after", {0, 2, 0}}}) && n == 2);
+        CHECK(same_table(loaded("head 1 3 16" + std::string(3000, 'x') + "\nafter 0 2 0\n", &n), {{"head", {1, 3, 16}}, {"after", {0, 2, 0}}}) && n == 2);
+        CHECK(same_table(loaded("# comment" + std::string(2100, ' ') + "key 0 2 2\nafter 0 2 0\n", &n), {{"after", {0, 2, 0}}}) && n == 1);
+        CHECK(same_table(loaded(std::string(1500, ' ') + "key 0 2 2", &n), {}) && n == 0);      // over-long and last, no newline
+    }
+}
+
+// ======================================================================================== 2. checkpoint file
+static std::string file_bytes(const std::string& path)
+{
+    std::string s;
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) return s;
+    char buf[4096];
+    size_t n;
+    while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) s.append(buf, n);
+    std::fclose(f);
+    return s;
+}
+static void checkpoint_cases()
+{
+    nrc_config cfg{};
+    cfg.pos_id = 3; cfg.dir_id = 0; cfg.nn_width = 64; cfg.nn_depth = 6;
+    const uint32_t N = 37;
+    const CkptHeader want = ckpt_header_of(cfg, N, 1234);
+    std::vector<std::vector<float>> v(4, std::vector<float>(N));
+    for (int w = 0; w < 4; w++) for (uint32_t i = 0; i < N; i++) v[w][i] = (float)(w * 1000 + (int)i) + 0.25f;
+    const std::string path = g_dir + "/ckpt.bin";
+
+    begin_case("checkpoint: header and round trip");
+    {
+        CHECK(std::memcmp(want.magic, "NRCCKPT1", 8) == 0 && want.pos_id == 3 && want.width == 64 && want.depth == 6 && want.hash_log2 == 0 && want.n_tcnn == N && want.step == 1234);
+        nrc_config hg{};      // the HashGrid model: table size 2^19 unless the config names one
+        CHECK(ckpt_header_of(hg, 1, 0).hash_log2 == 19);
+        hg.hashgrid_log2_size = 15;
+        CHECK(ckpt_header_of(hg, 1, 0).hash_log2 == 15);
+        for (uint32_t z : want.zero) CHECK(z == 0);
+        int order = 0;
+        ckpt_write(path.c_str(), want, [&](int which, std::vector<float>& t) { CHECK(which == order++ && t.size() == N); t = v[which]; });
+        CHECK(order == 4);
+        CHECK(file_bytes(path).size() == 64 + 4 * 4 * (size_t)N);
+        uint32_t step = 0;
+        CkptHeader other_step = want;
+        other_step.step = 7;      // (the step is read, not compared)
+        const auto back = ckpt_read(path.c_str(), other_step, &step);
+        CHECK(step == 1234 && back.size() == 4);
+        for (int w = 0; w < 4; w++) CHECK(back[w] == v[w]);
+        CHECK(has(message_of([&] { ckpt_write((g_dir + "/no_dir/x").c_str(), want, [](int, std::vector<float>&) {}); }), "cannot write checkpoint "));
+        CHECK(has(message_of([&] { uint32_t s; ckpt_read((g_dir + "/no_such_file").c_str(), want, &s); }), "cannot read checkpoint "));
+    }
+    begin_case("checkpoint: rejected files");
+    {
+        const std::string good = file_bytes(path);
+        auto verdict = [&](const std::string& bytes, const CkptHeader& model) {
+            const std::string p = write_file("ckpt_bad.bin", bytes);
+            uint32_t step = 99;
+            const std::string m = message_of([&] { ckpt_read(p.c_str(), model, &step); });
+            CHECK(m.empty() || step == 99);      // a rejected file leaves the step alone
+            return m;
+        };
+        const char *truncated = "SkyRenderer ERROR: checkpoint is truncated: ", *foreign = "SkyRenderer ERROR: checkpoint is not of this model (encoding / width / depth / table size): ",
+                   *trailing = "SkyRenderer ERROR: checkpoint has trailing bytes: ";
+        CHECK(verdict(good, want).empty());
+        CHECK(has(verdict("", want), truncated));
+        CHECK(has(verdict(good.substr(0, 63), want), truncated));
+        CHECK(has(verdict(good.substr(0, 64), want), truncated));                   // header only
+        CHECK(has(verdict(good.substr(0, good.size() - 4), want), truncated));      // one float short
+        CHECK(has(verdict(good + "x", want), trailing));
+        std::string magic = good;
+        magic[7] = '2';
+        CHECK(has(verdict(magic, want), foreign));
+        // each field that names the model, off by one in the file (header words 2..7 behind the 8-byte magic)
+        for (size_t field = 0; field < 6; field++) {
+            std::string b = good;
+            uint32_t x;
+            std::memcpy(&x, &b[8 + 4 * field], 4);
+            x += 1;
+            std::memcpy(&b[8 + 4 * field], &x, 4);
+            CHECK(has(verdict(b, want), foreign));
+        }
+        // a count the file asks for is never allocated or read: it is compared with the model's
+        for (uint32_t n : {0u, 0xFFFFFFFFu}) {
+            std::string b = good;
+            std::memcpy(&b[8 + 4 * 5], &n, 4);
+            CHECK(has(verdict(b, want), foreign));
+        }
+    }
+}
+
+// ======================================================================================== 3. occupancy builders
+static const uint32_t kOccMaxWords = 2048;      // nrc_integrator.hpp
+// brute-force restatement.  bits: the smallest cubic cell of 2^sh >= 8 voxels whose grid has at most 32 * max_words cells; a cell's bit
+// is set when a non-zero voxel lies inside it.  boxes: cells of 8^3 voxels, occupied when a non-zero voxel lies inside or within one
+// voxel; maximal runs along x, in world coordinates (the volume centred on the origin, `size` wide)
+static void occupancy_equals_brute_force(const std::vector<uint8_t>& vol, uint32_t nx, uint32_t ny, uint32_t nz, const float size[3], uint32_t max_words,
+                                         uint32_t* shift_out = nullptr)
+{
+    const OccupancyBits got = build_occupancy_bits(vol.data(), nx, ny, nz, max_words);
+    uint32_t sh = 3;
+    for (;; sh++) {
+        const uint64_t c = 1ull << sh;
+        if (((nx + c - 1) / c) * ((ny + c - 1) / c) * ((nz + c - 1) / c) <= 32ull * max_words) break;
+    }
+    const uint32_t c = 1u << sh, gx = (nx + c - 1) / c, gy = (ny + c - 1) / c, gz = (nz + c - 1) / c;
+    CHECK(got.shift == sh && got.gx == gx && got.gy == gy && got.gz == gz);
+    CHECK(got.bits.size() % 4 == 0 && got.bits.size() * 32 >= (size_t)gx * gy * gz && got.bits.size() <= (((size_t)gx * gy * gz + 31) / 32 + 3));
+    if (shift_out) *shift_out = got.shift;
+    std::vector<uint8_t> cell((size_t)gx * gy * gz, 0), near((size_t)((nx + 7) / 8) * ((ny + 7) / 8) * ((nz + 7) / 8), 0);
+    const uint32_t bx = (nx + 7) / 8, by = (ny + 7) / 8, bz = (nz + 7) / 8;
+    for (uint32_t z = 0; z < nz; z++)
+        for (uint32_t y = 0; y < ny; y++)
+            for (uint32_t x = 0; x < nx; x++) {
+                if (!vol[((size_t)z * ny + y) * nx + x]) continue;
+                cell[((size_t)(z / c) * gy + y / c) * gx + x / c] = 1;
+                for (int dz = -1; dz <= 1; dz++)
+                    for (int dy = -1; dy <= 1; dy++)
+                        for (int dx = -1; dx <= 1; dx++) {
+                            const long X = (long)x + dx, Y = (long)y + dy, Z = (long)z + dz;
+                            if (X < 0 || Y < 0 || Z < 0 || X >= (long)nx || Y >= (long)ny || Z >= (long)nz) continue;
+                            near[((size_t)(Z / 8) * by + (size_t)(Y / 8)) * bx + (size_t)(X / 8)] = 1;
+                        }
+            }
+    bool bits_equal = true;
+    for (size_t i = 0; i < got.bits.size() * 32; i++) {
+        const bool bit = (got.bits[i >> 5] >> (i & 31)) & 1u;
+        if (bit != (i < cell.size() && cell[i])) bits_equal = false;
+    }
+    CHECK(bits_equal);
+    std::vector<float> want;
+    auto world = [&](int axis, uint32_t voxel, uint32_t n) { return (float)(-0.5 * (double)size[axis] + ((double)size[axis] / n) * (double)voxel); };
+    for (uint32_t z = 0; z < bz; z++)
+        for (uint32_t y = 0; y < by; y++)
+            for (uint32_t x = 0; x < bx; x++) {
+                const uint8_t* row = &near[((size_t)z * by + y) * bx];
+                if (!row[x] || (x > 0 && row[x - 1])) continue;      // a run starts here
+                uint32_t e = x;
+                while (e + 1 < bx && row[e + 1]) e++;
+                want.insert(want.end(), {world(0, 8 * x, nx), world(1, 8 * y, ny), world(2, 8 * z, nz), world(0, std::min(8 * (e + 1), nx), nx),
+                                         world(1, std::min(8 * (y + 1), ny), ny), world(2, std::min(8 * (z + 1), nz), nz)});
+            }
+    CHECK(build_occupancy_boxes(vol.data(), nx, ny, nz, size) == want);
+}
+static void occupancy_cases()
+{
+    const float size[3] = {61.3f, 107.5f, 33.0f};
+    std::mt19937 rng(20240607);
+    const uint32_t dims[6] = {1, 7, 8, 9, 17, 64};
+    begin_case("occupancy: random sparse volumes");
+    for (int round = 0; round < 24; round++) {
+        const uint32_t nx = dims[rng() % 6], ny = dims[rng() % 6], nz = dims[rng() % 6];
+        std::vector<uint8_t> vol((size_t)nx * ny * nz, 0);
+        const uint32_t one_in = 1u << (rng() % 10);
+        for (auto& b : vol) b = (rng() % one_in == 0) ? (uint8_t)(1 + rng() % 255) : 0;
+        occupancy_equals_brute_force(vol, nx, ny, nz, size, kOccMaxWords);
+    }
+    begin_case("occupancy: empty, corners, full");
+    {
+        const uint32_t nx = 17, ny = 9, nz = 64;
+        std::vector<uint8_t> vol((size_t)nx * ny * nz, 0);
+        occupancy_equals_brute_force(vol, nx, ny, nz, size, kOccMaxWords);
+        CHECK(build_occupancy_boxes(vol.data(), nx, ny, nz, size).empty());
+        for (int corner = 0; corner < 8; corner++) {
+            std::fill(vol.begin(), vol.end(), (uint8_t)0);
+            vol[((size_t)((corner & 4) ? nz - 1 : 0) * ny + ((corner & 2) ? ny - 1 : 0)) * nx + ((corner & 1) ? nx - 1 : 0)] = 255;
+            occupancy_equals_brute_force(vol, nx, ny, nz, size, kOccMaxWords);
+            // one run of cells; a voxel in the last row of y (8 of 9) is within one voxel of the cell row below as well
+            CHECK(build_occupancy_boxes(vol.data(), nx, ny, nz, size).size() == ((corner & 2) ? 12u : 6u));
+        }
+        std::fill(vol.begin(), vol.end(), (uint8_t)1);
+        occupancy_equals_brute_force(vol, nx, ny, nz, size, kOccMaxWords);
+        CHECK(build_occupancy_boxes(vol.data(), nx, ny, nz, size).size() == 6u * 2 * 8);      // one run per (y, z) row of cells
+    }
+    begin_case("occupancy: cells larger than 8 voxels");
+    {
+        // 41 x 40 x 40 = 65 600 cells of 8^3 are more than the 65 536 the table holds: cells of 16^3
+        const uint32_t nx = 328, ny = 320, nz = 320;
+        std::vector<uint8_t> vol((size_t)nx * ny * nz, 0);
+        for (int k = 0; k < 4000; k++) vol[rng() % vol.size()] = 200;
+        vol.back() = 1;
+        uint32_t shift = 0;
+        occupancy_equals_brute_force(vol, nx, ny, nz, size, kOccMaxWords, &shift);
+        CHECK(shift == 4);
+        std::vector<uint8_t> small(64 * 64 * 64, 0);      // the same rule against a small table: 4 words hold 128 cells, 8^3 cells of 8 voxels do not fit
+        small[12345] = 9;
+        occupancy_equals_brute_force(small, 64, 64, 64, size, 4, &shift);
+        CHECK(shift == 4);
+    }
+    begin_case("occupancy: volume size limits");
+    {
+        CHECK(message_of([] { check_volume_size(1024, 1024, 1024); }).empty());
+        CHECK(has(message_of([] { check_volume_size(1u << 24, 1, 1); }), "SkyRenderer ERROR: density volume too large"));
+        CHECK(has(message_of([] { check_volume_size(1, 4096, 4096); }), "density volume too large"));
+        CHECK(has(message_of([] { check_volume_size(2048, 1024, 1024); }), "density volume too large"));
+    }
+}
+
+// ======================================================================================== 4. the tuner against a scripted clock
+// A frame loop shaped like Renderer::render: make room in the event pool, let the tuner step, take the frame's event set.  The clock is
+// scripted: a frame takes cost(schedule in use) milliseconds on the "GPU", which has finished every frame but the newest `in_flight` ones
+// (2: a pipeline that stays full; 0: a host that lets it drain before every frame).
+struct Sim {
+    ScheduleTuner tuner;
+    EventPoolIndex idx;
+    size_t pool_size = 0;
+    uint64_t frame = 0;
+    bool stage_events = true, multi_stream = true;
+    std::function<double(const Schedule&)> cost = [](const Schedule&) { return 1.0; };
+    uint64_t in_flight = 2;
+    long fail_wait_at_frame = -1;       // wait_gen_rays reports a communicator failure from this frame on
+    std::vector<double> start_ms;       // per event set: the frame's start time, and which frame it was
+    std::vector<uint64_t> frame_of;
+    double now_ms = 0.0;
+    long host_calls = 0;
+    std::vector<Schedule> history;      // the schedule each frame ran on
+
+    Sim(bool xcd_ok, const std::string& key) : tuner(xcd_ok, key) {}
+    void in_pool(size_t set) const
+    {
+        if (set >= pool_size) { std::printf("FAILED [%s] the tuner asked about event set %zu of %zu\n", g_case, set, pool_size); std::abort(); }
+    }
+    // ---- ScheduleTuner::step's Host
+    bool gen_rays_done(size_t set) { in_pool(set); host_calls++; return frame_of[set] + in_flight < frame; }
+    bool start_interval_ms(size_t a, size_t b, float* ms) { in_pool(a); in_pool(b); host_calls++; *ms = (float)(start_ms[b] - start_ms[a]); return true; }
+    bool wait_gen_rays(size_t set) { in_pool(set); host_calls++; return !(fail_wait_at_frame >= 0 && (long)frame >= fail_wait_at_frame); }
+
+    void render()
+    {
+        if (idx.must_grow(pool_size)) { pool_size++; start_ms.push_back(0.0); frame_of.push_back(0); }
+        tuner.step(TunerStep{frame, idx.used, pool_size, idx.last, idx.epoch, stage_events, multi_stream}, *this);
+        const size_t k = idx.take();
+        in_pool(k);
+        start_ms[k] = now_ms;
+        frame_of[k] = frame;
+        now_ms += cost(tuner.now());
+        history.push_back(tuner.now());
+        idx.timed = true;
+        frame++;
+    }
+    bool done() const { nrc_schedule s; int d = 0; tuner.get(&s, &d); return d != 0; }
+    nrc_schedule get() const { nrc_schedule s; tuner.get(&s, nullptr); return s; }
+    // renders until tuning is done (at most `limit` frames); the number of frames rendered by then
+    uint64_t run_until_done(uint64_t limit = 20000) { while (!done() && frame < limit) render(); return frame; }
+    size_t frames_with(const std::function<bool(const Schedule&)>& p) const { size_t n = 0; for (const Schedule& s : history) n += p(s) ? 1 : 0; return n; }
+};
+static bool is(const nrc_schedule& s, int pri, int lag, int window) { return s.camera_priority_low == pri && s.cost_order_lag == lag && s.xcd_window == window; }
+static const nrc_schedule kFree = {-1, -1, -1, -1};
+static const uint64_t kTrial = ScheduleTuner::kSettle + ScheduleTuner::kMeasure;      // frames a value is held
+
+static void tuner_cases()
+{
+    ScheduleCache& cache = ScheduleCache::get();
+    ScheduleEntry e;
+    auto pri_costs = [](double with_pri) { return [with_pri](const Schedule& s) { return s.pri ? with_pri : 1.0; }; };
+
+    begin_case("tuner: nothing before kWarm frames, without stage events, on one stream");
+    {
+        Sim a(true, "t.warm");
+        for (uint64_t f = 0; f < ScheduleTuner::kWarm; f++) a.render();
+        CHECK(a.host_calls == 0 && a.frames_with([](const Schedule& s) { return s.pri != 0 || s.lag != 2 || s.window != 2; }) == 0 && !a.done());
+        CHECK(std::string(a.tuner.source()) == "default" && std::string(a.tuner.key()) == "t.warm");
+        Sim b(true, "t.noev"), c(true, "t.single");
+        b.stage_events = false;
+        c.multi_stream = false;
+        for (int f = 0; f < 1000; f++) { b.render(); c.render(); }
+        for (Sim* s : {&b, &c}) CHECK(s->host_calls == 0 && !s->done() && is(s->get(), 0, 2, 2) && s->frames_with([](const Schedule& q) { return q.pri != 0 || q.lag != 2 || q.window != 2; }) == 0);
+        CHECK(!cache.find("t.warm", &e) && !cache.find("t.noev", &e) && !cache.find("t.single", &e));
+    }
+    begin_case("tuner: adoption threshold and the ambiguous band");
+    {
+        // lag and window pinned: one knob, three trials (base, alternative, base) of kTrial frames a round
+        const nrc_schedule only_pri = {-1, 2, 2, -1};
+        struct { const char* key; double cost; size_t rounds; int adopted; } rows[] = {
+            {"t.band5", 0.95, 1, 1},      // 5 % faster: outside the band, beyond the 1.5 % threshold
+            {"t.band1", 0.99, 3, 0},      // 1 % faster: in the band, replayed; the sums say 1 %: not adopted
+            {"t.band2", 0.975, 3, 1},     // 2.5 % faster: in the band, replayed; the sums say 2.5 %: adopted
+            {"t.slower", 1.05, 1, 0},      // slower: decided at once
+        };
+        for (const auto& row : rows) {
+            Sim s(true, row.key);
+            s.tuner.set(only_pri, 0);
+            CHECK(std::string(s.tuner.source()) == "pinned in part");
+            s.cost = pri_costs(row.cost);
+            const uint64_t frames = s.run_until_done();
+            // the trials start at frame kWarm; a round is judged by the step that finds its last frame out of the pipeline, and the frame
+            // of the step that decides already runs on what it decided
+            CHECK(frames == ScheduleTuner::kWarm + row.rounds * (3 * kTrial + s.in_flight + 1) + 1);
+            CHECK(s.frames_with([](const Schedule& q) { return q.pri == 1; }) == kTrial * row.rounds + (row.adopted ? 1 : 0));
+            CHECK(s.frames_with([](const Schedule& q) { return q.lag != 2 || q.window != 2; }) == 0);
+            CHECK(is(s.get(), row.adopted, 2, 2) && std::string(s.tuner.source()) == "tuner");
+            CHECK(cache.find(row.key, &e) && e.pri == row.adopted && e.lag == 2 && e.window == 2);
+        }
+    }
+    begin_case("tuner: knob order, each on top of the previous choice, cache entry");
+    {
+        auto costs = [](const Schedule& s) { return (s.pri ? 0.9 : 1.0) * (s.lag == 3 ? 0.9 : 1.0) * (s.window == 16 ? 0.9 : s.window == 0 ? 1.1 : 1.0); };
+        Sim s(true, "t.order");
+        s.cost = costs;
+        s.run_until_done();
+        CHECK(is(s.get(), 1, 3, 16) && std::string(s.tuner.source()) == "tuner");
+        // phases in the order priority, lag, window: once a later knob has left its start value an earlier one never changes again
+        size_t first_lag = 0, first_win = 0, last_pri_change = 0, last_lag_change = 0;
+        for (size_t f = 1; f < s.history.size(); f++) {
+            if (s.history[f].pri != s.history[f - 1].pri) last_pri_change = f;
+            if (s.history[f].lag != s.history[f - 1].lag) last_lag_change = f;
+            if (!first_lag && s.history[f].lag != 2) first_lag = f;
+            if (!first_win && s.history[f].window != 2) first_win = f;
+        }
+        CHECK(last_pri_change > 0 && last_pri_change < first_lag && last_lag_change < first_win);
+        CHECK(s.frames_with([](const Schedule& q) { return q.lag != 2 && q.pri != 1; }) == 0);                       // lag tried on top of pri = 1
+        CHECK(s.frames_with([](const Schedule& q) { return q.window != 2 && (q.pri != 1 || q.lag != 3); }) == 0);    // window on top of both
+        CHECK(s.frames_with([](const Schedule& q) { return q.window == 0; }) == kTrial);                             // both alternatives of the window, once
+        CHECK(cache.find("t.order", &e) && e.pri == 1 && e.lag == 3 && e.window == 16);
+        Sim again(true, "t.order");      // a second renderer of this kind starts on the result
+        CHECK(again.done() && is(again.get(), 1, 3, 16) && std::string(again.tuner.source()) == "cache");
+        for (int f = 0; f < 400; f++) again.render();
+        CHECK(again.host_calls == 0 && again.frames_with([](const Schedule& q) { return q.pri != 1 || q.lag != 3 || q.window != 16; }) == 0);
+
+        Sim no_xcd(false, "t.noxcd");      // a device without eight XCDs: the window is never tried
+        no_xcd.cost = costs;
+        CHECK(is(no_xcd.get(), 0, 2, 0));
+        const uint64_t frames = no_xcd.run_until_done();
+        CHECK(no_xcd.done() && is(no_xcd.get(), 1, 3, 0) && std::string(no_xcd.tuner.source()) == "tuner");
+        CHECK(no_xcd.frames_with([](const Schedule& q) { return q.window != 0; }) == 0);
+        // two knobs, one round each: done with the step that adopted the lag
+        CHECK(frames == ScheduleTuner::kWarm + 2 * (3 * kTrial + no_xcd.in_flight + 1) + 1);
+        CHECK(no_xcd.frames_with([](const Schedule& q) { return q.lag == 3; }) == kTrial + 1);
+        CHECK(cache.find("t.noxcd", &e) && e.pri == 1 && e.lag == 3 && e.window == 0);
+    }
+    begin_case("tuner: pinned knobs");
+    {
+        Sim all(true, "t.pinned");
+        all.cost = [](const Schedule& s) { return s.pri ? 2.0 : 1.0; };
+        all.tuner.set({1, 3, 16, 1}, 0);
+        CHECK(all.done() && std::string(all.tuner.source()) == "pinned" && is(all.get(), 1, 3, 16) && all.get().composite_defer == 1);
+        for (int f = 0; f < 400; f++) all.render();
+        CHECK(all.host_calls == 0 && all.frames_with([](const Schedule& q) { return q.pri != 1 || q.lag != 3 || q.window != 16 || q.defer != 1; }) == 0);
+        CHECK(std::string(all.tuner.source()) == "pinned" && !cache.find("t.pinned", &e));
+        Sim two(false, "t.pinned2");      // without eight XCDs the window counts as pinned
+        two.tuner.set({0, 2, -1, -1}, 0);
+        CHECK(two.done() && std::string(two.tuner.source()) == "pinned");
+        Sim part(true, "t.part");
+        part.cost = [](const Schedule& s) { return (s.pri ? 0.5 : 1.0) * (s.window == 16 ? 0.9 : 1.0); };
+        part.tuner.set({0, -1, -1, -1}, 0);
+        CHECK(!part.done() && std::string(part.tuner.source()) == "pinned in part");
+        part.run_until_done();
+        CHECK(part.frames_with([](const Schedule& q) { return q.pri != 0; }) == 0 && is(part.get(), 0, 2, 16));
+        CHECK(has(message_of([&] { part.tuner.set({0, 0, -1, -1}, 0); }), "SkyRenderer ERROR: nrc_schedule: cost_order_lag must be 1..64, xcd_window 0..32"));
+        CHECK(has(message_of([&] { part.tuner.set({0, 65, -1, -1}, 0); }), "nrc_schedule:") && has(message_of([&] { part.tuner.set({0, 2, 33, -1}, 0); }), "nrc_schedule:"));
+    }
+    begin_case("tuner: a host that lets the pipeline drain");
+    {
+        Sim s(true, "t.stall");
+        s.cost = pri_costs(0.5);
+        s.in_flight = 0;      // the previous frame is always complete: every measured frame counts as a stall
+        const uint64_t frames = s.run_until_done();
+        // three attempts at the first knob's sequence, then the base schedule stands
+        CHECK(s.done() && is(s.get(), 0, 2, 2) && std::string(s.tuner.source()) == "default" && !cache.find("t.stall", &e));
+        CHECK(s.frames_with([](const Schedule& q) { return q.pri == 1; }) == 3 * kTrial && s.frames_with([](const Schedule& q) { return q.lag != 2 || q.window != 2; }) == 0);
+        CHECK(frames == ScheduleTuner::kWarm + 3 * (3 * kTrial + 1) + 1);
+        for (int f = 0; f < 200; f++) s.render();
+        CHECK(s.frames_with([](const Schedule& q) { return q.pri == 1; }) == 3 * kTrial);
+        // one stalled frame in a trial is tolerated: the pipeline drains once, in the alternative's measured frames
+        Sim one(true, "t.stall1");
+        one.tuner.set({-1, 2, 2, -1}, 0);
+        one.cost = pri_costs(0.9);
+        while (!one.done() && one.frame < 20000) { one.in_flight = one.frame == ScheduleTuner::kWarm + kTrial + 12 ? 0 : 2; one.render(); }
+        CHECK(is(one.get(), 1, 2, 2) && one.frames_with([](const Schedule& q) { return q.pri == 1; }) == kTrial + 1);      // (one round, and the frame of the deciding step)
+    }
+    begin_case("tuner: statistics reset in mid-trial");
+    {
+        Sim s(true, "t.reset");
+        s.tuner.set({-1, 2, 2, -1}, 0);
+        s.cost = pri_costs(0.9);
+        while (!s.done() && s.frame < 20000) { if (s.frame == ScheduleTuner::kWarm + kTrial + 10) s.idx.reset(); s.render(); }
+        // the sequence whose event indices the reset made meaningless is played again, then decided
+        CHECK(is(s.get(), 1, 2, 2) && s.frames_with([](const Schedule& q) { return q.pri == 1; }) == 2 * kTrial + 1);
+        CHECK(cache.find("t.reset", &e) && e.pri == 1);
+    }
+    begin_case("tuner: the event pool wraps in mid-trial");
+    {
+        Sim s(true, "t.wrap");
+        s.cost = pri_costs(0.9);
+        const uint64_t restart = EventPoolIndex::kMaxSets - ScheduleTuner::kWarm - kTrial - 12;      // the wrap falls into the alternative's measured frames
+        s.stage_events = false;
+        while (s.frame < restart) s.render();
+        CHECK(!s.done() && s.host_calls == 0);
+        s.stage_events = true;      // (as if the host had had them off: the tuner starts kWarm frames from the set_schedule call)
+        s.tuner.set({-1, 2, 2, -1}, s.frame);
+        const uint64_t epoch_before = s.idx.epoch;
+        const uint64_t frames = s.run_until_done();
+        CHECK(s.pool_size == EventPoolIndex::kMaxSets && s.idx.epoch == epoch_before + 1 && s.idx.used == frames - EventPoolIndex::kMaxSets);
+        CHECK(is(s.get(), 1, 2, 2) && s.frames_with([](const Schedule& q) { return q.pri == 1; }) == 2 * kTrial + 1);      // replayed once
+    }
+    begin_case("tuner: set_schedule in mid-trial");
+    {
+        Sim s(true, "t.set");
+        s.cost = pri_costs(0.9);
+        while (s.frame < ScheduleTuner::kWarm + kTrial + 10) s.render();
+        CHECK(s.tuner.now().pri == 1 && s.get().camera_priority_low == 1);      // the alternative's trial is running
+        s.tuner.set({-1, 3, -1, 1}, s.frame);
+        CHECK(is(s.get(), 0, 3, 2) && s.get().composite_defer == 1 && !s.done() && std::string(s.tuner.source()) == "pinned in part");
+        const size_t before = s.history.size();
+        for (uint64_t f = 0; f < ScheduleTuner::kWarm; f++) { s.render(); CHECK(is(s.get(), 0, 3, 2)); }
+        s.run_until_done();
+        CHECK(is(s.get(), 1, 3, 2) && s.get().composite_defer == 1);
+        size_t other_lag = 0;
+        for (size_t f = before; f < s.history.size(); f++) other_lag += s.history[f].lag != 3 || s.history[f].defer != 1;
+        CHECK(other_lag == 0);
+    }
+    begin_case("tuner: communicator failure in the bounded wait");
+    {
+        Sim s(true, "t.comm");
+        s.cost = pri_costs(0.5);
+        s.fail_wait_at_frame = (long)(ScheduleTuner::kWarm + kTrial + 10);
+        const uint64_t frames = s.run_until_done();
+        CHECK(frames == (uint64_t)s.fail_wait_at_frame + 1 && s.done() && is(s.get(), 0, 2, 2) && s.tuner.now().pri == 0);
+        CHECK(std::string(s.tuner.source()) == "default" && !cache.find("t.comm", &e));
+        const long calls = s.host_calls;
+        for (int f = 0; f < 300; f++) s.render();
+        CHECK(s.host_calls == calls && s.frames_with([](const Schedule& q) { return q.pri == 1; }) == 10);
+    }
+}
+
+// ======================================================================================== 5. schedule key
+static void key_cases(const char* schedules_txt)
+{
+    begin_case("schedule key: the package's recorded keys");
+    std::vector<std::string> recorded;
+    {
+        FILE* f = std::fopen(schedules_txt, "r");
+        char line[1024];
+        while (f && std::fgets(line, sizeof line, f))
+            if (line[0] != '#') recorded.push_back(std::string(line).substr(0, std::string(line).find(' ')));
+        if (f) std::fclose(f);
+    }
+    CHECK(recorded.size() == 5);
+    if (recorded.size() != 5) return;
+    auto key = [](uint32_t pos, uint32_t width, uint32_t depth, unsigned long long voxels, uint32_t w, uint32_t h, uint32_t len, uint32_t self_train = 0) {
+        nrc_config cfg{};
+        cfg.pos_id = pos; cfg.dir_id = 0; cfg.nn_width = width; cfg.nn_depth = depth; cfg.train_batch_count = 1; cfg.self_train = self_train;
+        return schedule_key("gfx950", 256, 8, cfg, voxels, w, h, w, h, 16384, len);
+    };
+    const unsigned long long v256 = 256ull * 256 * 256, v512 = 512ull * 512 * 512;
+    CHECK(key(3, 64, 6, v256, 1920, 1080, 1) == recorded[0]);        // c2: Frequency 6 x 64, 256^3
+    CHECK(key(3, 64, 6, v256, 1920, 1080, 32) == recorded[1]);       // c2 with quirk Q2 fixed: 32-vertex train paths
+    CHECK(key(3, 128, 8, v512, 1920, 1080, 1) == recorded[2]);       // c5: 8 x 128, 512^3
+    CHECK(key(0, 64, 6, v256, 1920, 1080, 1) == recorded[3]);        // HashGrid, the default table of 2^19
+    CHECK(key(3, 64, 6, v256, 3840, 2160, 1) == recorded[4]);        // c4 on one GPU
+    begin_case("schedule key: suffix and fields");
+    CHECK(key(3, 64, 6, v256, 1920, 1080, 1, 1) == recorded[0] + ".st");
+    CHECK(key(3, 64, 6, v256 - 1, 1920, 1080, 1) == "gfx950:256cu:8xcd|pos3.dir0.w64.d6.hg0|vol2^23|1920x1080.of1920x1080|train1x16384.len1");
+    CHECK(key(3, 64, 6, v256 + 5, 1920, 1080, 1) == recorded[0]);
+    nrc_config cfg{};
+    cfg.pos_id = 0; cfg.dir_id = 2; cfg.nn_width = 32; cfg.nn_depth = 4; cfg.hashgrid_log2_size = 15; cfg.train_batch_count = 4;
+    CHECK(schedule_key("gfx942", 304, 4, cfg, 1, 960, 1080, 1920, 1080, 4096, 8) == "gfx942:304cu:4xcd|pos0.dir2.w32.d4.hg15|vol2^0|960x1080.of1920x1080|train4x4096.len8");
+}
+
+int main(int argc, char** argv)
+{
+    if (argc != 3) { std::printf("usage: host_logic_main <scratch directory> <schedules.txt>\n"); return 2; }
+    g_dir = argv[1];
+    schedule_cache_cases();
+    checkpoint_cases();
+    occupancy_cases();
+    tuner_cases();
+    key_cases(argv[2]);
+    std::printf("host_logic: %d cases, %d checks%s\n", g_cases, g_checks, g_failed ? ", FAILED" : "");
+    return g_failed ? 1 : 0;
+}

@@ -511,7 +511,7 @@ def test_no_value_of_the_schedule_changes_a_pixel(api, sc, cloud16, torch_gpu, m
 
 
 def test_the_renderer_chooses_its_schedule_on_live_frames_without_changing_them(api, sc, cloud16, torch_gpu):
-    """the Tuner (nrc_api.hip): with the pipeline kept full (render_frames, no host synchronisation) the renderer tries the alternatives of
+    """the Tuner (nrc_schedule.hpp): with the pipeline kept full (render_frames, no host synchronisation) the renderer tries the alternatives of
     each knob on the caller's own frames and settles -- tuning_done -- within 370 to 900 frames (128 to warm up, ten trials of 24, replayed up to
     three times where a result is inside the noise); the frames are those of a renderer whose
     schedule is pinned, bit for bit; pinned knobs keep their values; a host that synchronises after every frame never tunes.  (1080p: the
