@@ -159,6 +159,41 @@ int nrc_cache_comm_init(nrc_cache_t* c, const void* unique_id128, int rank, int 
 #define NRC_EXCHANGE_F16 1
 int nrc_cache_set_exchange_dtype(nrc_cache_t* c, int dtype);
 int nrc_cache_get_exchange_dtype(nrc_cache_t* c);
+/* Training guard: what a training step does whose loss or gradient is not finite (one NaN target, a self-training tail from a diverging
+ * cache, an fp16 exchange whose sum passes 65 504).  A per-cache policy:
+ *   NRC_NONFINITE_PROPAGATE (default)  the optimizer applies the step: weights, EMA weights and Adam moments become non-finite, the caller
+ *                                      learns it from the loss it polls.  Every result is bit for bit what it was without the guard.
+ *   NRC_NONFINITE_SKIP                 every training batch gets a verdict on the device, on the training stream, behind the gradient exchange
+ *                                      (RCCL all-reduce, fp16 exchange, list exchange, gradient hook, a caller's own reduction of
+ *                                      nrc_cache_grad_ptr) and in front of the optimizer's first write.  The step is BAD when
+ *                                        1. the loss cell loss[0] -- behind the exchange: the global loss -- is not finite, or
+ *                                        2. one of the first n_mlp (matrix) words of the gradient vector the optimizer is about to read is not
+ *                                           finite (exponent bits all ones).
+ *                                      The HashGrid table gradient is not scanned: its entries are fp16 / fixed-point sums of per-ray terms that
+ *                                      can only leave the finite range together with the loss, and in the list exchange every rank's loss is
+ *                                      summed into the cell: rule 1 covers it.
+ * Both inputs of the verdict are bits every rank holds identically behind the exchange (what keeps the replicas identical in the first place), so
+ * every rank reaches the same verdict with no further collective.  Set the policy on every rank alike.
+ * A bad step
+ *   - leaves master weights, EMA weights and Adam m / v (table entries included) exactly as they were;
+ *   - still writes the fp16 images of the next inference set, from the unchanged weights (the host alternates the sets whatever the verdict);
+ *   - still publishes its (non-finite) loss and sequence number: nrc_cache_get_loss / nrc_cache_get_loss_async keep their meaning;
+ *   - still consumes its step number.  The host never learns a verdict in time and does not wait for one, and it computes the bias corrections of
+ *     Adam and of the EMA from the step number.  The contract therefore is: A SKIPPED STEP IS A STEP WHOSE UPDATE IS THE IDENTITY; THE BIAS
+ *     CORRECTIONS COUNT ENQUEUED STEPS.  (An approximation against an optimizer that would not count it: Adam's lr_t differs by 0.5 % at step
+ *     100, less later.)  A run with a skipped step k equals, bit for bit, the run without that batch and nrc_cache_set_step(k) in its place;
+ *   - increments a device-resident counter and records its step number (nrc_cache_get_step's value for that step).
+ * A good step under SKIP produces the bits it produces under PROPAGATE.  Cost: the scan rides on the pass that writes the final gradient where there
+ * is one (the gradient reduction without an exchange, the last pass of the fp16 exchange); behind an fp32 all-reduce, an fp32 hook or a caller's
+ * own reduction it is one launch over n_mlp words.
+ * The policy may be changed between steps; that does not reset the counter.  Checkpoints do not carry the counter.
+ * nrc_cache_get_skipped_steps: *skipped = steps skipped since the cache was created, *last_skipped_step = step number of the latest (0: none);
+ * waits for the last enqueued training step only, like nrc_cache_get_loss. */
+#define NRC_NONFINITE_PROPAGATE 0
+#define NRC_NONFINITE_SKIP 1
+int nrc_cache_set_nonfinite_policy(nrc_cache_t* c, int policy);
+int nrc_cache_get_nonfinite_policy(nrc_cache_t* c);
+int nrc_cache_get_skipped_steps(nrc_cache_t* c, uint32_t* skipped, uint32_t* last_skipped_step);
 /* rank / size as the library's own RCCL communicator reports them (ncclCommUserRank / ncclCommCount); world = 0: none */
 int nrc_cache_comm_info(nrc_cache_t* c, int* rank, int* world);
 /* Failure detection on the exchange ("RCCL error -> status code").  An enqueued collective reports nothing by itself:

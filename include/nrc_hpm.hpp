@@ -340,6 +340,19 @@ public:
     // what the exchange carries: NRC_EXCHANGE_F32 (default) or NRC_EXCHANGE_F16 -- the gradients as fp16 numbers pre-scaled by loss_scale
     void SetExchangeDtype(int dtype) { nrc_check(nrc_cache_set_exchange_dtype(h_, dtype)); }
     int GetExchangeDtype() const { return nrc_cache_get_exchange_dtype(h_); }
+    // training guard (nrc_hpm.h, nrc_cache_set_nonfinite_policy): NRC_NONFINITE_PROPAGATE (default) or NRC_NONFINITE_SKIP -- a step whose loss or
+    // gradient is not finite leaves weights, EMA weights and Adam moments as they are and is counted.  A host that sums the gradient in a
+    // hook (SetGradHook) needs nothing more: the verdict is taken from what the hook leaves, which every rank holds identically
+    void SetNonFinitePolicy(int policy) { nrc_check(nrc_cache_set_nonfinite_policy(h_, policy)); }
+    int GetNonFinitePolicy() const { return nrc_cache_get_nonfinite_policy(h_); }
+    // steps skipped so far; lastSkippedStep (optional): the step number of the latest, 0 = none.  Waits for the last enqueued step only
+    uint32_t GetSkippedSteps(uint32_t* lastSkippedStep = nullptr) const
+    {
+        uint32_t n = 0, last = 0;
+        nrc_check(nrc_cache_get_skipped_steps(h_, &n, &last));
+        if (lastSkippedStep) *lastSkippedStep = last;
+        return n;
+    }
     // frame gather / metric reduction over a transport of the host's own (a cache without CommInit): include/nrc_hpm.h
     void SetCollectiveHooks(int rank, int world, nrc_allreduce_f64_fn allreduce, nrc_allgather_fn allgather, void* user)
     {

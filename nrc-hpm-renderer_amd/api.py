@@ -21,6 +21,8 @@ LIB_PATH = os.environ.get("NRC_HPM_LIB") or os.path.join(_HERE, "lib", "libnrc_h
 
 NRC_FIX_Q1_TRAIN_Y_DIST = 1
 NRC_FIX_Q2_TRAIN_RAY_LEN = 2
+NRC_NONFINITE_PROPAGATE = 0      # include/nrc_hpm.h, nrc_cache_set_nonfinite_policy
+NRC_NONFINITE_SKIP = 1
 
 
 class NrcConfig(C.Structure):
@@ -74,6 +76,7 @@ ABI_SYMBOLS = [
     "nrc_cache_grad_ptr", "nrc_cache_param_count", "nrc_cache_loss_ptr", "nrc_cache_set_loss_norm_factor",
     "nrc_comm_unique_id", "nrc_cache_comm_init", "nrc_cache_comm_sparse", "nrc_cache_grid_list_capacity",
     "nrc_cache_set_exchange_dtype", "nrc_cache_get_exchange_dtype",
+    "nrc_cache_set_nonfinite_policy", "nrc_cache_get_nonfinite_policy", "nrc_cache_get_skipped_steps",
     "nrc_cache_grid_grad_pack", "nrc_cache_grid_grad_apply",
     "nrc_cache_set_stream", "nrc_cache_set_grad_hook", "nrc_cache_get_params", "nrc_cache_set_params",
     "nrc_cache_get_step", "nrc_cache_set_step", "nrc_cache_param_count_tcnn", "nrc_cache_get_params_tcnn", "nrc_cache_set_params_tcnn",
@@ -469,6 +472,20 @@ class NeuralRadianceCache:
 
     def GetExchangeDtype(self):
         return "f16" if self.L.nrc_cache_get_exchange_dtype(self.h) == 1 else "f32"
+
+    def SetNonFinitePolicy(self, policy):
+        """nrc_cache_set_nonfinite_policy: NRC_NONFINITE_PROPAGATE (default) or NRC_NONFINITE_SKIP -- a training step whose loss or
+        gradient is not finite leaves weights, EMA weights and Adam moments as they are and is counted; every rank alike"""
+        _check(self.L.nrc_cache_set_nonfinite_policy(self.h, C.c_int(int(policy))))
+
+    def GetNonFinitePolicy(self):
+        return int(self.L.nrc_cache_get_nonfinite_policy(self.h))
+
+    def GetSkippedSteps(self):
+        """(number of steps skipped so far, step number of the last one skipped; 0 = none) -- waits for the last enqueued step only"""
+        n, last = C.c_uint32(0), C.c_uint32(0)
+        _check(self.L.nrc_cache_get_skipped_steps(self.h, C.byref(n), C.byref(last)))
+        return int(n.value), int(last.value)
 
     def SetLossNormFactor(self, factor):
         _check(self.L.nrc_cache_set_loss_norm_factor(self.h, C.c_uint32(factor)))

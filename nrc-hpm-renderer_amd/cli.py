@@ -44,6 +44,9 @@ def main(argv=None):
     ap.add_argument("--output", default="output")
     ap.add_argument("--export", default=None, help="write the final NRC image to this EXR")
     ap.add_argument("--gpus", type=int, default=1, help="ranks the frame is sharded over (one GPU each)")
+    ap.add_argument("--skip-nonfinite", action="store_true",
+                    help="training guard: a step whose loss or gradient is not finite is skipped and counted instead of ending the run "
+                         "(include/nrc_hpm.h, nrc_cache_set_nonfinite_policy)")
     ap.add_argument("--self-train", action="store_true",
                     help="self-training: train paths end with the cache's own estimate (include/nrc_hpm.h, nrc_config.self_train)")
     args = ap.parse_args(argv)
@@ -99,6 +102,8 @@ def main(argv=None):
             raise SystemExit("SkyRenderer ERROR: rank %d's %d x %d tile is not a multiple of 16 pixels" % (rank, lw, H))
 
     nrc = api.NeuralRadianceCache(cfg)
+    if args.skip_nonfinite:
+        nrc.SetNonFinitePolicy(api.NRC_NONFINITE_SKIP)      # (every rank: the verdicts are identical by construction, no agreement needed)
     if world > 1:
         # one exchange step per train batch: the library's own RCCL all-reduce (one device per rank), or the gloo hook of a rehearsal
         parallel.attach_gradient_allreduce(nrc, world, native=not shared_gpu)
@@ -140,7 +145,7 @@ def main(argv=None):
             nrc_renderer.SetVolume(seq_dev[(frame // args.frames_per_volume) % len(seq_dev)])
         nrc_renderer.Render(None, True)
         loss = nrc.GetLoss(wait=False)          # src/main.cu:376: polled every frame, never blocks the frame pipeline
-        if math.isnan(loss) or math.isinf(loss):                    # src/main.cu:380-384
+        if (math.isnan(loss) or math.isinf(loss)) and not args.skip_nonfinite:      # src/main.cu:380-384; with the guard that step was skipped
             print("SkyRenderer ERROR: NRC Loss is %s" % loss, file=sys.stderr)
             bad = True
         if world == 1:
@@ -165,6 +170,8 @@ def main(argv=None):
             print("frame %d: loss %.5f, %.3f ms" % (frame, loss, nrc_renderer.GetFrameTimeMS()))
     if log is not None:
         log.close()
+    if args.skip_nonfinite and rank == 0:
+        print("skipped %d of %d steps" % (nrc.GetSkippedSteps()[0], nrc.GetStep()))
     if args.export and not failed:
         nrc_renderer.ExportOutputImageToFile(None, args.export)      # sharded: collective, rank 0 writes the whole frame
     nrc_renderer.Destroy()

@@ -1,7 +1,8 @@
 // nrc_checkpoint.hpp -- the checkpoint file of nrc_cache_save_checkpoint / _load_checkpoint: a 64-byte header that names the model, then
 // the four parameter vectors (weights, two Adam moments, EMA weights) in tiny-cuda-nn layout, fp32.  Device-free: the C ABI functions
 // copy from / to the device and convert the layout; this file reads, writes and judges (tests/cpp/host_logic_main.cpp runs it under
-// the sanitizers).
+// the sanitizers).  The step number travels in the header; the non-finite guard's counter of skipped steps (nrc_cache_get_skipped_steps)
+// does not: it is a statistic of the process, not state of the model.
 #pragma once
 #include <cstdint>
 #include <cstdio>

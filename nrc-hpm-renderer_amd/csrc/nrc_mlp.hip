@@ -2213,9 +2213,13 @@ __global__ __launch_bounds__(WGRAD2_WAVES * 64, NRC_WGRAD2_MIN_WAVES) void k_wgr
 // grad[i] = sum over chunk slabs in a fixed order (bitwise reproducible): a 256-thread block owns 64 parameters, four
 // thread groups each add a contiguous quarter of the slabs in chunk order, the four partials are combined in group order.
 // Block 0 also folds the loss partials.
+// Guard... (nothing, or one GuardArgs: the non-finite guard of nrc_mlp.hpp): the values stored are also the scan's input -- where no
+// exchange and no hook follows, this pass writes the gradient the optimizer reads.  (A trailing pack, not a wrapper around a shared body:
+// the instantiation without it is then the kernel it was, instruction for instruction; tools/kernel_body_diff.py.)
+template <class... Guard>
 __global__ __launch_bounds__(256) void k_reduce_grads(const float* __restrict__ slabs, uint32_t n_chunks, uint32_t n_params,
                                                      float* __restrict__ grad, const float* __restrict__ loss_part,
-                                                     uint32_t n_loss, float* __restrict__ loss)
+                                                     uint32_t n_loss, float* __restrict__ loss, Guard... ga)
 {
     NRC_RAISE_WAVE_PRIORITY(1);
     __shared__ float part[4][64];
@@ -2230,6 +2234,7 @@ __global__ __launch_bounds__(256) void k_reduce_grads(const float* __restrict__ 
     part[g][p] = s;
     __syncthreads();
     if (g == 0 && i < n_params) grad[i] = ((part[0][p] + part[1][p]) + part[2][p]) + part[3][p];
+    if constexpr (sizeof...(Guard) != 0) guard_flag(g == 0 && i < n_params && guard_nonfinite(((part[0][p] + part[1][p]) + part[2][p]) + part[3][p]), ga...);
     if (blockIdx.x == 0) {
         float l = 0.0f;
         for (uint32_t k = threadIdx.x; k < n_loss; k += 256u) l += loss_part[k];
@@ -2240,7 +2245,18 @@ __global__ __launch_bounds__(256) void k_reduce_grads(const float* __restrict__ 
             __syncthreads();
         }
         if (threadIdx.x == 0) { loss[0] = red[0]; loss[1] = 0.0f; }
+        if constexpr (sizeof...(Guard) != 0) guard_flag(threadIdx.x == 0 && guard_nonfinite(red[0]), ga...);
     }
+}
+// The scan on its own, for a gradient that something behind backward() rewrote in place (fp32 all-reduce, fp32 hook, a caller that holds
+// nrc_cache_grad_ptr): the first n words of the vector and the loss cell.
+__global__ __launch_bounds__(256) void k_guard_scan(const float* __restrict__ grad, uint32_t n, const float* __restrict__ loss, GuardArgs ga)
+{
+    NRC_RAISE_WAVE_PRIORITY(1);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool bad = i < n && guard_nonfinite(grad[i]);
+    if (i == 0) bad = bad || guard_nonfinite(loss[0]);
+    guard_flag(bad, ga);
 }
 
 // EMA{Adam} (tiny-cuda-nn defaults: beta1 .9, beta2 .999, eps 1e-8, l2_reg 1e-8), SURVEY App. B
@@ -2308,6 +2324,35 @@ __global__ void k_sgd_ema(float* __restrict__ w, float* __restrict__ ema, const 
     sgd_ema_update(i, w, ema, grad[i], lr, a, &wn, &en);
 }
 
+// The same two with the non-finite guard: a bad step (nrc_mlp.hpp, GuardArgs) leaves every vector as it is and is counted by thread 0;
+// repack() behind them then writes the next inference set from the unchanged weights.
+__global__ void k_adam_ema_guarded(float* __restrict__ w, float* __restrict__ ema, float* __restrict__ m, float* __restrict__ v,
+                                   const float* __restrict__ grad, uint32_t n, uint32_t n_matrix, AdamArgs a, GuardArgs ga)
+{
+    NRC_RAISE_WAVE_PRIORITY(1);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (guard_bad(ga)) {
+        if (i == 0) guard_count(ga);
+        return;
+    }
+    float wn, en;
+    adam_ema_update(i, w, ema, m, v, grad[i], i < n_matrix, a, &wn, &en);
+}
+__global__ void k_sgd_ema_guarded(float* __restrict__ w, float* __restrict__ ema, const float* __restrict__ grad, uint32_t n, float lr,
+                                  AdamArgs a, GuardArgs ga)
+{
+    NRC_RAISE_WAVE_PRIORITY(1);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (guard_bad(ga)) {
+        if (i == 0) guard_count(ga);
+        return;
+    }
+    float wn, en;
+    sgd_ema_update(i, w, ema, grad[i], lr, a, &wn, &en);
+}
+
 // The optimizer step of a model without a trainable encoding as ONE launch: every thread updates its parameter and stores the
 // fp16 copies straight into the three fragment images (dst: image slot of parameter i in the forward / EMA inference / backward
 // image, -1 = not in that image; the images' padding slots are zero since construction), thread 0 also publishes the step's loss
@@ -2317,11 +2362,13 @@ struct PackDst {
     const int32_t *fwd, *inf, *bwd;
     half_t *pk_fwd, *pk_inf, *pk_bwd;
 };
-template <bool SGD>
+// Guard... (nothing, or one GuardArgs): on a bad step the three images are still written -- the inference image is the OTHER set of the
+// double buffer, the host flips to it whatever the verdict -- from the weights as they are; thread 0 counts the step.
+template <bool SGD, class... Guard>
 __global__ __launch_bounds__(256) void k_opt_pack(float* __restrict__ w, float* __restrict__ ema, float* __restrict__ m,
                                                  float* __restrict__ v, const float* __restrict__ grad, uint32_t n, float lr,
                                                  AdamArgs a, PackDst d, const float* __restrict__ loss, uint32_t loss_seq,
-                                                 unsigned long long* __restrict__ loss_cell)
+                                                 unsigned long long* __restrict__ loss_cell, Guard... ga)
 {
     NRC_RAISE_WAVE_PRIORITY(1);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2329,9 +2376,15 @@ __global__ __launch_bounds__(256) void k_opt_pack(float* __restrict__ w, float* 
         const unsigned long long bits = (unsigned long long)__builtin_bit_cast(uint32_t, loss[0]) | ((unsigned long long)loss_seq << 32);
         __hip_atomic_store(loss_cell, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+    bool bad = false;
+    if constexpr (sizeof...(Guard) != 0) {
+        bad = guard_bad(ga...);
+        if (i == 0 && bad) guard_count(ga...);
+    }
     if (i >= n) return;
     float wn, en;
-    if (SGD) sgd_ema_update(i, w, ema, grad[i], lr, a, &wn, &en);
+    if (sizeof...(Guard) != 0 && bad) { wn = w[i]; en = ema[i]; }
+    else if (SGD) sgd_ema_update(i, w, ema, grad[i], lr, a, &wn, &en);
     else adam_ema_update(i, w, ema, m, v, grad[i], true, a, &wn, &en);
     const int32_t df = d.fwd[i], di = d.inf[i], db = d.bwd[i];
     if (df >= 0) d.pk_fwd[df] = (half_t)wn;
@@ -2343,11 +2396,13 @@ __global__ __launch_bounds__(256) void k_opt_pack(float* __restrict__ w, float* 
 // the atomics accumulated into (FROM16; no fp32 widening pass) or from the fp32 vector (after an exchange / a caller's hook), the
 // update of k_adam_ema / k_sgd_ema for parameters n_matrix + 2e, + 1, and the two fp16 gather copies (training weights, EMA set
 // `next`) that k_pack_grid would write.  Replaces k_grid_grad_f32 + the table part of k_adam_ema + k_pack_grid.
-template <bool SGD, bool FROM16>
+// Guard... (nothing, or one GuardArgs; k_opt_pack in front of it has counted the step): a bad step still clears the fp16 gradient entries
+// it reads -- the next backward pass expects a clean table -- and writes both gather copies from the entry as it is.
+template <bool SGD, bool FROM16, class... Guard>
 __global__ __launch_bounds__(256) void k_grid_opt(float* __restrict__ w, float* __restrict__ ema, float* __restrict__ m,
                                                  float* __restrict__ v, const float* __restrict__ grad,
                                                  uint32_t* __restrict__ grad16, uint32_t n_matrix, uint32_t n_entries, float lr,
-                                                 AdamArgs a, uint32_t* __restrict__ t_train, uint32_t* __restrict__ t_ema)
+                                                 AdamArgs a, uint32_t* __restrict__ t_train, uint32_t* __restrict__ t_ema, Guard... ga)
 {
     NRC_RAISE_WAVE_PRIORITY(1);
     const uint32_t e = blockIdx.x * 256u + threadIdx.x;
@@ -2366,6 +2421,15 @@ __global__ __launch_bounds__(256) void k_grid_opt(float* __restrict__ w, float* 
         g0 = grad[i0]; g1 = grad[i0 + 1u];
     }
     float2v wn, en;
+    if constexpr (sizeof...(Guard) != 0) {
+        if (guard_bad(ga...)) {
+            wn[0] = w[i0]; wn[1] = w[i0 + 1u];
+            en[0] = ema[i0]; en[1] = ema[i0 + 1u];
+            t_train[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(wn, half2v));
+            t_ema[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(en, half2v));
+            return;
+        }
+    }
     float x, y;
     if (SGD) sgd_ema_update(i0, w, ema, g0, lr, a, &x, &y);
     else adam_ema_update(i0, w, ema, m, v, g0, false, a, &x, &y);
@@ -2400,11 +2464,12 @@ __device__ __forceinline__ void sgd_value(float& wi, float graw, float lr, const
     const float g = graw * a.inv_loss_scale + l2 * wi;
     wi = wi - lr * g;
 }
-template <bool SGD, bool FROM16>
+// Guard... (nothing, or one GuardArgs): as in k_grid_opt; the training gather copy already holds fp16(w), so a bad step writes the EMA copy alone.
+template <bool SGD, bool FROM16, class... Guard>
 __global__ __launch_bounds__(256) void k_grid_opt2(float* __restrict__ w, float* __restrict__ ema, float* __restrict__ m,
                                                   float* __restrict__ v, const float* __restrict__ grad,
                                                   uint32_t* __restrict__ grad16, uint32_t n_matrix, uint32_t n_pairs, float lr,
-                                                  AdamArgs a, uint32_t* __restrict__ t_train, uint32_t* __restrict__ t_ema)
+                                                  AdamArgs a, uint32_t* __restrict__ t_train, uint32_t* __restrict__ t_ema, Guard... ga)
 {
     NRC_RAISE_WAVE_PRIORITY(1);
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
@@ -2419,6 +2484,15 @@ __global__ __launch_bounds__(256) void k_grid_opt2(float* __restrict__ w, float*
     } else {
         const float4 gv = *reinterpret_cast<const float4*>(grad + i0);
         g[0] = gv.x; g[1] = gv.y; g[2] = gv.z; g[3] = gv.w;
+    }
+    if constexpr (sizeof...(Guard) != 0) {
+        if (guard_bad(ga...)) {
+            const float4 ek = *reinterpret_cast<const float4*>(ema + i0);
+            const float2v k0 = {ek.x, ek.y}, k1 = {ek.z, ek.w};
+            *reinterpret_cast<uint2*>(t_ema + e) = make_uint2(__builtin_bit_cast(uint32_t, __builtin_convertvector(k0, half2v)),
+                                                             __builtin_bit_cast(uint32_t, __builtin_convertvector(k1, half2v)));
+            return;
+        }
     }
     const float4 wv = *reinterpret_cast<const float4*>(w + i0), ev = *reinterpret_cast<const float4*>(ema + i0);
     float wi[4] = {wv.x, wv.y, wv.z, wv.w}, ei[4] = {ev.x, ev.y, ev.z, ev.w};
@@ -2681,6 +2755,8 @@ Mlp::~Mlp()
                     d_t16_ema_[0], d_t16_ema_[1], d_denc_, d_grad16_, d_grid_lists_, d_grid_counters_, d_grid_bin_entry0_, d_grid_fix_};
     for (void* p : ptrs)
         if (p) dev_free(p);
+    if (d_guard_) dev_free(d_guard_);
+    if (h_guard_) (void)hipHostFree(h_guard_);
 }
 
 float* Mlp::buffer(int which)
@@ -3304,9 +3380,40 @@ void Mlp::backward(const float* d_in, const float* d_target, uint32_t n, uint32_
                            (const half_t*)d_deltas_, (const half_t*)d_acts_, n, chunk, depth_ * kw_ + 8, enc_dims_ + depth_ * kw_,
                            (const WgradTask*)d_tasks_, n_wgrad_tasks_, d_slabs_, n_mlp_);
     NRC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_reduce_grads, dim3(ceil_div(n_mlp_, 64)), dim3(256), 0, s, d_slabs_, n_chunks, n_mlp_,
-                       d_grad_, d_loss_part_, n_tiles, d_loss_);
+    if (guard_on_)
+        hipLaunchKernelGGL(k_reduce_grads<GuardArgs>, dim3(ceil_div(n_mlp_, 64)), dim3(256), 0, s, d_slabs_, n_chunks, n_mlp_,
+                           d_grad_, d_loss_part_, n_tiles, d_loss_, guard_scan_args());
+    else
+        hipLaunchKernelGGL(k_reduce_grads<>, dim3(ceil_div(n_mlp_, 64)), dim3(256), 0, s, d_slabs_, n_chunks, n_mlp_,
+                           d_grad_, d_loss_part_, n_tiles, d_loss_);
     NRC_HIP(hipGetLastError());
+}
+
+void Mlp::set_guard(bool on)
+{
+    if (on && !d_guard_) {
+        dev_alloc((void**)&d_guard_, 4 * sizeof(uint32_t), "d_guard_");
+        NRC_HIP(hipMemset(d_guard_, 0, 4 * sizeof(uint32_t)));
+        NRC_HIP(hipHostMalloc((void**)&h_guard_, sizeof(unsigned long long), hipHostMallocMapped));
+        *h_guard_ = 0ull;
+        NRC_HIP(hipHostGetDevicePointer((void**)&d_guard_cell_, h_guard_, 0));
+    }
+    guard_on_ = on;
+    guard_scanned_ = false;      // (a gradient that backward() left before the switch has no verdict: optimizer_step() scans it)
+}
+
+GuardArgs Mlp::guard_scan_args()
+{
+    if (++guard_stamp_ == 0u) guard_stamp_ = 1u;      // 0 is the word's initial value: no scan has that stamp
+    guard_scanned_ = true;
+    return GuardArgs{d_guard_, d_guard_cell_, guard_stamp_, 0u};
+}
+
+void Mlp::guard_stats(uint32_t* skipped, uint32_t* last_step) const
+{
+    const unsigned long long bits = h_guard_ ? __atomic_load_n(h_guard_, __ATOMIC_ACQUIRE) : 0ull;
+    *skipped = (uint32_t)bits;
+    *last_step = (uint32_t)(bits >> 32);
 }
 
 uint32_t Mlp::grid_list_capacity(uint32_t n) const
@@ -3338,18 +3445,26 @@ void Mlp::grid_grad_apply(const uint32_t* d_lists, uint32_t n_lists, uint32_t ca
     NRC_HIP(hipGetLastError());
 }
 
-bool Mlp::optimizer_step(hipStream_t s, uint32_t loss_seq, unsigned long long* loss_cell)
+// the step's host scalars: the bias corrections of Adam and of the EMA count ENQUEUED steps (a step the guard skips included)
+static AdamArgs adam_args_of(const nrc_config& cfg, uint32_t step)
 {
-    step += 1;
     const double b1 = 0.9, b2 = 0.999;
     const double t = (double)step;
-    const double d = (double)cfg_.ema_decay;
+    const double d = (double)cfg.ema_decay;
     AdamArgs a;
-    a.lr_t = cfg_.learning_rate * (float)(std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t)));
-    a.inv_loss_scale = 1.0f / kLossScale;
+    a.lr_t = cfg.learning_rate * (float)(std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t)));
+    a.inv_loss_scale = 1.0f / Mlp::kLossScale;
     a.ema_old = (float)(d * (1.0 - std::pow(d, t - 1.0)));
     a.ema_new = (float)(1.0 - d);
     a.ema_div = (float)(1.0 - std::pow(d, t));
+    return a;
+}
+
+bool Mlp::optimizer_step(hipStream_t s, uint32_t loss_seq, unsigned long long* loss_cell)
+{
+    step += 1;
+    if (guard_on_) return optimizer_step_guarded(s, loss_seq, loss_cell);
+    const AdamArgs a = adam_args_of(cfg_, step);
     if (fused_opt_) {
         const int next = infer_set_ ^ 1;
         const PackDst d{d_dst_, d_dst_ + n_mlp_, d_dst_ + 2 * (size_t)n_mlp_, (half_t*)d_pk_fwd_, (half_t*)d_pk_infer_[next], (half_t*)d_pk_bwd_};
@@ -3406,6 +3521,71 @@ bool Mlp::optimizer_step(hipStream_t s, uint32_t loss_seq, unsigned long long* l
     NRC_HIP(hipGetLastError());
     repack(s);
     return false;
+}
+
+// optimizer_step() with the non-finite guard on: the same launches in the same order, each in its guarded variant, behind the verdict
+// of the gradient they read (k_guard_scan here, unless the pass that wrote the gradient has scanned it)
+bool Mlp::optimizer_step_guarded(hipStream_t s, uint32_t loss_seq, unsigned long long* loss_cell)
+{
+    const AdamArgs a = adam_args_of(cfg_, step);
+    if (!guard_scanned_) {
+        hipLaunchKernelGGL(k_guard_scan, dim3(ceil_div(n_mlp_, 256)), dim3(256), 0, s, (const float*)d_grad_, n_mlp_, (const float*)d_loss_,
+                           guard_scan_args());
+        NRC_HIP(hipGetLastError());
+    }
+    guard_scanned_ = false;      // (the verdict is this step's alone)
+    const GuardArgs ga{d_guard_, d_guard_cell_, guard_stamp_, step};
+    const float lr = cfg_.learning_rate;
+    if (!fused_opt_) {
+        if (sgd_)
+            hipLaunchKernelGGL(k_sgd_ema_guarded, dim3(ceil_div(n_params_, 256)), dim3(256), 0, s, d_w_, d_ema_, d_grad_, n_params_, lr, a, ga);
+        else
+            hipLaunchKernelGGL(k_adam_ema_guarded, dim3(ceil_div(n_params_, 256)), dim3(256), 0, s, d_w_, d_ema_, d_m_, d_v_, d_grad_,
+                               n_params_, n_mlp_, a, ga);
+        NRC_HIP(hipGetLastError());
+        repack(s);
+        return false;
+    }
+    const int next = infer_set_ ^ 1;
+    const PackDst d{d_dst_, d_dst_ + n_mlp_, d_dst_ + 2 * (size_t)n_mlp_, (half_t*)d_pk_fwd_, (half_t*)d_pk_infer_[next], (half_t*)d_pk_bwd_};
+    const dim3 gm(ceil_div(n_mlp_, 256)), b(256);
+    const float* loss = d_loss_;
+    if (hash_) {
+        if (sgd_) hipLaunchKernelGGL((k_opt_pack<true, GuardArgs>), gm, b, 0, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_, lr, a, d, loss, loss_seq, loss_cell, ga);
+        else hipLaunchKernelGGL((k_opt_pack<false, GuardArgs>), gm, b, 0, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_, lr, a, d, loss, loss_seq, loss_cell, ga);
+        uint32_t *tt = (uint32_t*)d_t16_train_, *te = (uint32_t*)d_t16_ema_[next];
+        uint32_t* g16 = (uint32_t*)d_grad16_;
+        if (grid16_valid_) grad16_clean_ = true;      // k_grid_opt<., true> clears the entries it reads, on a bad step too
+        if (n_mlp_ % 4u == 0u && n_grid_entries_ % 2u == 0u) {
+            const uint32_t np = n_grid_entries_ / 2u;
+            const dim3 g2(ceil_div(np, 256));
+            if (sgd_ && grid16_valid_)
+                launch_last((k_grid_opt2<true, true, GuardArgs>), g2, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, np, lr, a, tt, te, ga);
+            else if (sgd_)
+                launch_last((k_grid_opt2<true, false, GuardArgs>), g2, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, np, lr, a, tt, te, ga);
+            else if (grid16_valid_)
+                launch_last((k_grid_opt2<false, true, GuardArgs>), g2, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, np, lr, a, tt, te, ga);
+            else
+                launch_last((k_grid_opt2<false, false, GuardArgs>), g2, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, np, lr, a, tt, te, ga);
+        } else {
+            const dim3 g(ceil_div(n_grid_entries_, 256));
+            const uint32_t ne = n_grid_entries_;
+            if (sgd_ && grid16_valid_)
+                launch_last((k_grid_opt<true, true, GuardArgs>), g, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, ne, lr, a, tt, te, ga);
+            else if (sgd_)
+                launch_last((k_grid_opt<true, false, GuardArgs>), g, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, ne, lr, a, tt, te, ga);
+            else if (grid16_valid_)
+                launch_last((k_grid_opt<false, true, GuardArgs>), g, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, ne, lr, a, tt, te, ga);
+            else
+                launch_last((k_grid_opt<false, false, GuardArgs>), g, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, ne, lr, a, tt, te, ga);
+        }
+    } else if (sgd_)
+        launch_last((k_opt_pack<true, GuardArgs>), gm, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_, lr, a, d, loss, loss_seq, loss_cell, ga);
+    else
+        launch_last((k_opt_pack<false, GuardArgs>), gm, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_, lr, a, d, loss, loss_seq, loss_cell, ga);
+    NRC_HIP(hipGetLastError());
+    infer_set_ = next;
+    return loss_cell != nullptr;
 }
 
 }  // namespace nrc

@@ -25,6 +25,34 @@ struct CompositeArgs {
     float blend_factor;
 };
 
+// The non-finite guard (include/nrc_hpm.h, nrc_cache_set_nonfinite_policy).  A pass that reads the final gradient stores `stamp` into
+// words[0] when a word of it, or the loss, is not finite; the optimizer kernels of the same step compare words[0] with `stamp` and turn
+// their update into the identity on a match.  Every scan gets a stamp of its own, so the word is never cleared: a verdict that is not
+// this step's does not match.  All writers of one scan store the same value (plain vector stores, no atomics).
+struct GuardArgs {
+    uint32_t* words = nullptr;                   // device: [0] stamp of the last bad scan, [1] skipped steps, [2] number of the last skipped step
+    unsigned long long* host_cell = nullptr;     // host-mapped copy of {[1], [2]}, one 8-byte store per skipped step
+    uint32_t stamp = 0, step = 0;
+};
+#if defined(__HIPCC__)
+__device__ __forceinline__ bool guard_nonfinite(float x) { return (__builtin_bit_cast(uint32_t, x) & 0x7f800000u) == 0x7f800000u; }
+// every lane of the (one-dimensional) block calls it; the first lane that found something stores for its wave
+__device__ __forceinline__ void guard_flag(bool bad, const GuardArgs& ga)
+{
+    const unsigned long long found = __ballot(bad);
+    if (found != 0ull && (threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)found) - 1)) ga.words[0] = ga.stamp;
+}
+__device__ __forceinline__ bool guard_bad(const GuardArgs& ga) { return ga.words[0] == ga.stamp; }
+// one thread of a bad step's first optimizer launch
+__device__ __forceinline__ void guard_count(const GuardArgs& ga)
+{
+    const uint32_t skipped = ga.words[1] + 1u;
+    ga.words[1] = skipped;
+    ga.words[2] = ga.step;
+    __hip_atomic_store(ga.host_cell, (unsigned long long)skipped | ((unsigned long long)ga.step << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+#endif
+
 void mlp_set_wave_priority_raise(int on);      // nrc_common.hpp: NRC_RAISE_WAVE_PRIORITY's run-time switch, nrc_mlp.hip's kernels
 
 class Mlp {
@@ -94,7 +122,24 @@ public:
     uint32_t step = 0;
     static constexpr float kLossScale = 128.0f;
 
+    // ---- non-finite guard (GuardArgs above).  Off (the default) nothing below is allocated, launched or read.
+    void set_guard(bool on);
+    bool guard_on() const { return guard_on_; }
+    // the gradient vector or the loss cell was rewritten behind backward()'s own scan (exchange, hook, a caller that holds the pointer):
+    // optimizer_step() scans again (k_guard_scan, one launch) unless a pass of the caller's does it first with guard_scan_args()
+    void guard_stale() { guard_scanned_ = false; }
+    // for a pass that scans the final gradient + loss itself: a fresh stamp; the next optimizer_step() reads that verdict
+    GuardArgs guard_scan_args();
+    // {skipped steps, number of the last skipped step} as of the last optimizer launch that has completed (a plain host read)
+    void guard_stats(uint32_t* skipped, uint32_t* last_step) const;
+
 private:
+    bool optimizer_step_guarded(hipStream_t s, uint32_t loss_seq, unsigned long long* loss_cell);
+    bool guard_on_ = false, guard_scanned_ = false;
+    uint32_t guard_stamp_ = 0;
+    uint32_t* d_guard_ = nullptr;                   // GuardArgs::words
+    unsigned long long* h_guard_ = nullptr;         // GuardArgs::host_cell (pinned, host-mapped)
+    unsigned long long* d_guard_cell_ = nullptr;    // its device address
     int num_cus();
     int num_cus_ = 0;
     bool attr_infer_set_ = false, attr_infer4_set_ = false, attr_train_set_ = false, attr_train2_set_ = false;     // hipFuncSetAttribute done on this instance's device
