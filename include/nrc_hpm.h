@@ -331,6 +331,23 @@ int nrc_renderer_set_scene_params(nrc_renderer_t* r, const nrc_scene* scene);
 #define NRC_VOLUME_U8 0
 #define NRC_VOLUME_F32 1
 int nrc_renderer_set_volume(nrc_renderer_t* r, const void* density, uint32_t nx, uint32_t ny, uint32_t nz, int format, int on_device);
+/* The same replacement from a sparse source: n_bricks bricks of 8 x 8 x 8 voxels (the leaf size of a VDB tree and the cell size of the
+ * renderer's empty-space boxes).  origins[3*i .. 3*i+2] is the voxel coordinate (x0, y0, z0) of brick i's first voxel; bricks holds
+ * n_bricks * 512 elements, voxel (x0+dx, y0+dy, z0+dz) of brick i at element 512*i + 64*dz + 8*dy + dx (an [8][8][8] array, x fastest,
+ * like the dense [nz][ny][nx]); format and its quantisation rule as above.  The volume keeps the dims of creation (they are not passed).
+ *   Whole replacement: every voxel no brick covers becomes 0, whatever the volume held before.  Brick voxels past the volume's edge are
+ *     ignored (the dims need not be multiples of 8); a brick of zeros is legal and leaves its cell empty; n_bricks = 0 (the pointers
+ *     may be NULL) is the empty medium.  When several bricks name one cell, the one with the highest index wins, deterministically.
+ *   An origin is valid when every component is a multiple of 8 and 0 <= x0 < nx, 0 <= y0 < ny, 0 <= z0 < nz.  A host list is checked:
+ *     a violation returns NRC_ERR_INVALID, the message names the brick, and the renderer is unchanged.  A device list cannot be
+ *     checked without a wait: a brick with an invalid origin is ignored on the device, and nothing is written out of bounds.
+ *   on_device applies to both pointers, as above: device memory is read on the creation stream and the call does not wait for the GPU;
+ *     host memory is copied (12*n + 512*n*element size bytes) and the call returns when the copy is done.  The vector loads of the
+ *     rebuild need bricks aligned to 4 elements (device memory; any allocation is); an unaligned pointer is read element by element.
+ * Everything else is as for nrc_renderer_set_volume: the order against frames enqueued before and after, the blending reset, what is
+ * kept (cache, optimizer state, training ring, schedule key), and in a sharded run every rank calls it with the whole list.  Dense and
+ * brick calls may be mixed freely.  The device buffers are the rebuild of the densified list, bit for bit. */
+int nrc_renderer_set_volume_bricks(nrc_renderer_t* r, const int32_t* origins, const void* bricks, uint32_t n_bricks, int format, int on_device);
 /* diagnostics: the current volume's device buffers after synchronising the renderer -- which 0: density [nz][ny][nx] u8, 1: occupancy
  * bits (uint32 words), 2: empty-space boxes float[6 * n] {lo.xyz, hi.xyz}; *bytes = their size (NULL, bytes 0: no boxes) */
 const void* nrc_renderer_volume_buffer(nrc_renderer_t* r, int which, size_t* bytes);
@@ -487,6 +504,8 @@ int nrc_mc_renderer_is_blending(nrc_mc_renderer_t* r);          /* include/engin
 int nrc_mc_renderer_set_scene_params(nrc_mc_renderer_t* r, const nrc_scene* scene);   /* see nrc_renderer_set_scene_params */
 /* see nrc_renderer_set_volume / nrc_renderer_volume_buffer (one stream: the volume is rewritten in stream order behind the frames) */
 int nrc_mc_renderer_set_volume(nrc_mc_renderer_t* r, const void* density, uint32_t nx, uint32_t ny, uint32_t nz, int format, int on_device);
+/* see nrc_renderer_set_volume_bricks */
+int nrc_mc_renderer_set_volume_bricks(nrc_mc_renderer_t* r, const int32_t* origins, const void* bricks, uint32_t n_bricks, int format, int on_device);
 const void* nrc_mc_renderer_volume_buffer(nrc_mc_renderer_t* r, int which, size_t* bytes);
 int nrc_mc_renderer_set_frame_random(nrc_mc_renderer_t* r, const float random4[4]);
 const float* nrc_mc_renderer_framebuffer(nrc_mc_renderer_t* r);   /* RGBA32F, alpha = blended didScatter */

@@ -456,6 +456,11 @@ public:
     {
         nrc_check(nrc_renderer_set_volume(h_, density, nx, ny, nz, format, onDevice ? 1 : 0));
     }
+    // the same from nBricks 8^3 bricks: origins int32[3 * n], bricks n * 512 elements; voxels no brick covers become 0 (nrc_renderer_set_volume_bricks)
+    void SetVolumeBricks(const int32_t* origins, const void* bricks, uint32_t nBricks, int format = NRC_VOLUME_U8, bool onDevice = true)
+    {
+        nrc_check(nrc_renderer_set_volume_bricks(h_, origins, bricks, nBricks, format, onDevice ? 1 : 0));
+    }
     nrc_renderer_t* Handle() const { return h_; }
 
 private:
@@ -501,6 +506,10 @@ public:
     void SetVolume(const void* density, uint32_t nx, uint32_t ny, uint32_t nz, int format = NRC_VOLUME_U8, bool onDevice = true)
     {
         nrc_check(nrc_mc_renderer_set_volume(h_, density, nx, ny, nz, format, onDevice ? 1 : 0));
+    }
+    void SetVolumeBricks(const int32_t* origins, const void* bricks, uint32_t nBricks, int format = NRC_VOLUME_U8, bool onDevice = true)
+    {
+        nrc_check(nrc_mc_renderer_set_volume_bricks(h_, origins, bricks, nBricks, format, onDevice ? 1 : 0));
     }
     nrc_mc_renderer_t* Handle() const { return h_; }
 

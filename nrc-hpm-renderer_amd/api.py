@@ -84,6 +84,7 @@ ABI_SYMBOLS = [
     "nrc_renderer_create", "nrc_renderer_render", "nrc_renderer_render_frames", "nrc_renderer_set_stage_events", "nrc_renderer_set_camera", "nrc_renderer_set_blend",
     "nrc_renderer_set_scene_params", "nrc_mc_renderer_set_scene_params",
     "nrc_renderer_set_volume", "nrc_mc_renderer_set_volume", "nrc_renderer_volume_buffer", "nrc_mc_renderer_volume_buffer",
+    "nrc_renderer_set_volume_bricks", "nrc_mc_renderer_set_volume_bricks",
     "nrc_renderer_set_show_nrc", "nrc_renderer_set_frame_random", "nrc_renderer_framebuffer", "nrc_renderer_framebuffer_on",
     "nrc_renderer_export_exr",
     "nrc_renderer_frame_time_ms", "nrc_renderer_stage_stats", "nrc_renderer_frame_timeline", "nrc_set_wave_priority_raise", "nrc_renderer_destroy", "nrc_renderer_buffer", "nrc_renderer_count_fetches",
@@ -148,6 +149,9 @@ def load_library():
     for name in ("nrc_renderer_set_volume", "nrc_mc_renderer_set_volume"):
         if hasattr(L, name):      # (an older build loaded through NRC_HPM_LIB has no volume swap)
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int]
+    for name in ("nrc_renderer_set_volume_bricks", "nrc_mc_renderer_set_volume_bricks"):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int]
     for name in ("nrc_renderer_volume_buffer", "nrc_mc_renderer_volume_buffer"):
         if hasattr(L, name):
             getattr(L, name).restype = C.c_void_p
@@ -317,6 +321,31 @@ def _set_volume(fn, h, vol):
         raise RuntimeError("SkyRenderer ERROR: SetVolume takes a contiguous CUDA tensor, uint8 or float32 [nz][ny][nx], or a uint8 numpy array")
     nz, ny, nx = vol.shape
     _check(fn(h, _dev_ptr(vol), nx, ny, nz, VOLUME_F32 if vol.dtype == torch.float32 else VOLUME_U8, 1))
+
+
+def _set_volume_bricks(fn, h, origins, bricks):
+    """SetVolumeBricks of both renderers: origins int32 [n][3] and bricks uint8 or float32 [n][8][8][8] ([dz][dy][dx]), both C-contiguous
+    numpy arrays (host memory: the call copies them and waits for the copy) or both contiguous CUDA torch tensors (read on the renderer's
+    stream; the call does not wait).  n = 0 is the empty medium."""
+    if isinstance(origins, np.ndarray) and isinstance(bricks, np.ndarray):
+        if origins.dtype != np.int32 or origins.ndim != 2 or origins.shape[1] != 3 or not origins.flags.c_contiguous \
+                or bricks.dtype not in (np.uint8, np.float32) or bricks.shape != (origins.shape[0], 8, 8, 8) or not bricks.flags.c_contiguous:
+            raise RuntimeError("SkyRenderer ERROR: SetVolumeBricks takes C-contiguous numpy arrays, origins int32 [n][3] and bricks uint8 or "
+                               "float32 [n][8][8][8] (got %s %s and %s %s)" % (origins.dtype, origins.shape, bricks.dtype, bricks.shape))
+        n = origins.shape[0]
+        fmt = VOLUME_F32 if bricks.dtype == np.float32 else VOLUME_U8
+        _check(fn(h, C.c_void_p(origins.ctypes.data) if n else None, C.c_void_p(bricks.ctypes.data) if n else None, n, fmt, 0))
+        return
+    import torch
+    ok = isinstance(origins, torch.Tensor) and isinstance(bricks, torch.Tensor) and origins.is_cuda and bricks.is_cuda \
+        and origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 3 and origins.is_contiguous() \
+        and bricks.dtype in (torch.uint8, torch.float32) and tuple(bricks.shape) == (origins.shape[0], 8, 8, 8) and bricks.is_contiguous()
+    if not ok:
+        raise RuntimeError("SkyRenderer ERROR: SetVolumeBricks takes contiguous CUDA tensors, origins int32 [n][3] and bricks uint8 or float32 "
+                           "[n][8][8][8], or two numpy arrays of those types")
+    n = origins.shape[0]
+    fmt = VOLUME_F32 if bricks.dtype == torch.float32 else VOLUME_U8
+    _check(fn(h, _dev_ptr(origins) if n else None, _dev_ptr(bricks) if n else None, n, fmt, 1))
 
 
 def _volume_buffer(fn, h, name, dims):
@@ -686,6 +715,11 @@ class NrcHpmRenderer:
         blending restarts, the cache keeps its weights"""
         _set_volume(self.L.nrc_renderer_set_volume, self.h, vol)
 
+    def SetVolumeBricks(self, origins, bricks):
+        """the same from 8^3 bricks (include/nrc_hpm.h, nrc_renderer_set_volume_bricks; scene.volume_to_bricks makes them of a dense volume):
+        origins int32 [n][3] (x, y, z: multiples of 8), bricks uint8 or float32 [n][8][8][8]; voxels no brick covers become 0"""
+        _set_volume_bricks(self.L.nrc_renderer_set_volume_bricks, self.h, origins, bricks)
+
     def VolumeBuffer(self, name):
         """device view of the current volume's 'density', 'occ_bits' or 'boxes' (after synchronising the renderer)"""
         return _volume_buffer(self.L.nrc_renderer_volume_buffer, self.h, name, (self._scene.nx, self._scene.ny, self._scene.nz))
@@ -899,6 +933,10 @@ class McHpmRenderer:
     def SetVolume(self, vol):
         """see NrcHpmRenderer.SetVolume"""
         _set_volume(self.L.nrc_mc_renderer_set_volume, self.h, vol)
+
+    def SetVolumeBricks(self, origins, bricks):
+        """see NrcHpmRenderer.SetVolumeBricks"""
+        _set_volume_bricks(self.L.nrc_mc_renderer_set_volume_bricks, self.h, origins, bricks)
 
     def VolumeBuffer(self, name):
         """see NrcHpmRenderer.VolumeBuffer"""

@@ -17,6 +17,9 @@ frame from rank 0 (nrc_renderer_gather_frame).  Rank 0 owns the log.  NRC_CLI_SH
 Animated media (new): `--vdb` with several files is a sequence.  Every file is densified over the union of their bboxes (one grid),
 uploaded once, and the renderer steps through them with NrcHpmRenderer.SetVolume, a new file every `--frames-per-volume` frames (the
 cache keeps training across the swaps).  `--benchmark` needs a single volume: there is no reference image of a moving medium.
+With `--bricks` the sequence is held as brick lists instead: every file's 8^3 leaves are read over the union bbox with its minimum
+snapped down to multiples of 8 (io_vdb.read_vdb_bricks; no dense array per file on the host or the device) and the renderer steps
+through them with NrcHpmRenderer.SetVolumeBricks.  The run prints the device bytes held per file, dense against bricks.
 """
 import argparse
 import math
@@ -36,6 +39,9 @@ def main(argv=None):
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--vdb", nargs="+", default=None, help="OpenVDB FloatGrid file(s) (Texture3D::FromVDB semantics); several = a sequence")
     ap.add_argument("--frames-per-volume", type=int, default=1, help="frames rendered with each volume of a --vdb sequence")
+    ap.add_argument("--bricks", action="store_true",
+                    help="hold a --vdb sequence on the device as lists of 8^3 bricks and step it with SetVolumeBricks (include/nrc_hpm.h, "
+                         "nrc_renderer_set_volume_bricks)")
     ap.add_argument("--volume", type=int, default=256, help="edge of the procedural fBm cloud when no --vdb is given")
     ap.add_argument("--env", choices=["white", "black", "sky"], default="white")
     ap.add_argument("--benchmark", action="store_true")
@@ -52,6 +58,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.benchmark and args.vdb and len(args.vdb) > 1:
         raise SystemExit("SkyRenderer ERROR: --benchmark needs a single --vdb volume (there is no reference image of a moving medium)")
+    if args.bricks and not (args.vdb and len(args.vdb) > 1):
+        raise SystemExit("SkyRenderer ERROR: --bricks goes with a --vdb sequence (several files)")
     if args.frames_per_volume < 1:
         raise SystemExit("SkyRenderer ERROR: --frames-per-volume must be at least 1")
 
@@ -79,8 +87,18 @@ def main(argv=None):
     cfg = api.AppConfig(["NRC-HPM-Renderer"] + (args.config or DEFAULT_ARGV))
     if args.self_train:
         cfg.c.self_train = 1
-    sequence = []
-    if args.vdb:
+    sequence, brick_lists = [], []
+    if args.vdb and args.bricks:
+        # bricks: only the creation volume (the densified first file) exists as a dense array
+        bbox = io_vdb.aligned_bbox(io_vdb.union_bbox(args.vdb))
+        dims = tuple(int(hi - lo + 1) for lo, hi in zip(bbox[0], bbox[1]))[::-1]      # (nz, ny, nx)
+        brick_lists = [io_vdb.read_vdb_bricks(p, bbox) for p in args.vdb]
+        for p, (_, b) in zip(args.vdb, brick_lists):
+            if len(b) and float(b.max()) != 1.0:      # (Texture3D::FromVDB's check, src/Texture3D.cpp:74)
+                raise RuntimeError("SkyRenderer ERROR: VDB is not normalized")
+        # (the first list densified: float32 [nz][ny][nx], quantised as quantize_density does)
+        density = (sc.bricks_to_volume(*brick_lists[0], dims) * np.float32(255.0)).astype(np.uint8)
+    elif args.vdb:
         bbox = io_vdb.union_bbox(args.vdb) if len(args.vdb) > 1 else None
         sequence = [sc.quantize_density(io_vdb.from_vdb(p, bbox)[0]) for p in args.vdb]
         density = sequence[0]
@@ -112,6 +130,13 @@ def main(argv=None):
     nrc_renderer = api.NrcHpmRenderer(lw, H, False, camera, cfg, scene, nrc, tile=tile)
     # a sequence: every volume uploaded once, swapped in on the device (every rank swaps the whole volume before the same frame)
     seq_dev = [torch.from_numpy(np.ascontiguousarray(v)).cuda() for v in sequence] if len(sequence) > 1 else []
+    # --bricks: every file's list uploaded once (float32 bricks, quantised by the rebuild as the dense path quantises on the host)
+    seq_bricks = [(torch.from_numpy(o).cuda(), torch.from_numpy(b).cuda()) for o, b in brick_lists]
+    if seq_bricks and rank == 0:
+        for p, (o, b) in zip(args.vdb, seq_bricks):
+            held = o.numel() * 4 + b.numel() * 4
+            print("%s: %d bricks, %d bytes on the device as float32 bricks (%d as uint8 bricks); dense %d bytes" %
+                  (os.path.basename(p), o.shape[0], held, o.numel() * 4 + b.numel(), density.size))
     out_dir = os.path.join(args.output, " " + cfg.GetName())
     log = None
     if rank == 0:
@@ -143,6 +168,8 @@ def main(argv=None):
     for frame in range(args.frames):
         if seq_dev and frame > 0 and frame % args.frames_per_volume == 0:
             nrc_renderer.SetVolume(seq_dev[(frame // args.frames_per_volume) % len(seq_dev)])
+        if seq_bricks and frame > 0 and frame % args.frames_per_volume == 0:
+            nrc_renderer.SetVolumeBricks(*seq_bricks[(frame // args.frames_per_volume) % len(seq_bricks)])
         nrc_renderer.Render(None, True)
         loss = nrc.GetLoss(wait=False)          # src/main.cu:376: polled every frame, never blocks the frame pipeline
         if (math.isnan(loss) or math.isinf(loss)) and not args.skip_nonfinite:      # src/main.cu:380-384; with the guard that step was skipped

@@ -2148,6 +2148,97 @@ __global__ __launch_bounds__(1024) void k_vol_rows(const uint8_t* __restrict__ c
     if (t == 0u) *n_boxes = base;
 }
 
+// ---- the same rebuild from a list of 8^3 bricks (nrc_renderer_set_volume_bricks): k_vol_brick_index + k_vol_ingest_bricks take
+// k_vol_ingest's place, k_vol_cells and k_vol_rows run behind them unchanged.
+//
+// One lane per brick: cell_brick[cell] = 1 + the highest index of the bricks that name the cell (cleared to 0 = none by the caller).
+// atomicMax on integers: which brick wins does not depend on the order the lanes run in.  An origin that is not a multiple of 8 or
+// lies outside the volume is ignored (a device list cannot be checked by the host without a wait).
+__global__ __launch_bounds__(256) void k_vol_brick_index(const int32_t* __restrict__ origins, uint32_t n_bricks, uint32_t* __restrict__ cell_brick,
+                                                        uint32_t nx, uint32_t ny, uint32_t nz, uint32_t gx, uint32_t gy)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_bricks) return;
+    const int32_t x0 = origins[3u * (size_t)i], y0 = origins[3u * (size_t)i + 1u], z0 = origins[3u * (size_t)i + 2u];
+    if ((x0 | y0 | z0) < 0 || ((x0 | y0 | z0) & 7) != 0) return;
+    if ((uint32_t)x0 >= nx || (uint32_t)y0 >= ny || (uint32_t)z0 >= nz) return;
+    atomicMax(&cell_brick[((size_t)((uint32_t)z0 >> 3) * gy + ((uint32_t)y0 >> 3)) * gx + ((uint32_t)x0 >> 3)], i + 1u);
+}
+
+// k_vol_ingest's decomposition -- one workgroup per (32 cells along x) x (one cell row), a lane owns four consecutive voxels of x in 16
+// of the 64 voxel rows -- with the voxels fetched from the bricks k_vol_brick_index named: element 64 * dz + 8 * dy + dx of brick b,
+// a lane's four are half a brick row (one 4- / 16-byte load when `aligned`: the brick base is aligned to 4 elements).  Every voxel of
+// the volume is written exactly once, zeros where no brick covers it: nothing of the density's old contents is read or kept.
+// vec: nx % 4 == 0 (one 4-byte store per lane and row).
+template <bool F32, bool VEC>
+__global__ __launch_bounds__(256) void k_vol_ingest_bricks(const void* __restrict__ bricks, const uint32_t* __restrict__ cell_brick,
+                                                          uint8_t* __restrict__ density, uint32_t* __restrict__ cell_mask, uint32_t nx, uint32_t ny,
+                                                          uint32_t nz, uint32_t gx, uint32_t gy, uint32_t n_chunks, uint32_t aligned)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    __shared__ uint32_t lmask[32];
+    __shared__ uint32_t lbrick[32];
+    const uint32_t t = threadIdx.x;
+    const uint32_t chunk = blockIdx.x % n_chunks, crow = blockIdx.x / n_chunks;
+    const uint32_t cy = crow % gy, cz = crow / gy;
+    if (t < 32u) {
+        const uint32_t cx = chunk * 32u + t;
+        lmask[t] = 0u;
+        lbrick[t] = cx < gx ? cell_brick[((size_t)cz * gy + cy) * gx + cx] : 0u;
+    }
+    __syncthreads();
+    const uint32_t x = chunk * 256u + 4u * (t & 63u);
+    uint32_t m = 0u;
+    if (x < nx) {
+        const uint32_t b = lbrick[(t & 63u) >> 1];
+        const size_t base = b ? (size_t)(b - 1u) * 512u + 4u * (t & 1u) : 0u;
+        uint32_t xs_q[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) xs_q[k] = x + k < nx ? vol_axis_set(x + k, nx) : 0u;
+        for (uint32_t r = t >> 6; r < 64u; r += 4u) {
+            const uint32_t y = cy * 8u + (r & 7u), z = cz * 8u + (r >> 3);
+            if (y >= ny || z >= nz) continue;
+            uint32_t q[4] = {0u, 0u, 0u, 0u};
+            if (b) {
+                const size_t e = base + 8u * r;      // 64 * dz + 8 * dy: r = 8 * dz + dy
+                if (F32) {
+                    float f[4];
+                    if (aligned) {
+                        const float4 v = *(const float4*)((const float*)bricks + e);
+                        f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+                    } else {
+#pragma unroll
+                        for (uint32_t k = 0; k < 4u; k++) f[k] = ((const float*)bricks)[e + k];
+                    }
+#pragma unroll
+                    for (uint32_t k = 0; k < 4u; k++) q[k] = vol_quantize(f[k]);
+                } else if (aligned) {
+                    const uint32_t w = *(const uint32_t*)((const uint8_t*)bricks + e);
+                    q[0] = w & 255u; q[1] = (w >> 8) & 255u; q[2] = (w >> 16) & 255u; q[3] = w >> 24;
+                } else {
+#pragma unroll
+                    for (uint32_t k = 0; k < 4u; k++) q[k] = (uint32_t)((const uint8_t*)bricks)[e + k];
+                }
+            }
+            const size_t idx = ((size_t)z * ny + y) * nx + x;
+            if (VEC) *(uint32_t*)(density + idx) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+            else {
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; k++) {
+                    if (x + k < nx) density[idx + k] = (uint8_t)q[k];      // (a brick voxel past the volume's edge is ignored: xs_q 0)
+                }
+            }
+            const uint32_t xs = (q[0] ? xs_q[0] : 0u) | (q[1] ? xs_q[1] : 0u) | (q[2] ? xs_q[2] : 0u) | (q[3] ? xs_q[3] : 0u);
+            if (xs) m |= vol_touch_mask(xs, vol_axis_set(y, ny), vol_axis_set(z, nz));
+        }
+    }
+    if (m) atomicOr(&lmask[(t & 63u) >> 1], m);
+    __syncthreads();
+    const uint32_t cx = chunk * 32u + t;
+    if (t < 32u && cx < gx) cell_mask[((size_t)cz * gy + cy) * gx + cx] = lmask[t];
+}
+
 }  // namespace
 
 // ================================================================================================ launchers
@@ -2228,12 +2319,12 @@ size_t volume_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t nz)
     return (size_t)ceil_div(nx, 8) * ceil_div(ny, 8) * ceil_div(nz, 8) * 5;
 }
 
+static void launch_volume_cells_rows(const VolumeRebuild& v, void* scratch, hipStream_t s);
+
 void launch_volume_rebuild(const void* src, int format, const VolumeRebuild& v, void* scratch, hipStream_t s)
 {
     const uint32_t gx = ceil_div(v.nx, 8), gy = ceil_div(v.ny, 8), gz = ceil_div(v.nz, 8);
-    const size_t cells = (size_t)gx * gy * gz;
     uint32_t* cell_mask = (uint32_t*)scratch;
-    uint8_t* cell_occ = (uint8_t*)(cell_mask + cells);
     const uint32_t n_chunks = ceil_div(gx, 32);
     const dim3 grid(n_chunks * gy * gz);
     const size_t align = format == NRC_VOLUME_F32 ? 16 : 4;
@@ -2242,6 +2333,41 @@ void launch_volume_rebuild(const void* src, int format, const VolumeRebuild& v, 
                                            : (vec ? k_vol_ingest<false, true> : k_vol_ingest<false, false>);
     hipLaunchKernelGGL(ingest, grid, dim3(256), 0, s, src, v.density, cell_mask, v.nx, v.ny, v.nz, gx, gy, n_chunks);
     NRC_HIP(hipGetLastError());
+    launch_volume_cells_rows(v, scratch, s);
+}
+
+size_t volume_brick_index_bytes(uint32_t nx, uint32_t ny, uint32_t nz)
+{
+    return (size_t)ceil_div(nx, 8) * ceil_div(ny, 8) * ceil_div(nz, 8) * 4;
+}
+
+void launch_volume_rebuild_bricks(const int32_t* origins, const void* bricks, uint32_t n_bricks, int format, const VolumeRebuild& v, void* scratch,
+                                  uint32_t* brick_index, hipStream_t s)
+{
+    const uint32_t gx = ceil_div(v.nx, 8), gy = ceil_div(v.ny, 8), gz = ceil_div(v.nz, 8);
+    NRC_HIP(hipMemsetAsync(brick_index, 0, volume_brick_index_bytes(v.nx, v.ny, v.nz), s));
+    if (n_bricks) {
+        hipLaunchKernelGGL(k_vol_brick_index, dim3(ceil_div(n_bricks, 256)), dim3(256), 0, s, origins, n_bricks, brick_index, v.nx, v.ny, v.nz, gx, gy);
+        NRC_HIP(hipGetLastError());
+    }
+    const uint32_t n_chunks = ceil_div(gx, 32);
+    const bool f32 = format == NRC_VOLUME_F32, vec = v.nx % 4 == 0;
+    const uint32_t aligned = (uintptr_t)bricks % (f32 ? 16 : 4) == 0 ? 1u : 0u;
+    auto ingest = f32 ? (vec ? k_vol_ingest_bricks<true, true> : k_vol_ingest_bricks<true, false>)
+                      : (vec ? k_vol_ingest_bricks<false, true> : k_vol_ingest_bricks<false, false>);
+    hipLaunchKernelGGL(ingest, dim3(n_chunks * gy * gz), dim3(256), 0, s, bricks, (const uint32_t*)brick_index, v.density, (uint32_t*)scratch,
+                       v.nx, v.ny, v.nz, gx, gy, n_chunks, aligned);
+    NRC_HIP(hipGetLastError());
+    launch_volume_cells_rows(v, scratch, s);
+}
+
+// the two launches behind either ingest: scratch holds the cells' touch masks, then their occupancy flags
+static void launch_volume_cells_rows(const VolumeRebuild& v, void* scratch, hipStream_t s)
+{
+    const uint32_t gx = ceil_div(v.nx, 8), gy = ceil_div(v.ny, 8), gz = ceil_div(v.nz, 8);
+    const size_t cells = (size_t)gx * gy * gz;
+    uint32_t* cell_mask = (uint32_t*)scratch;
+    uint8_t* cell_occ = (uint8_t*)(cell_mask + cells);
     const uint32_t cell_blocks = ceil_div((uint32_t)cells, 256), occ_blocks = ceil_div(v.occ_words * 32u, 256);
     hipLaunchKernelGGL(k_vol_cells, dim3(cell_blocks + occ_blocks), dim3(256), 0, s, (const uint32_t*)cell_mask, cell_occ, v.occ_bits, gx, gy, gz,
                        cell_blocks, v.occ_shift, v.occ_gx, v.occ_gy, v.occ_gz, v.occ_words);

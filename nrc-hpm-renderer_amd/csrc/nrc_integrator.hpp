@@ -133,6 +133,13 @@ uint32_t volume_box_capacity(uint32_t nx, uint32_t ny, uint32_t nz);
 size_t volume_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
 // scratch: volume_scratch_bytes; src must stay unchanged until the launches on s have run.  Three launches.
 void launch_volume_rebuild(const void* src, int format, const VolumeRebuild& v, void* scratch, hipStream_t s);
+// the same from n_bricks 8^3 bricks in device memory (nrc_renderer_set_volume_bricks: origins int32[3 * n], bricks n * 512 elements of
+// `format`): voxels no brick covers become 0, the highest index wins a cell named twice, an invalid origin is ignored.  brick_index:
+// volume_brick_index_bytes (one word per 8^3 cell), scratch as above.  A clear and four launches (three when n_bricks == 0); the result is
+// what launch_volume_rebuild makes of the densified list, bit for bit.
+size_t volume_brick_index_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+void launch_volume_rebuild_bricks(const int32_t* origins, const void* bricks, uint32_t n_bricks, int format, const VolumeRebuild& v, void* scratch,
+                                  uint32_t* brick_index, hipStream_t s);
 // table[m] = optical distance covered by the 128 free flights a delta walk draws from RNG state m when it rejects every collision
 constexpr uint32_t kFlightStates = 1u << 23;
 constexpr uint32_t kFlightListMax = 8;

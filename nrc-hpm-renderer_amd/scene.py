@@ -79,6 +79,45 @@ def quantize_density(vol_f32):
     return np.ascontiguousarray(q.transpose(2, 1, 0))
 
 
+def volume_to_bricks(vol):
+    """A dense [nz][ny][nx] uint8 or float32 volume as the brick list of SetVolumeBricks (include/nrc_hpm.h, nrc_renderer_set_volume_bricks):
+    (origins int32 [n][3] = (x0, y0, z0), bricks [n][8][8][8] = [dz][dy][dx]) of the aligned 8^3 cells that hold a non-zero voxel, in
+    cell order z, y, x; cells at the volume's edge are padded with zeros."""
+    vol = np.asarray(vol)
+    if vol.ndim != 3 or vol.dtype not in (np.uint8, np.float32):
+        raise ValueError("volume_to_bricks: a [nz][ny][nx] uint8 or float32 array (got %s %s)" % (vol.dtype, vol.shape))
+    nz, ny, nx = vol.shape
+    gz, gy, gx = (nz + 7) // 8, (ny + 7) // 8, (nx + 7) // 8
+    padded = np.zeros((gz * 8, gy * 8, gx * 8), vol.dtype)
+    padded[:nz, :ny, :nx] = vol
+    cells = padded.reshape(gz, 8, gy, 8, gx, 8).transpose(0, 2, 4, 1, 3, 5)      # [cz][cy][cx][dz][dy][dx]
+    cz, cy, cx = np.nonzero((cells != 0).any(axis=(3, 4, 5)))
+    origins = (np.stack([cx, cy, cz], axis=1) * 8).astype(np.int32).reshape(-1, 3)
+    return np.ascontiguousarray(origins), np.ascontiguousarray(cells[cz, cy, cx]).reshape(-1, 8, 8, 8)
+
+
+def bricks_to_volume(origins, bricks, dims, ignore_invalid=False):
+    """The dense volume a brick list stands for, dims = its shape (nz, ny, nx): the inverse of volume_to_bricks and the CPU statement of
+    SetVolumeBricks.  Voxels no brick covers are 0, brick voxels past the edge are dropped, of several bricks with one origin the last
+    wins.  An origin that is not a multiple of 8 inside the volume raises ValueError (what the call does with a host list) or, with
+    ignore_invalid, is skipped (what the kernels do with a device list)."""
+    origins, bricks = np.asarray(origins), np.asarray(bricks)
+    n = origins.shape[0]
+    if origins.shape != (n, 3) or bricks.shape != (n, 8, 8, 8):
+        raise ValueError("bricks_to_volume: origins [n][3] and bricks [n][8][8][8] (got %s and %s)" % (origins.shape, bricks.shape))
+    nz, ny, nx = (int(v) for v in dims)
+    vol = np.zeros((nz, ny, nx), bricks.dtype)
+    for i in range(n):
+        x0, y0, z0 = (int(v) for v in origins[i])
+        if min(x0, y0, z0) < 0 or x0 % 8 or y0 % 8 or z0 % 8 or x0 >= nx or y0 >= ny or z0 >= nz:
+            if ignore_invalid:
+                continue
+            raise ValueError("bricks_to_volume: brick %d has origin (%d, %d, %d): multiples of 8 inside %dx%dx%d" % (i, x0, y0, z0, nx, ny, nz))
+        ez, ey, ex = min(8, nz - z0), min(8, ny - y0), min(8, nx - x0)
+        vol[z0:z0 + ez, y0:y0 + ey, x0:x0 + ex] = bricks[i, :ez, :ey, :ex]
+    return vol
+
+
 def white_env(value=1.0):
     """Quirk Q9 (src/read_file.cpp:129-130): every loaded env texel is overwritten with 1.0."""
     return np.full((1, 1, 4), value, np.float32)
