@@ -311,6 +311,34 @@ int nrc_renderer_render(nrc_renderer_t* r, int train);
 int nrc_renderer_render_frames(nrc_renderer_t* r, uint32_t n_frames, const float* frame_randoms, int train);
 /* NrcHpmRenderer::SetCamera / SetBlend (src/NrcHpmRenderer.cu:561-610) */
 int nrc_renderer_set_camera(nrc_renderer_t* r, const nrc_camera* camera);
+/* A camera path (a turntable, a fly-through; the reference has no equivalent): n_cameras views of frames_per_camera frames each,
+ * enqueued by one call that does not wait for the GPU.  It computes, bit for bit, what this loop computes --
+ *     for i in 0 .. n_cameras-1:  set_camera(cameras[i]);
+ *                                 for k in 0 .. frames_per_camera-1:  [set_frame_random(frame_randoms + 4*(i*fpc + k))]  render(train)
+ *                                 copy the framebuffer to d_frames + i*h*w*4
+ * -- framebuffer, d_frames and, with train, the cache's loss, weights, optimizer state, step and training ring; but where set_camera
+ * waits for every frame in flight, a view here starts behind the previous one on the device: the frames in flight keep their camera,
+ * blending restarts at every view, the accumulation image is cleared behind the previous view's last compositing and copy, and the
+ * empty-space tile mask of the view is built by kernels that run in parallel over the mask (the same words as set_camera's mask).
+ *   cameras        host memory, n_cameras entries.
+ *   frame_randoms  n_cameras * frames_per_camera * 4 host floats, or NULL: the renderer draws them, in the sequence that many
+ *                  consecutive Render calls would.
+ *   d_frames       device memory, [n_cameras][h][w][4] RGBA32F (local columns of a sharded renderer), or NULL: only the last view
+ *                  stays, in the framebuffer.  View i is copied on the stream of its last compositing, behind it.  When the call returns
+ *                  the stream given at creation has been made to wait, on the device, for the last copy: work enqueued on that stream
+ *                  afterwards sees all of d_frames (the contract of nrc_renderer_framebuffer).
+ * n_cameras == 0 is a no-op; otherwise cameras == NULL or frames_per_camera == 0 returns NRC_ERR_INVALID and leaves the renderer
+ * unchanged.  No hipStreamSynchronize, no blocking copy -- with two exceptions that are not the path's: a renderer's very first tile
+ * mask reads 36 bytes back (the selection of capped RNG states, kept from then on), and while the schedule tuner plays a trial Render
+ * bounds the host's run-ahead.  The tuner discards a trial window that contains a view change (no schedule measured across views reaches
+ * the schedule cache) and starts its trials again 128 frames after the path's last view change.  The first path of a renderer allocates 8 bytes per
+ * empty-space box.  In a sharded run every rank makes the same call. */
+int nrc_renderer_render_path(nrc_renderer_t* r, uint32_t n_cameras, const nrc_camera* cameras, uint32_t frames_per_camera,
+                             const float* frame_randoms, int train, float* d_frames);
+/* diagnostics: the empty-space tile mask in use after synchronising: n = nrc_renderer_tile_mask(r, NULL, 0) words
+ * (ceil(tiles / 32) bit words, tile ty * ceil(w / 8) + tx at bit id % 32 of word id / 32, + the trailing "mask off for this camera"
+ * word); 0 words when the frame uses no mask (empty skip off, no perspective camera, a medium too dense for it) */
+size_t nrc_renderer_tile_mask(nrc_renderer_t* r, uint32_t* host_out, size_t capacity);
 int nrc_renderer_set_blend(nrc_renderer_t* r, int blend);
 /* The uniform-buffer half of the scene -- DirLight / PointLight / VolumeData / HdrEnvMap strength (src/DirLight.cpp:31-49,
  * src/HpmScene.cpp:56-76 `HpmScene::Update`, the ImGui light editors): takes effect with the next Render and does not reset
@@ -502,6 +530,11 @@ int nrc_mc_renderer_set_empty_skip(nrc_mc_renderer_t* r, int on);   /* see nrc_r
 int nrc_mc_renderer_set_cost_order(nrc_mc_renderer_t* r, int on);   /* see nrc_renderer_set_cost_order */
 int nrc_mc_renderer_is_blending(nrc_mc_renderer_t* r);          /* include/engine/graphics/renderer/McHpmRenderer.hpp */
 int nrc_mc_renderer_set_scene_params(nrc_mc_renderer_t* r, const nrc_scene* scene);   /* see nrc_renderer_set_scene_params */
+/* see nrc_renderer_render_path (no train flag; one stream: views, frames and copies follow each other in stream order) and
+ * nrc_renderer_tile_mask */
+int nrc_mc_renderer_render_path(nrc_mc_renderer_t* r, uint32_t n_cameras, const nrc_camera* cameras, uint32_t frames_per_camera,
+                                const float* frame_randoms, float* d_frames);
+size_t nrc_mc_renderer_tile_mask(nrc_mc_renderer_t* r, uint32_t* host_out, size_t capacity);
 /* see nrc_renderer_set_volume / nrc_renderer_volume_buffer (one stream: the volume is rewritten in stream order behind the frames) */
 int nrc_mc_renderer_set_volume(nrc_mc_renderer_t* r, const void* density, uint32_t nx, uint32_t ny, uint32_t nz, int format, int on_device);
 /* see nrc_renderer_set_volume_bricks */

@@ -448,6 +448,21 @@ public:
     }
     void SetCamera(void* /*queue*/, const nrc_camera* camera) { nrc_check(nrc_renderer_set_camera(h_, camera)); }
     void SetCamera(void* queue, const Camera* camera) { SetCamera(queue, camera->Matrices()); }
+    // nCameras views of framesPerCamera frames each, enqueued by one call that does not wait for the GPU: SetCamera + Render per view, bit
+    // for bit (nrc_renderer_render_path).  frameRandoms: nCameras * framesPerCamera * 4 floats or nullptr; dFrames: device
+    // [nCameras][height][width][4] or nullptr (the last view stays in GetImage())
+    void RenderPath(void* /*queue*/, uint32_t nCameras, const nrc_camera* cameras, uint32_t framesPerCamera, const float* frameRandoms, bool train,
+                    float* dFrames)
+    {
+        nrc_check(nrc_renderer_render_path(h_, nCameras, cameras, framesPerCamera, frameRandoms, train ? 1 : 0, dFrames));
+    }
+    // diagnostics: the empty-space tile mask in use (synchronises; empty: the frame uses none) -- nrc_renderer_tile_mask
+    std::vector<uint32_t> TileMask() const
+    {
+        std::vector<uint32_t> m(nrc_renderer_tile_mask(h_, nullptr, 0));
+        if (!m.empty() && nrc_renderer_tile_mask(h_, m.data(), m.size()) != m.size()) nrc_check(NRC_ERR_STATE);
+        return m;
+    }
     void SetBlend(bool blend) { nrc_check(nrc_renderer_set_blend(h_, blend ? 1 : 0)); }
     void SetSceneParams(const nrc_scene& scene) { nrc_check(nrc_renderer_set_scene_params(h_, &scene)); }   // HpmScene::Update
     void SetSceneParams(const HpmScene& scene) { SetSceneParams(scene.Scene()); }
@@ -499,6 +514,17 @@ public:
     float GetFrameTimeMS() const { return frame_ms_; }
     void SetCamera(void* /*queue*/, const nrc_camera* camera) { nrc_check(nrc_mc_renderer_set_camera(h_, camera)); }
     void SetCamera(void* queue, const Camera* camera) { SetCamera(queue, camera->Matrices()); }
+    // see NrcHpmRenderer::RenderPath / TileMask (nrc_mc_renderer_render_path, nrc_mc_renderer_tile_mask)
+    void RenderPath(void* /*queue*/, uint32_t nCameras, const nrc_camera* cameras, uint32_t framesPerCamera, const float* frameRandoms, float* dFrames)
+    {
+        nrc_check(nrc_mc_renderer_render_path(h_, nCameras, cameras, framesPerCamera, frameRandoms, dFrames));
+    }
+    std::vector<uint32_t> TileMask() const
+    {
+        std::vector<uint32_t> m(nrc_mc_renderer_tile_mask(h_, nullptr, 0));
+        if (!m.empty() && nrc_mc_renderer_tile_mask(h_, m.data(), m.size()) != m.size()) nrc_check(NRC_ERR_STATE);
+        return m;
+    }
     void SetBlend(bool blend) { nrc_check(nrc_mc_renderer_set_blend(h_, blend ? 1 : 0)); }
     bool IsBlending() const { return nrc_mc_renderer_is_blending(h_) != 0; }
     void SetSceneParams(const nrc_scene& scene) { nrc_check(nrc_mc_renderer_set_scene_params(h_, &scene)); }

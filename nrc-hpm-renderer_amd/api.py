@@ -85,6 +85,7 @@ ABI_SYMBOLS = [
     "nrc_renderer_set_scene_params", "nrc_mc_renderer_set_scene_params",
     "nrc_renderer_set_volume", "nrc_mc_renderer_set_volume", "nrc_renderer_volume_buffer", "nrc_mc_renderer_volume_buffer",
     "nrc_renderer_set_volume_bricks", "nrc_mc_renderer_set_volume_bricks",
+    "nrc_renderer_render_path", "nrc_mc_renderer_render_path", "nrc_renderer_tile_mask", "nrc_mc_renderer_tile_mask",
     "nrc_renderer_set_show_nrc", "nrc_renderer_set_frame_random", "nrc_renderer_framebuffer", "nrc_renderer_framebuffer_on",
     "nrc_renderer_export_exr",
     "nrc_renderer_frame_time_ms", "nrc_renderer_stage_stats", "nrc_renderer_frame_timeline", "nrc_set_wave_priority_raise", "nrc_renderer_destroy", "nrc_renderer_buffer", "nrc_renderer_count_fetches",
@@ -156,6 +157,13 @@ def load_library():
         if hasattr(L, name):
             getattr(L, name).restype = C.c_void_p
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
+    for name in ("nrc_renderer_tile_mask", "nrc_mc_renderer_tile_mask"):
+        if hasattr(L, name):      # (an older build loaded through NRC_HPM_LIB has no camera paths)
+            getattr(L, name).restype = C.c_size_t
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    if hasattr(L, "nrc_renderer_render_path"):
+        L.nrc_renderer_render_path.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
+        L.nrc_mc_renderer_render_path.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.nrc_mc_renderer_frame_time_ms.restype = C.c_float
     for name in ("nrc_cache_get_loss", "nrc_cache_get_loss_blocking", "nrc_renderer_is_blending", "nrc_mc_renderer_is_blending",
                  "nrc_cache_get_infer_batch_count", "nrc_cache_get_train_batch_count",
@@ -346,6 +354,40 @@ def _set_volume_bricks(fn, h, origins, bricks):
     n = origins.shape[0]
     fmt = VOLUME_F32 if bricks.dtype == torch.float32 else VOLUME_U8
     _check(fn(h, _dev_ptr(origins) if n else None, _dev_ptr(bricks) if n else None, n, fmt, 1))
+
+
+def _render_path(call, width, height, cameras, framesPerCamera, frameRandoms, out):
+    """RenderPath of both renderers: cameras is a sequence of scene.make_camera dicts, frameRandoms None or [len(cameras) * framesPerCamera][4],
+    out None (a new tensor is returned) or a contiguous float32 CUDA tensor [len(cameras)][height][width][4], or False (no images: the last
+    view stays in GetImage()).  call(n, cameras pointer, frames per camera, randoms pointer, images pointer) makes the library call."""
+    import torch
+    cams = list(cameras)
+    n, fpc = len(cams), int(framesPerCamera)
+    if fpc < 0:
+        raise ValueError("RenderPath: framesPerCamera must not be negative")
+    arr = (NrcCamera * max(n, 1))(*[make_c_camera(c) for c in cams])
+    r = None
+    if frameRandoms is not None:
+        r = np.ascontiguousarray(frameRandoms, np.float32).reshape(-1)
+        if r.size != n * fpc * 4:
+            raise ValueError("RenderPath: frameRandoms holds %d floats, %d views x %d frames need %d" % (r.size, n, fpc, n * fpc * 4))
+    shape = (n, height, width, 4)
+    if out is None:
+        out = torch.empty(shape, device="cuda", dtype=torch.float32)
+    elif out is not False:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError("RenderPath: out must be a contiguous float32 CUDA tensor of shape %s" % (shape,))
+    _check(call(C.c_uint32(n), C.cast(arr, C.c_void_p), C.c_uint32(fpc), C.c_void_p(r.ctypes.data) if r is not None else None,
+                _dev_ptr(out) if out is not False and n else None))
+    return None if out is False else out
+
+
+def _tile_mask(fn, h):
+    n = fn(h, None, C.c_size_t(0))
+    out = np.zeros(n, np.uint32)
+    if n and fn(h, out.ctypes.data_as(C.c_void_p), C.c_size_t(n)) != n:
+        raise RuntimeError(load_library().nrc_last_error().decode() or "tile_mask failed")
+    return out
 
 
 def _volume_buffer(fn, h, name, dims):
@@ -702,6 +744,19 @@ class NrcHpmRenderer:
         cam = make_c_camera(camera)
         _check(self.L.nrc_renderer_set_camera(self.h, C.byref(cam)))
 
+    def RenderPath(self, cameras, framesPerCamera, frameRandoms=None, train=False, out=None):
+        """a camera path (include/nrc_hpm.h, nrc_renderer_render_path): for every camera of `cameras` (scene.make_camera / scene.orbit_cameras)
+        SetCamera + framesPerCamera Render calls, bit for bit, enqueued by one call that does not wait for the GPU.  Returns the views as a
+        torch CUDA tensor [n, height, width, 4] (`out` when given; out=False: no images, the last view stays in GetImage()); the stream given
+        at construction is ordered behind the last view's copy.  frameRandoms: None or [n * framesPerCamera][4]."""
+        return _render_path(lambda n, cams, fpc, rnd, img: self.L.nrc_renderer_render_path(self.h, n, cams, fpc, rnd, C.c_int(int(bool(train))), img),
+                            self.width, self.height, cameras, framesPerCamera, frameRandoms, out)
+
+    def TileMask(self):
+        """the empty-space tile mask in use (numpy uint32: the bit words + the trailing "off for this camera" word; empty: no mask in use);
+        synchronises the renderer"""
+        return _tile_mask(self.L.nrc_renderer_tile_mask, self.h)
+
     def SetBlend(self, blend):
         _check(self.L.nrc_renderer_set_blend(self.h, C.c_int(int(blend))))
 
@@ -913,6 +968,17 @@ class McHpmRenderer:
     def SetCamera(self, queue, camera):
         cam = make_c_camera(camera)
         _check(self.L.nrc_mc_renderer_set_camera(self.h, C.byref(cam)))
+
+    def RenderPath(self, cameras, framesPerCamera, frameRandoms=None, train=False, out=None):
+        """see NrcHpmRenderer.RenderPath (this renderer does not train: `train` must be False)"""
+        if train:
+            raise ValueError("McHpmRenderer.RenderPath: the Monte Carlo renderer has nothing to train")
+        return _render_path(lambda n, cams, fpc, rnd, img: self.L.nrc_mc_renderer_render_path(self.h, n, cams, fpc, rnd, img),
+                            self.width, self.height, cameras, framesPerCamera, frameRandoms, out)
+
+    def TileMask(self):
+        """see NrcHpmRenderer.TileMask"""
+        return _tile_mask(self.L.nrc_mc_renderer_tile_mask, self.h)
 
     def SetBlend(self, blend):
         _check(self.L.nrc_mc_renderer_set_blend(self.h, C.c_int(int(blend))))

@@ -17,6 +17,9 @@ frame from rank 0 (nrc_renderer_gather_frame).  Rank 0 owns the log.  NRC_CLI_SH
 Animated media (new): `--vdb` with several files is a sequence.  Every file is densified over the union of their bboxes (one grid),
 uploaded once, and the renderer steps through them with NrcHpmRenderer.SetVolume, a new file every `--frames-per-volume` frames (the
 cache keeps training across the swaps).  `--benchmark` needs a single volume: there is no reference image of a moving medium.
+Camera paths (new): `--orbit N` renders an N-view turntable around the volume (scene.orbit_cameras) with one
+NrcHpmRenderer.RenderPath call -- `--frames` frames per view, trained like the per-frame loop's -- instead of the loop below; an
+`--export` name with a printf integer conversion (out_%04d.exr) then writes one file per view.
 With `--bricks` the sequence is held as brick lists instead: every file's 8^3 leaves are read over the union bbox with its minimum
 snapped down to multiples of 8 (io_vdb.read_vdb_bricks; no dense array per file on the host or the device) and the renderer steps
 through them with NrcHpmRenderer.SetVolumeBricks.  The run prints the device bytes held per file, dense against bricks.
@@ -24,9 +27,39 @@ through them with NrcHpmRenderer.SetVolumeBricks.  The run prints the device byt
 import argparse
 import math
 import os
+import re
 import sys
 
 import numpy as np
+
+def export_paths(pattern, n_views):
+    """--export: the files a run writes -- a name with a printf integer conversion (out_%04d.exr) once per view, any other name once"""
+    if pattern is None:
+        return []
+    if "%" not in pattern:
+        return [pattern]
+    if pattern.count("%") != 1 or len(re.findall(r"%0?[0-9]*[di]", pattern)) != 1:
+        raise SystemExit("SkyRenderer ERROR: --export %r is not a file name with one integer conversion such as out_%%04d.exr" % pattern)
+    return [pattern % k for k in range(n_views)]
+
+
+def check_orbit_args(args):
+    """what --orbit can be combined with (raises SystemExit); returns the number of views, 0 without --orbit"""
+    if args.orbit is None:      # (an --export name is then taken literally, as it always was)
+        return 0
+    if args.orbit < 1:
+        raise SystemExit("SkyRenderer ERROR: --orbit must be at least 1")
+    if args.frames < 1:
+        raise SystemExit("SkyRenderer ERROR: --orbit needs --frames of at least 1 (frames per view)")
+    if args.benchmark:
+        raise SystemExit("SkyRenderer ERROR: --orbit and --benchmark exclude each other (the reference image belongs to one camera)")
+    if args.vdb and len(args.vdb) > 1:
+        raise SystemExit("SkyRenderer ERROR: --orbit takes one volume, not a --vdb sequence")
+    if args.gpus > 1 and args.export and "%" in args.export:
+        raise SystemExit("SkyRenderer ERROR: one file per view (--export with %) is not available with --gpus")
+    export_paths(args.export, args.orbit)
+    return args.orbit
+
 
 DEFAULT_ARGV = ["RelativeL2Luminance", "Adam", "0.01", "0.99", "0", "0", "64", "6", "21", "14", "4", "4", "1.0", "1", "1", "0.0", "32"]
 
@@ -48,7 +81,12 @@ def main(argv=None):
     ap.add_argument("--reference", default=None, help="reference EXR (e.g. reference/4/0.exr of the reference repo)")
     ap.add_argument("--ref-frames", type=int, default=256)
     ap.add_argument("--output", default="output")
-    ap.add_argument("--export", default=None, help="write the final NRC image to this EXR")
+    ap.add_argument("--export", default=None, help="write the final NRC image to this EXR; with --orbit a pattern such as out_%%04d.exr writes one file per view")
+    ap.add_argument("--orbit", type=int, default=None, metavar="N",
+                    help="render an N-view turntable around the volume with one RenderPath call (include/nrc_hpm.h, nrc_renderer_render_path): "
+                         "--frames frames per view")
+    ap.add_argument("--orbit-radius", type=float, default=64.0)
+    ap.add_argument("--orbit-height", type=float, default=0.0)
     ap.add_argument("--gpus", type=int, default=1, help="ranks the frame is sharded over (one GPU each)")
     ap.add_argument("--skip-nonfinite", action="store_true",
                     help="training guard: a step whose loss or gradient is not finite is skipped and counted instead of ending the run "
@@ -62,6 +100,7 @@ def main(argv=None):
         raise SystemExit("SkyRenderer ERROR: --bricks goes with a --vdb sequence (several files)")
     if args.frames_per_volume < 1:
         raise SystemExit("SkyRenderer ERROR: --frames-per-volume must be at least 1")
+    n_views = check_orbit_args(args)
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # start the ranks before anything touches the GPU in this process (a process that has initialised HIP must not spawn them)
@@ -165,7 +204,22 @@ def main(argv=None):
     # only NOTES a bad loss, the flag is max-reduced every kStopEvery frames (and at the last one), and all ranks leave at that frame.
     kStopEvery = 8
     bad, failed = False, False
-    for frame in range(args.frames):
+    if n_views:
+        # a turntable: every view's frames enqueued by one call that does not wait for the GPU; every rank makes the same call
+        views = sc.orbit_cameras(n_views, args.orbit_radius, args.orbit_height, aspect=W / H)
+        per_view = args.export is not None and "%" in args.export
+        images = nrc_renderer.RenderPath(views, args.frames, train=True, out=None if per_view else False)
+        loss = nrc.GetLoss(wait=True)
+        failed = (math.isnan(loss) or math.isinf(loss)) and not args.skip_nonfinite      # (the all-reduced loss: the same on every rank)
+        if failed:
+            print("SkyRenderer ERROR: NRC Loss is %s" % loss, file=sys.stderr)
+        elif rank == 0:
+            print("orbit: %d views x %d frames, loss %.5f" % (n_views, args.frames, loss))
+        if per_view and not failed:
+            host = images.cpu().numpy()
+            for path, img in zip(export_paths(args.export, n_views), host):
+                io_exr.write_exr(path, img)
+    for frame in range(0 if n_views else args.frames):
         if seq_dev and frame > 0 and frame % args.frames_per_volume == 0:
             nrc_renderer.SetVolume(seq_dev[(frame // args.frames_per_volume) % len(seq_dev)])
         if seq_bricks and frame > 0 and frame % args.frames_per_volume == 0:
@@ -199,7 +253,7 @@ def main(argv=None):
         log.close()
     if args.skip_nonfinite and rank == 0:
         print("skipped %d of %d steps" % (nrc.GetSkippedSteps()[0], nrc.GetStep()))
-    if args.export and not failed:
+    if args.export and not failed and not (n_views and "%" in args.export):
         nrc_renderer.ExportOutputImageToFile(None, args.export)      # sharded: collective, rank 0 writes the whole frame
     nrc_renderer.Destroy()
     if ref is not None:

@@ -1406,8 +1406,14 @@ __global__ __launch_bounds__(1024) void k_tile_order_xcd(uint32_t* __restrict__ 
 // corners are projected with the camera's forward transform; the screen rectangle around them, grown by a pixel, covers every
 // pixel whose camera ray can pass through the box (a pixel's ray consists of the points that project onto the pixel).  The 8x8
 // tiles the rectangle touches are marked.  A box with a corner at or behind the eye plane switches the mask off for this camera.
+// kRects (k_tile_rects, the tile-parallel build below): instead of marking tiles, the box's tile rectangle goes to *rect, packed into 64
+// bits, tx0 | tx1 << 16 | ty0 << 32 | ty1 << 48 (camera_slots bounds a frame's tiles far below 2^16 per axis); a box behind the eye plane
+// and one off screen are two sentinels whose row range ty0 > ty1 is empty.  One body, so that the two builds agree to the last bit.
+constexpr unsigned long long kTileRectOff = 0x0000ffff00000000ull | 0xfffeull;        // ty0 = 0xffff > ty1 = 0, tx0 = 0xfffe: behind
+constexpr unsigned long long kTileRectNone = 0x0000ffff00000000ull | 0xffffull;       // ... tx0 = 0xffff: off screen
+template <bool kRects = false>
 __device__ __forceinline__ void tile_mask_box(const float* __restrict__ boxes, uint32_t i, const DevProjView& pv, const DevFrame& fr,
-                                              uint32_t* __restrict__ mask)
+                                              uint32_t* __restrict__ mask, unsigned long long* __restrict__ rect = nullptr)
 {
     const uint32_t tiles_x = (fr.w + 7u) >> 3, tiles_y = (fr.h + 7u) >> 3;
     const uint32_t n_words = (tiles_x * tiles_y + 31u) >> 5;
@@ -1426,7 +1432,8 @@ __device__ __forceinline__ void tile_mask_box(const float* __restrict__ boxes, u
         ymin = fminf(ymin, ny); ymax = fmaxf(ymax, ny);
     }
     if (behind || !(xmin <= xmax) || !(ymin <= ymax)) {      // NaN-safe
-        atomicOr(&mask[n_words], 1u);
+        if constexpr (kRects) *rect = kTileRectOff;
+        else atomicOr(&mask[n_words], 1u);
         return;
     }
     // pixel (gx, y) looks along ndc = (2 gx / gw - 1, 2 y / gh - 1): gx = (ndc.x + 1) / 2 * gw
@@ -1440,8 +1447,15 @@ __device__ __forceinline__ void tile_mask_box(const float* __restrict__ boxes, u
     float lx1 = (ceilf((floorf(gx1 / blk) - (float)fr.x_offset) / (float)fr.x_stride) + 1.0f) * blk - 1.0f;
     lx0 = fmaxf(lx0, 0.0f); gy0 = fmaxf(gy0, 0.0f);
     lx1 = fminf(lx1, (float)(fr.w - 1u)); gy1 = fminf(gy1, (float)(fr.h - 1u));
-    if (!(lx0 <= lx1) || !(gy0 <= gy1)) return;             // off screen
+    if (!(lx0 <= lx1) || !(gy0 <= gy1)) {                    // off screen
+        if constexpr (kRects) *rect = kTileRectNone;
+        return;
+    }
     const uint32_t tx0 = (uint32_t)lx0 >> 3, tx1 = (uint32_t)lx1 >> 3, ty0 = (uint32_t)gy0 >> 3, ty1 = (uint32_t)gy1 >> 3;
+    if constexpr (kRects) {
+        *rect = (unsigned long long)tx0 | ((unsigned long long)tx1 << 16) | ((unsigned long long)ty0 << 32) | ((unsigned long long)ty1 << 48);
+        return;
+    }
     for (uint32_t ty = ty0; ty <= ty1; ty++)
         for (uint32_t tx = tx0; tx <= tx1; tx++) {
             const uint32_t id = ty * tiles_x + tx;
@@ -1467,6 +1481,64 @@ __global__ __launch_bounds__(256) void k_tile_mask_dev(const float* __restrict__
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= *n_boxes) return;
     tile_mask_box(boxes, i, pv, fr, mask);
+}
+
+// ---- the same mask, built in parallel over its words (nrc_renderer_render_path: a mask per view, beside the previous view's frames).
+// k_tile_rects, one lane per box: tile_mask_box's packed rectangle, or one of its two sentinels.  k_tile_mask_words, one wave per mask
+// word: the workgroup stages the rectangles through LDS 1024 at a time (each is read from memory once per workgroup), a lane takes every 64th of them and ORs, per tile row of the word the rectangle covers, the span of
+// bits [row * tiles_x + tx0, row * tiles_x + tx1] clipped to the word; the lanes' words are OR-reduced across the wave and lane 0 stores the
+// result.  The wave behind the last bit word owns the trailing "off" word: 1 when any box is behind the eye plane.  Every word is written,
+// once, by a plain store: no atomics, and the buffer needs no clear.
+constexpr uint32_t kTileRectChunk = 1024u;
+
+// n = *n_dev when the count lives in device memory (a volume rebuilt on the device; the grid covers the capacity), else n_host
+__global__ __launch_bounds__(256) void k_tile_rects(const float* __restrict__ boxes, uint32_t n_host, const uint32_t* __restrict__ n_dev, DevProjView pv,
+                                                   DevFrame fr, unsigned long long* __restrict__ rects)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    const uint32_t n = n_dev != nullptr ? *n_dev : n_host;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    tile_mask_box<true>(boxes, i, pv, fr, nullptr, rects + i);
+}
+
+__global__ __launch_bounds__(256) void k_tile_mask_words(const unsigned long long* __restrict__ rects, uint32_t n_host, const uint32_t* __restrict__ n_dev,
+                                                        DevFrame fr, uint32_t* __restrict__ mask)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    __shared__ unsigned long long stage[kTileRectChunk];
+    const uint32_t tiles_x = (fr.w + 7u) >> 3, tiles_y = (fr.h + 7u) >> 3;
+    const uint32_t n_words = (tiles_x * tiles_y + 31u) >> 5;
+    const uint32_t n = n_dev != nullptr ? *n_dev : n_host;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t word = blockIdx.x * 4u + (threadIdx.x >> 6);      // wave-uniform; n_words: the off word; beyond: staging only
+    const uint32_t b0 = word << 5, b1 = b0 + 31u;                     // the word's tile ids
+    const uint32_t row_a = b0 / tiles_x, row_b = min(b1 / tiles_x, tiles_y - 1u);
+    uint32_t acc = 0u;
+    for (uint32_t base = 0; base < n; base += kTileRectChunk) {
+        const uint32_t m = min(kTileRectChunk, n - base);
+        for (uint32_t k = threadIdx.x; k < m; k += 256u) stage[k] = rects[base + k];
+        __syncthreads();
+        if (word < n_words) {
+            for (uint32_t k = lane; k < m; k += 64u) {
+                const unsigned long long r = stage[k];
+                const uint32_t tx0 = (uint32_t)r & 0xffffu, tx1 = (uint32_t)(r >> 16) & 0xffffu;
+                const uint32_t ty0 = (uint32_t)(r >> 32) & 0xffffu, ty1 = (uint32_t)(r >> 48);
+                const uint32_t r0 = max(ty0, row_a), r1 = min(ty1, row_b);
+                for (uint32_t row = r0; row <= r1; row++) {
+                    const uint32_t lo = max(row * tiles_x + tx0, b0), hi = min(row * tiles_x + tx1, b1);
+                    if (lo <= hi) acc |= (0xffffffffu >> (31u - (hi - lo))) << (lo - b0);
+                }
+            }
+        } else if (word == n_words) {
+            for (uint32_t k = lane; k < m; k += 64u) acc |= stage[k] == kTileRectOff ? 1u : 0u;
+        }
+        __syncthreads();
+    }
+    if (word > n_words) return;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc |= (uint32_t)__shfl_xor((int)acc, off);
+    if (lane == 0u) mask[word] = acc;
 }
 
 // ------------------------------------------------------------------------------------------------ nrc/clear.comp + ring ordering
@@ -2305,6 +2377,19 @@ void launch_tile_mask_dev(const float* boxes, const uint32_t* n_boxes, uint32_t 
     NRC_HIP(hipMemsetAsync(mask, 0, (size_t)tile_mask_words(fr.w, fr.h) * 4, s));
     if (capacity == 0) return;
     hipLaunchKernelGGL(k_tile_mask_dev, dim3(ceil_div(capacity, 256)), dim3(256), 0, s, boxes, n_boxes, pv, fr, mask);
+    NRC_HIP(hipGetLastError());
+}
+
+void launch_tile_mask_tiles(const float* boxes, uint32_t n_boxes, const uint32_t* n_boxes_dev, uint32_t capacity, const DevProjView& pv,
+                            const DevFrame& fr, void* rects, uint32_t* mask, hipStream_t s)
+{
+    const uint32_t grid_boxes = n_boxes_dev != nullptr ? capacity : n_boxes;      // (no box: k_tile_mask_words alone writes an all-clear mask)
+    if (grid_boxes > 0) {
+        hipLaunchKernelGGL(k_tile_rects, dim3(ceil_div(grid_boxes, 256)), dim3(256), 0, s, boxes, n_boxes, n_boxes_dev, pv, fr, (unsigned long long*)rects);
+        NRC_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_tile_mask_words, dim3(ceil_div(tile_mask_words(fr.w, fr.h), 4)), dim3(256), 0, s, (const unsigned long long*)rects,
+                       grid_boxes > 0 ? n_boxes : 0u, grid_boxes > 0 ? n_boxes_dev : nullptr, fr, mask);
     NRC_HIP(hipGetLastError());
 }
 

@@ -116,6 +116,11 @@ uint32_t tile_mask_words(uint32_t w, uint32_t h);
 // the same with the box count in device memory (*n_boxes <= capacity), as launch_volume_rebuild leaves it
 void launch_tile_mask_dev(const float* boxes, const uint32_t* n_boxes, uint32_t capacity, const DevProjView& pv, const DevFrame& fr, uint32_t* mask,
                          hipStream_t s);
+// the same words (the trailing "off" word included) from a build that runs in parallel over the mask instead of over the boxes, without
+// atomics and without a clear of `mask` (nrc_renderer_render_path: one mask per view).  The box count is n_boxes, or *n_boxes_dev
+// (<= capacity) when n_boxes_dev is not null; rects: 8 bytes per box (n_boxes, or capacity), scratch between the two launches.
+void launch_tile_mask_tiles(const float* boxes, uint32_t n_boxes, const uint32_t* n_boxes_dev, uint32_t capacity, const DevProjView& pv,
+                            const DevFrame& fr, void* rects, uint32_t* mask, hipStream_t s);
 
 // ---- device-side volume rebuild (nrc_renderer_set_volume): from a density volume in device memory (NRC_VOLUME_U8 / NRC_VOLUME_F32,
 // index i + nx*(j + ny*k)) the R8 density, the exact occupancy bits (DevScene::occ_bits) and the dilated 8^3-cell boxes of the tile mask,

@@ -204,6 +204,22 @@ public:
         if (tuning_done) *tuning_done = (tune_.state == Tuner::Done || all_pinned()) ? 1 : 0;
     }
 
+    // nrc_renderer_render_path, at every view: a trial window that contains a camera change is discarded.  The schedule goes back to the
+    // trial sequence's base, the knob's sequence starts again kWarm frames from now (so no trial runs inside a view shorter than that, and
+    // none is timed across two views), and nothing measured across a view change reaches the ScheduleCache.
+    void view_changed(uint64_t frame_index)
+    {
+        Tuner& t = tune_;
+        if (t.state == Tuner::Done) return;
+        if (t.state != Tuner::Warm) {
+            apply(t.trials[0]);
+            t.state = Tuner::Warm;
+            t.rounds = 0;
+            t.attempts = 0;
+        }
+        tune_start_ = frame_index;
+    }
+
     // once per frame, before the frame is enqueued (may change now(): the renderer chooses its scheduling knobs from its own frame timeline)
     template <class Host>
     void step(const TunerStep& s, Host& host)

@@ -57,6 +57,25 @@ def make_camera(pos=(64.0, 0.0, 0.0), view_dir=(-1.0, 0.0, 0.0), up=(0.0, 1.0, 0
                 pos=pos.astype(np.float32))
 
 
+def orbit_cameras(n, radius=64.0, height=0.0, aspect=1920.0 / 1080.0, center=(0.0, 0.0, 0.0), start_angle=0.0, **camera_kw):
+    """A turntable: n make_camera views on the circle of `radius` around `center` (the volume's centre: the box is centred on the origin)
+    in the plane y = center.y + height, every one looking at `center`.  View k stands at angle start_angle + 2 pi k / n from the x axis
+    towards z, so view 0 of the defaults is make_camera's default view.  camera_kw goes to make_camera (up, fovy, near, far).
+    What NrcHpmRenderer.RenderPath / McHpmRenderer.RenderPath take."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("orbit_cameras: n must be at least 1")
+    if not (radius > 0.0 or height != 0.0):
+        raise ValueError("orbit_cameras: the eye must not stand on the centre (radius > 0 or height != 0)")
+    c = np.asarray(center, np.float64)
+    cams = []
+    for k in range(n):
+        a = start_angle + 2.0 * math.pi * k / n
+        pos = c + np.array([radius * math.cos(a), height, radius * math.sin(a)], np.float64)
+        cams.append(make_camera(pos=pos, view_dir=c - pos, aspect=aspect, **camera_kw))
+    return cams
+
+
 def dir_light_dir(zenith=-1.57, azimuth=0.0):
     """VecFromAngles (src/DirLight.cpp:5-14): Ry(azimuth) * Rx(zenith) * (0,1,0)."""
     cz, sz = math.cos(zenith), math.sin(zenith)

@@ -1,0 +1,341 @@
+"""nrc_renderer_render_path / nrc_mc_renderer_render_path: a sequence of views enqueued by one call that does not wait for the GPU.
+The specification is an equivalence: the call computes, bit for bit, what SetCamera + Render per view compute -- images, framebuffer and,
+with training, the cache's loss, weights, optimizer state, step and ring.  The views' empty-space tile masks come from kernels that run in
+parallel over the mask (k_tile_rects + k_tile_mask_words); they equal k_tile_mask's words, the trailing "off" word included."""
+import ctypes as C
+import time
+
+import numpy as np
+import pytest
+
+from conftest import nrc_debug
+
+pytestmark = pytest.mark.gpu
+
+CFG = dict(train_batch_count=1, log2_train_batch_size=10, log2_infer_batch_size=14)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return a.shape == b.shape and bool((a.view(np.uint32) == b.view(np.uint32)).all())
+
+
+def views_of(sc, aspect):
+    """the one view set of this file, chosen to hit every branch of the mask: the default view and two orbit views (rectangles that cover
+    part of the screen), an eye inside the volume (a box corner behind the eye plane: the off word), and a far eye that looks past the
+    cloud (every box in front of the eye plane, every rectangle off screen: all clear).  The all-clear view follows mixed ones and the
+    off view is followed by others, so a word the build failed to rewrite would show."""
+    orbit = sc.orbit_cameras(5, radius=70.0, height=25.0, aspect=aspect)
+    return [sc.make_camera(aspect=aspect), orbit[1], sc.make_camera(pos=(10.0, 0.0, 0.0), aspect=aspect),
+            sc.make_camera(pos=(200.0, 0.0, 0.0), view_dir=(-1.0, 0.0, 2.5), aspect=aspect), orbit[3]]
+
+
+def _rolled(cloud16):
+    return np.ascontiguousarray(np.roll(cloud16, (30, 20, -50), axis=(0, 1, 2)))
+
+
+def _make(api, sc, kind, scene, W, H, cam, blend=False, tile=None, gw=None, **cfg_kw):
+    if kind == "mc":
+        return api.McHpmRenderer(W, H, 8, blend, cam, scene, tile=tile), None
+    kw = dict(CFG)
+    kw.update(cfg_kw)
+    cfg = api.AppConfig(**kw)
+    nrc = api.NeuralRadianceCache(cfg)
+    return api.NrcHpmRenderer(W, H, blend, cam, cfg, scene, nrc, tile=tile), nrc
+
+
+def _render(ren, kind, train=False):
+    if kind == "mc":
+        ren.Render()
+    else:
+        ren.Render(None, train)
+
+
+def _destroy(*pairs):
+    for ren, nrc in pairs:
+        ren.Destroy()
+        if nrc is not None:
+            nrc.Destroy()
+
+
+def _classify(mask, n_tiles):
+    """'off' / 'full' / 'clear' / 'mixed' of a TileMask() result"""
+    words, off = mask[:-1], int(mask[-1])
+    set_bits = int(sum(bin(int(w)).count("1") for w in words))
+    if off:
+        return "off"
+    return "full" if set_bits == n_tiles else "clear" if set_bits == 0 else "mixed"
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1. mask equality
+@pytest.mark.parametrize("kind,W,H,tile", [("nrc", 128, 80, None), ("nrc", 100, 52, None), ("nrc", 8, 6, None),
+                                           ("mc", 128, 80, None), ("mc", 100, 52, None), ("mc", 8, 6, None),
+                                           ("nrc", 128, 80, (1, 3, 128, 80, 8))],
+                         ids=["nrc-128x80", "nrc-ragged100x52", "nrc-tiny8x6", "mc-128x80", "mc-ragged100x52", "mc-tiny8x6", "nrc-sharded-1-of-3"])
+def test_tile_parallel_mask_equals_the_box_parallel_mask(api, sc, cloud16, torch_gpu, kind, W, H, tile):
+    """for every view, TileMask() after SetCamera + Render (k_tile_mask) == TileMask() after a one-view RenderPath (the tile-parallel
+    kernels), word for word; once more after a SetVolume from a device tensor (the box count then lives in device memory)"""
+    import torch
+    from nrc_hpm_renderer_amd import parallel
+    lw = parallel.local_width(tile[0], tile[1], W, tile[4]) if tile else W
+    views = views_of(sc, W / H)
+    scene = sc.make_scene(cloud16, scene_id=4)
+    old, new = _make(api, sc, kind, scene, lw, H, views[0], tile=tile), _make(api, sc, kind, scene, lw, H, views[0], tile=tile)
+    fr = sc.frame_randoms(1, seed=3)
+    n_tiles = ((lw + 7) // 8) * ((H + 7) // 8)
+    for medium in ("creation", "device rebuild"):
+        if medium == "device rebuild":
+            for ren, _ in (old, new):
+                ren.SetVolume(torch.from_numpy(_rolled(cloud16)).cuda())
+        kinds = []
+        for i, v in enumerate(views):
+            old[0].SetCamera(None, v)
+            old[0].SetFrameRandom(fr[0])
+            _render(old[0], kind)
+            want = old[0].TileMask()
+            new[0].RenderPath([v], 1, fr, out=False)
+            got = new[0].TileMask()
+            assert want.size == (n_tiles + 31) // 32 + 1, (medium, i, want.size)
+            assert np.array_equal(got, want), (medium, i, [hex(int(x)) for x in got[:4]], [hex(int(x)) for x in want[:4]])
+            kinds.append(_classify(want, n_tiles))
+        print(medium, kinds)
+        # otherwise the comparison shows nothing.  (A mask of one tile -- 8x6 -- is full, clear or off: it cannot be mixed.)
+        assert any(k in ("off", "full") for k in kinds), kinds
+        assert "clear" in kinds, kinds
+        assert n_tiles == 1 or "mixed" in kinds, kinds
+    _destroy(old, new)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2. path == loop, NRC
+def _nrc_state(ren, nrc):
+    return dict(image=ren.GetImage().cpu().numpy().copy(), loss=nrc.GetLoss(), step=nrc.GetStep(),
+                params=[nrc.GetParams(k).copy() for k in range(4)], ring=ren.Buffer("ring").cpu().numpy().copy())
+
+
+def _assert_same_state(a, b):
+    assert np.isfinite(a["image"]).all()
+    assert same_bits(a["image"], b["image"])
+    assert bits(np.float32(a["loss"])) == bits(np.float32(b["loss"])), (a["loss"], b["loss"])
+    assert a["step"] == b["step"]
+    for k in range(4):
+        assert np.array_equal(bits(a["params"][k]), bits(b["params"][k])), k
+    assert np.array_equal(a["ring"], b["ring"])
+
+
+@pytest.mark.parametrize("mode", ["pipelined", "single-stream", "q2-long-trace", "self-train"])
+def test_nrc_path_equals_the_set_camera_loop(api, sc, cloud16, torch_gpu, monkeypatch, mode):
+    """128x80, blending on, train=True, 5 views x 3 frames, pinned frame randoms: images, framebuffer, loss, step, master / EMA weights,
+    Adam moments and the ring equal those of a second renderer + cache driven by SetCamera / SetFrameRandom / Render"""
+    import torch
+    W, H, FPC = 128, 80, 3
+    views = views_of(sc, W / H)
+    frs = sc.frame_randoms(len(views) * FPC, seed=21)
+    extra = {"q2-long-trace": dict(compat_fix=2, train_ray_length=32, train_spp=1), "self-train": dict(self_train=1)}.get(mode, {})
+    if mode == "single-stream":
+        nrc_debug(monkeypatch, single_stream=True, poison_alloc=True)
+    scene = sc.make_scene(cloud16, scene_id=4)
+    start = sc.make_camera(pos=(0.0, 0.0, 80.0), view_dir=(0.0, 0.0, -1.0), aspect=W / H)      # (none of the views)
+    path, loop = (_make(api, sc, "nrc", scene, W, H, start, blend=True, **extra) for _ in range(2))
+    out = torch.full((len(views), H, W, 4), float("nan"), device="cuda")
+    got = path[0].RenderPath(views, FPC, frs, train=True, out=out)
+    assert got is out
+    want = []
+    for i, v in enumerate(views):
+        loop[0].SetCamera(None, v)
+        for k in range(FPC):
+            loop[0].SetFrameRandom(frs[i * FPC + k])
+            loop[0].Render(None, True)
+        want.append(loop[0].GetImage().cpu().numpy().copy())
+    imgs = out.cpu().numpy()
+    for i in range(len(views)):
+        assert same_bits(imgs[i], want[i]), i
+    assert not same_bits(imgs[0], imgs[1])
+    a, b = _nrc_state(*path), _nrc_state(*loop)
+    assert a["step"] == len(views) * FPC
+    _assert_same_state(a, b)
+    assert same_bits(a["image"], imgs[-1])
+    _destroy(path, loop)
+    nrc_debug(monkeypatch)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 3. path == loop, MC
+def test_mc_path_equals_the_loop_and_the_oracle(api, orc, sc, cloud16, torch_gpu):
+    """100x52, path length 8, 5 views x 2 frames, bitwise; view 0's image is also the oracle's MC frame of that view's last random numbers"""
+    W, H, FPC = 100, 52, 2
+    views = views_of(sc, W / H)
+    frs = sc.frame_randoms(len(views) * FPC, seed=22)
+    scene = sc.make_scene(cloud16, scene_id=4)
+    path, loop = (_make(api, sc, "mc", scene, W, H, views[2]) for _ in range(2))
+    imgs = path[0].RenderPath(views, FPC, frs).cpu().numpy()
+    for i, v in enumerate(views):
+        loop[0].SetCamera(None, v)
+        for k in range(FPC):
+            loop[0].SetFrameRandom(frs[i * FPC + k])
+            loop[0].Render()
+        assert same_bits(imgs[i], loop[0].GetImage().cpu().numpy()), i
+    assert same_bits(path[0].GetImage().cpu().numpy(), imgs[-1])
+    ref, _, _ = orc.mc_render(scene, views[0], W, H, 8, frs[FPC - 1], threads=8)
+    assert same_bits(imgs[0], ref)
+    _destroy(path, loop)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 4. empty skip on / off
+@pytest.mark.parametrize("kind", ["nrc", "mc"])
+def test_path_frames_do_not_depend_on_the_empty_skip(api, sc, cloud16, torch_gpu, kind):
+    W, H = 128, 80
+    views = views_of(sc, W / H)
+    frs = sc.frame_randoms(len(views), seed=23)
+    scene = sc.make_scene(cloud16, scene_id=4)
+    imgs = []
+    for skip in (True, False):
+        pair = _make(api, sc, kind, scene, W, H, views[0])
+        pair[0].SetEmptySkip(skip)
+        imgs.append(pair[0].RenderPath(views, 1, frs).cpu().numpy().copy())
+        assert (pair[0].TileMask().size > 0) == skip
+        _destroy(pair)
+    assert np.isfinite(imgs[0]).all()
+    assert same_bits(imgs[0], imgs[1])
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5. NULL randoms / NULL out
+@pytest.mark.parametrize("kind", ["nrc", "mc"])
+def test_path_without_randoms_and_without_images(api, sc, cloud16, torch_gpu, kind):
+    """frameRandoms=None draws the numbers consecutive Render calls would; out=None returns a new tensor and out=False copies nothing:
+    either way the last view stays in GetImage()"""
+    W, H, FPC = 128, 80, 2
+    views = views_of(sc, W / H)
+    scene = sc.make_scene(cloud16, scene_id=4)
+    path, bare, loop = (_make(api, sc, kind, scene, W, H, views[0], seed=42) for _ in range(3))
+    train = kind == "nrc"
+    imgs = path[0].RenderPath(views, FPC, None, train=train).cpu().numpy()
+    assert bare[0].RenderPath(views, FPC, None, train=train, out=False) is None
+    for i, v in enumerate(views):
+        loop[0].SetCamera(None, v)
+        for k in range(FPC):
+            _render(loop[0], kind, train)
+        assert same_bits(imgs[i], loop[0].GetImage().cpu().numpy()), i
+    assert same_bits(path[0].GetImage().cpu().numpy(), imgs[-1])
+    assert same_bits(bare[0].GetImage().cpu().numpy(), imgs[-1])
+    # the generator has advanced as the loop's has: the next unpinned frame is the same too
+    for pair in (path, loop):
+        _render(pair[0], kind, train)
+    assert same_bits(path[0].GetImage().cpu().numpy(), loop[0].GetImage().cpu().numpy())
+    _destroy(path, bare, loop)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 6. no host wait
+def test_render_path_does_not_wait_for_the_gpu(api, sc, torch_gpu):
+    """behind a backlog of 32 trained frames at 1080p, a 4-view RenderPath returns long before the backlog has run (SetCamera would wait
+    for all of it); its frames are those a second renderer on the same cache makes of the views afterwards"""
+    import torch
+    W, H = 1920, 1080
+    vol = sc.cached_volume("cloud", 128, seed=1337)
+    scene = sc.make_scene(vol, scene_id=4)
+    cfg = api.AppConfig()
+    views = sc.orbit_cameras(4, radius=64.0, height=10.0, aspect=W / H)
+    frs = sc.frame_randoms(4, seed=4)
+    nrc = api.NeuralRadianceCache(cfg)
+    ren = api.NrcHpmRenderer(W, H, False, views[0], cfg, scene, nrc)
+    other = api.NrcHpmRenderer(W, H, False, views[0], cfg, scene, nrc)
+    out = torch.empty((4, H, W, 4), device="cuda")
+    ren.RenderPath(views[:1], 1, frs[:1], out=False)      # (first call: the rectangle scratch is allocated, the capped states selected)
+    ren.RenderFrames(sc.frame_randoms(4, seed=1), train=True)
+    torch.cuda.synchronize()
+    s = torch.cuda.current_stream()
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record(s)
+    ren.RenderFrames(sc.frame_randoms(32, seed=2), train=True)
+    ren.GetImage()      # (the stream waits for the last compositing on the device)
+    end.record(s)
+    t0 = time.perf_counter()
+    ren.RenderPath(views, 1, frs, train=False, out=out)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    end.synchronize()
+    gpu_ms = start.elapsed_time(end)
+    print("RenderPath returned after %.3f ms; the backlog in front of it ran %.3f ms" % (host_ms, gpu_ms))
+    assert host_ms < 0.25 * gpu_ms, (host_ms, gpu_ms)
+    imgs = out.cpu().numpy()      # (on the renderer's stream: ordered behind the last copy)
+    assert np.isfinite(imgs).all()
+    for i, v in enumerate(views):
+        other.SetCamera(None, v)
+        other.SetFrameRandom(frs[i])
+        other.Render(None, False)
+        assert same_bits(imgs[i], other.GetImage().cpu().numpy()), i
+    ren.Destroy()
+    other.Destroy()
+    nrc.Destroy()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 7. mixing
+def test_paths_mix_with_frames_volume_swaps_and_set_camera(api, sc, cloud16, torch_gpu):
+    """Render, RenderPath, SetVolume, RenderPath, SetCamera + Render == the same sequence with every path written as its loop"""
+    import torch
+    W, H = 128, 80
+    views = views_of(sc, W / H)
+    frs = sc.frame_randoms(8, seed=24)
+    scene = sc.make_scene(cloud16, scene_id=4)
+    dB = torch.from_numpy(_rolled(cloud16)).cuda()
+    path, loop = (_make(api, sc, "nrc", scene, W, H, views[1], blend=True) for _ in range(2))
+
+    def as_loop(ren, vs, fpc, rnd):
+        for i, v in enumerate(vs):
+            ren.SetCamera(None, v)
+            for k in range(fpc):
+                ren.SetFrameRandom(rnd[i * fpc + k])
+                ren.Render(None, True)
+
+    for (ren, _), run_path in ((path, lambda ren, vs, fpc, rnd: ren.RenderPath(vs, fpc, rnd, train=True, out=False)), (loop, as_loop)):
+        ren.SetFrameRandom(frs[0])
+        ren.Render(None, True)
+        run_path(ren, views[0:2], 2, frs[1:5])
+        ren.SetVolume(dB)
+        run_path(ren, views[2:4], 1, frs[5:7])
+        ren.SetCamera(None, views[4])
+        ren.SetFrameRandom(frs[7])
+        ren.Render(None, True)
+    _assert_same_state(_nrc_state(*path), _nrc_state(*loop))
+    _destroy(path, loop)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 8. errors
+def test_path_errors_leave_the_renderers_unchanged(api, sc, cloud16, torch_gpu):
+    import torch
+    W, H = 96, 54
+    views = views_of(sc, W / H)
+    scene = sc.make_scene(cloud16, scene_id=4)
+    frs = sc.frame_randoms(2, seed=25)
+    L = api.load_library()
+    INVALID = -1      # NRC_ERR_INVALID
+    for kind in ("nrc", "mc"):
+        used, untouched = (_make(api, sc, kind, scene, W, H, views[0], blend=True) for _ in range(2))
+        for ren, _ in (used, untouched):
+            ren.SetFrameRandom(frs[0])
+            _render(ren, kind)
+        ren = used[0]
+        cams = (api.NrcCamera * 2)(api.make_c_camera(views[1]), api.make_c_camera(views[2]))
+        if kind == "nrc":
+            call = lambda n, c, fpc: L.nrc_renderer_render_path(ren.h, n, c, fpc, None, 0, None)      # noqa: E731
+        else:
+            call = lambda n, c, fpc: L.nrc_mc_renderer_render_path(ren.h, n, c, fpc, None, None)      # noqa: E731
+        assert call(2, None, 1) == INVALID
+        assert b"SkyRenderer ERROR" in L.nrc_last_error()
+        assert call(2, C.cast(cams, C.c_void_p), 0) == INVALID
+        assert b"SkyRenderer ERROR" in L.nrc_last_error()
+        assert call(0, None, 0) == 0      # no view: a no-op
+        with pytest.raises(RuntimeError, match="SkyRenderer ERROR"):
+            ren.RenderPath(views[1:3], 0)
+        for wrong in (torch.empty((2, H, W + 1, 4), device="cuda"), torch.empty((1, H, W, 4), device="cuda"),
+                      torch.empty((2, H, W, 4), device="cuda", dtype=torch.float64), torch.empty((2, H, W, 4))):
+            with pytest.raises(ValueError):
+                ren.RenderPath(views[1:3], 1, out=wrong)
+        with pytest.raises(ValueError):
+            ren.RenderPath(views[1:3], 1, frameRandoms=frs[:1])
+        for r, _ in (used, untouched):      # still the first view, blending not restarted
+            r.SetFrameRandom(frs[1])
+            _render(r, kind)
+        assert same_bits(used[0].GetImage().cpu().numpy(), untouched[0].GetImage().cpu().numpy())
+        _destroy(used, untouched)
