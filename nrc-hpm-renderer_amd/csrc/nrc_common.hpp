@@ -47,7 +47,7 @@ inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 //   zero_dead_queries   gen_rays writes the zero queries of pixels that did not scatter (the reference's zero-filled buffer)
 //   fused_composite     compositing as the epilogue of the inference launch (6 x 64 model; measured slower in the frame)
 //   dense_grid_exchange the HashGrid table gradient through the dense all-reduce instead of the all-gathered lists
-//   no_fused_opt        three optimizer launches (k_adam_ema / k_sgd_ema, k_pack, k_pack_grid) instead of the fused one
+//   no_fused_opt        three optimizer launches (k_adam_ema / k_sgd_ema, k_pack, k_pack_grid) instead of the fused ones (k_opt_pack, k_grid_opt2)
 //   grid_no_bins        every pair of the table gradient through the fixed-point shadow (no per-bin lists)
 //   wgrad_old=0|1       round 3's k_wgrad (1) or k_wgrad2 (0) whatever the width;   train_gen_old=0|1, train_gen_nt=N: likewise k_train_gen
 //   wave_priority_raise=0|1   nrc_set_wave_priority_raise for hosts that cannot call it (tests/cpp/stress_main)

@@ -2263,91 +2263,90 @@ __global__ __launch_bounds__(256) void k_guard_scan(const float* __restrict__ gr
 struct AdamArgs {
     float lr_t, inv_loss_scale, ema_old, ema_new, ema_div;
 };
-// (no contraction in the two update rules: k_adam_ema / k_sgd_ema and the one-launch k_opt_pack then round identically, and like the
-// CPU oracle, which is built with -ffp-contract=off)
+// (no contraction in the update rules: k_adam_ema / k_sgd_ema, the one-launch k_opt_pack and the table's k_grid_opt2 then round identically,
+// and like the CPU oracle, which is built with -ffp-contract=off)
 #pragma clang fp contract(off)
+// Each rule once, on values; the kernels differ in how they load and store around them.
+__device__ __forceinline__ float ema_value(float e_old, float wi, const AdamArgs& a) { return (e_old * a.ema_old + wi * a.ema_new) / a.ema_div; }
+// matrix: the l2 term; a table parameter adds 0.0f in its place, and one whose gradient is zero does not get here at all (the callers)
+__device__ __forceinline__ void adam_value(float& wi, float& mi, float& vi, float graw, bool matrix, const AdamArgs& a)
+{
+    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f, l2 = 1e-8f;
+    const float g = graw * a.inv_loss_scale + (matrix ? l2 * wi : 0.0f);
+    const float m_new = b1 * mi + (1.0f - b1) * g;
+    const float v_new = b2 * vi + (1.0f - b2) * (g * g);
+    mi = m_new;
+    vi = v_new;
+    wi = wi - a.lr_t * m_new / (sqrtf(v_new) + eps);
+}
+// tiny-cuda-nn sgd.h nested in the EMA wrapper: w -= lr * (g / loss_scale + l2 * w), l2_reg 1e-8, every parameter
+__device__ __forceinline__ void sgd_value(float& wi, float graw, float lr, const AdamArgs& a)
+{
+    const float l2 = 1e-8f;
+    const float g = graw * a.inv_loss_scale + l2 * wi;
+    wi = wi - lr * g;
+}
+// the rules on parameter i of the fp32 vectors
 __device__ __forceinline__ void adam_ema_update(uint32_t i, float* __restrict__ w, float* __restrict__ ema, float* __restrict__ m,
                                                 float* __restrict__ v, float graw, bool matrix, const AdamArgs& a, float* w_new,
                                                 float* ema_new)
 {
-    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f, l2 = 1e-8f;
     float wi = w[i];
     if (!matrix && graw == 0.0f) {      // tiny-cuda-nn: grid entries with a zero gradient keep weight and moments
-        const float e = (ema[i] * a.ema_old + wi * a.ema_new) / a.ema_div;
+        const float e = ema_value(ema[i], wi, a);
         ema[i] = e;
         *w_new = wi; *ema_new = e;
         return;
     }
-    float g = graw * a.inv_loss_scale + (matrix ? l2 * wi : 0.0f);
-    float mi = b1 * m[i] + (1.0f - b1) * g;
-    float vi = b2 * v[i] + (1.0f - b2) * (g * g);
-    m[i] = mi;
-    v[i] = vi;
-    wi = wi - a.lr_t * mi / (sqrtf(vi) + eps);
+    adam_value(wi, m[i], v[i], graw, matrix, a);      // (the moments in place)
     w[i] = wi;
-    const float e = (ema[i] * a.ema_old + wi * a.ema_new) / a.ema_div;
+    const float e = ema_value(ema[i], wi, a);
     ema[i] = e;
     *w_new = wi; *ema_new = e;
 }
-// tiny-cuda-nn sgd.h nested in the EMA wrapper: w -= lr * (g / loss_scale + l2 * w), l2_reg 1e-8, every parameter
 __device__ __forceinline__ void sgd_ema_update(uint32_t i, float* __restrict__ w, float* __restrict__ ema, float graw, float lr,
                                                const AdamArgs& a, float* w_new, float* ema_new)
 {
-    const float l2 = 1e-8f;
     float wi = w[i];
-    const float g = graw * a.inv_loss_scale + l2 * wi;
-    wi = wi - lr * g;
+    sgd_value(wi, graw, lr, a);
     w[i] = wi;
-    const float e = (ema[i] * a.ema_old + wi * a.ema_new) / a.ema_div;
+    const float e = ema_value(ema[i], wi, a);
     ema[i] = e;
     *w_new = wi; *ema_new = e;
 }
 #pragma clang fp contract(fast)
 
+// The step of NRC_DEBUG=no_fused_opt, every parameter, in front of repack().  Guard... (nothing, or one GuardArgs: the non-finite guard of
+// nrc_mlp.hpp): a bad step leaves every vector as it is and is counted by thread 0; repack() then writes the next inference set from the
+// unchanged weights.
+template <class... Guard>
 __global__ void k_adam_ema(float* __restrict__ w, float* __restrict__ ema, float* __restrict__ m,
-                           float* __restrict__ v, const float* __restrict__ grad, uint32_t n, uint32_t n_matrix, AdamArgs a)
+                           float* __restrict__ v, const float* __restrict__ grad, uint32_t n, uint32_t n_matrix, AdamArgs a, Guard... ga)
 {
     NRC_RAISE_WAVE_PRIORITY(1);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    float wn, en;
-    adam_ema_update(i, w, ema, m, v, grad[i], i < n_matrix, a, &wn, &en);
-}
-
-__global__ void k_sgd_ema(float* __restrict__ w, float* __restrict__ ema, const float* __restrict__ grad, uint32_t n, float lr,
-                          AdamArgs a)
-{
-    NRC_RAISE_WAVE_PRIORITY(1);
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float wn, en;
-    sgd_ema_update(i, w, ema, grad[i], lr, a, &wn, &en);
-}
-
-// The same two with the non-finite guard: a bad step (nrc_mlp.hpp, GuardArgs) leaves every vector as it is and is counted by thread 0;
-// repack() behind them then writes the next inference set from the unchanged weights.
-__global__ void k_adam_ema_guarded(float* __restrict__ w, float* __restrict__ ema, float* __restrict__ m, float* __restrict__ v,
-                                   const float* __restrict__ grad, uint32_t n, uint32_t n_matrix, AdamArgs a, GuardArgs ga)
-{
-    NRC_RAISE_WAVE_PRIORITY(1);
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (guard_bad(ga)) {
-        if (i == 0) guard_count(ga);
-        return;
+    if constexpr (sizeof...(Guard) != 0) {
+        if (guard_bad(ga...)) {
+            if (i == 0) guard_count(ga...);
+            return;
+        }
     }
     float wn, en;
     adam_ema_update(i, w, ema, m, v, grad[i], i < n_matrix, a, &wn, &en);
 }
-__global__ void k_sgd_ema_guarded(float* __restrict__ w, float* __restrict__ ema, const float* __restrict__ grad, uint32_t n, float lr,
-                                  AdamArgs a, GuardArgs ga)
+template <class... Guard>
+__global__ void k_sgd_ema(float* __restrict__ w, float* __restrict__ ema, const float* __restrict__ grad, uint32_t n, float lr,
+                          AdamArgs a, Guard... ga)
 {
     NRC_RAISE_WAVE_PRIORITY(1);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    if (guard_bad(ga)) {
-        if (i == 0) guard_count(ga);
-        return;
+    if constexpr (sizeof...(Guard) != 0) {
+        if (guard_bad(ga...)) {
+            if (i == 0) guard_count(ga...);
+            return;
+        }
     }
     float wn, en;
     sgd_ema_update(i, w, ema, grad[i], lr, a, &wn, &en);
@@ -2392,79 +2391,22 @@ __global__ __launch_bounds__(256) void k_opt_pack(float* __restrict__ w, float* 
     if (db >= 0) d.pk_bwd[db] = (half_t)wn;
 }
 
-// The trainable table's share of the step, one thread per entry (two features): the gradient straight from the packed fp16 table
-// the atomics accumulated into (FROM16; no fp32 widening pass) or from the fp32 vector (after an exchange / a caller's hook), the
-// update of k_adam_ema / k_sgd_ema for parameters n_matrix + 2e, + 1, and the two fp16 gather copies (training weights, EMA set
+// The trainable table's share of the step, TWO entries (four parameters) per thread with 16-byte accesses: the gradient straight from the
+// packed fp16 table the atomics accumulated into (FROM16; no fp32 widening pass) or from the fp32 vector (after an exchange / a caller's
+// hook), the update of k_adam_ema / k_sgd_ema for parameters n_matrix + 4p .. + 3, and the two fp16 gather copies (training weights, EMA set
 // `next`) that k_pack_grid would write.  Replaces k_grid_grad_f32 + the table part of k_adam_ema + k_pack_grid.
-// Guard... (nothing, or one GuardArgs; k_opt_pack in front of it has counted the step): a bad step still clears the fp16 gradient entries
-// it reads -- the next backward pass expects a clean table -- and writes both gather copies from the entry as it is.
-template <bool SGD, bool FROM16, class... Guard>
-__global__ __launch_bounds__(256) void k_grid_opt(float* __restrict__ w, float* __restrict__ ema, float* __restrict__ m,
-                                                 float* __restrict__ v, const float* __restrict__ grad,
-                                                 uint32_t* __restrict__ grad16, uint32_t n_matrix, uint32_t n_entries, float lr,
-                                                 AdamArgs a, uint32_t* __restrict__ t_train, uint32_t* __restrict__ t_ema, Guard... ga)
-{
-    NRC_RAISE_WAVE_PRIORITY(1);
-    const uint32_t e = blockIdx.x * 256u + threadIdx.x;
-    if (e >= n_entries) return;
-    const uint32_t i0 = n_matrix + 2u * e;
-    float g0, g1;
-    if (FROM16) {
-        const uint32_t word = grad16[e];
-        const half2v h = __builtin_bit_cast(half2v, word);
-        g0 = (float)h[0]; g1 = (float)h[1];
-        // the table the atomics of the next step accumulate into is cleared here, entry by touched entry, instead of by a 28 MB memset in
-        // front of every backward pass (the runtime's fill kernel runs at wave priority 0 beside this library's kernels at 3: ~170 us in
-        // the frame for 7 us of work)
-        if (word != 0u) grad16[e] = 0u;
-    } else {
-        g0 = grad[i0]; g1 = grad[i0 + 1u];
-    }
-    float2v wn, en;
-    if constexpr (sizeof...(Guard) != 0) {
-        if (guard_bad(ga...)) {
-            wn[0] = w[i0]; wn[1] = w[i0 + 1u];
-            en[0] = ema[i0]; en[1] = ema[i0 + 1u];
-            t_train[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(wn, half2v));
-            t_ema[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(en, half2v));
-            return;
-        }
-    }
-    float x, y;
-    if (SGD) sgd_ema_update(i0, w, ema, g0, lr, a, &x, &y);
-    else adam_ema_update(i0, w, ema, m, v, g0, false, a, &x, &y);
-    wn[0] = x; en[0] = y;
-    if (SGD) sgd_ema_update(i0 + 1u, w, ema, g1, lr, a, &x, &y);
-    else adam_ema_update(i0 + 1u, w, ema, m, v, g1, false, a, &x, &y);
-    wn[1] = x; en[1] = y;
-    t_train[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(wn, half2v));
-    t_ema[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(en, half2v));
-}
-
-// Round 4: the same step with TWO entries (four parameters) per thread and 16-byte accesses.  k_grid_opt's one entry per thread reads and
-// writes its two parameters as separate 4-byte accesses at an 8-byte stride and moves 36 B per entry at 2.3 TB/s (110 us for the 7 M
-// entries of the reference-default table -- the longest kernel of the training step).  Here a thread whose four gradients are all zero --
-// three entries in four at 16 384 train rays -- loads w and ema (float4), stores ema and the EMA gather copy, and leaves the weight
-// copies alone: w does not change, so the training gather copy already holds fp16(w) (every writer of w also writes the copy: this
-// kernel, k_pack_grid after set_params / construction).  The others run the per-parameter update of adam_ema_update / sgd_ema_update
-// (same expressions, same rounding: the functions below restate them on values; fp contraction is off here too).
+// A thread whose four gradients are all zero -- three entries in four at 16 384 train rays -- loads w and ema (float4), stores ema and the
+// EMA gather copy, and leaves the weight copies alone: w does not change, so the training gather copy already holds fp16(w) (every writer
+// of w also writes the copy: this kernel, k_pack_grid after set_params / construction).  The others run adam_value / sgd_value parameter by
+// parameter.  (One entry per thread, two 4-byte accesses at an 8-byte stride, moved 36 B per entry at 2.3 TB/s: 110 us for the 7 M entries
+// of the reference-default table, the longest kernel of the training step.)
+// FROM16 clears the fp16 gradient entries it reads: the table the atomics of the next step accumulate into is cleared here, entry by touched
+// entry, instead of by a 28 MB memset in front of every backward pass (the runtime's fill kernel runs at wave priority 0 beside this
+// library's kernels at 3: ~170 us in the frame for 7 us of work).
+// Guard... (nothing, or one GuardArgs; k_opt_pack in front of it has counted the step): a bad step still clears the fp16 gradient entries it
+// reads -- the next backward pass expects a clean table -- and writes the EMA gather copy from the entry as it is; the training gather copy
+// already holds fp16(w).
 #pragma clang fp contract(off)
-__device__ __forceinline__ float ema_value(float e_old, float wi, const AdamArgs& a) { return (e_old * a.ema_old + wi * a.ema_new) / a.ema_div; }
-__device__ __forceinline__ void adam_value(float& wi, float& mi, float& vi, float graw, const AdamArgs& a)      // non-matrix parameter, graw != 0
-{
-    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-    const float g = graw * a.inv_loss_scale + 0.0f;
-    mi = b1 * mi + (1.0f - b1) * g;
-    vi = b2 * vi + (1.0f - b2) * (g * g);
-    wi = wi - a.lr_t * mi / (sqrtf(vi) + eps);
-}
-__device__ __forceinline__ void sgd_value(float& wi, float graw, float lr, const AdamArgs& a)
-{
-    const float l2 = 1e-8f;
-    const float g = graw * a.inv_loss_scale + l2 * wi;
-    wi = wi - lr * g;
-}
-// Guard... (nothing, or one GuardArgs): as in k_grid_opt; the training gather copy already holds fp16(w), so a bad step writes the EMA copy alone.
 template <bool SGD, bool FROM16, class... Guard>
 __global__ __launch_bounds__(256) void k_grid_opt2(float* __restrict__ w, float* __restrict__ ema, float* __restrict__ m,
                                                   float* __restrict__ v, const float* __restrict__ grad,
@@ -2474,13 +2416,13 @@ __global__ __launch_bounds__(256) void k_grid_opt2(float* __restrict__ w, float*
     NRC_RAISE_WAVE_PRIORITY(1);
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p >= n_pairs) return;
-    const uint32_t e = 2u * p, i0 = n_matrix + 4u * p;      // (n_matrix % 4 == 0 and an even number of entries: checked by the caller)
+    const uint32_t e = 2u * p, i0 = n_matrix + 4u * p;      // (n_matrix % 4 == 0 and an even number of entries: Mlp's constructor)
     float g[4];
     if (FROM16) {
         const uint2 word = *reinterpret_cast<const uint2*>(grad16 + e);
         const half2v h0 = __builtin_bit_cast(half2v, word.x), h1 = __builtin_bit_cast(half2v, word.y);
         g[0] = (float)h0[0]; g[1] = (float)h0[1]; g[2] = (float)h1[0]; g[3] = (float)h1[1];
-        if ((word.x | word.y) != 0u) *reinterpret_cast<uint2*>(grad16 + e) = make_uint2(0u, 0u);      // (see k_grid_opt: the table is left clean)
+        if ((word.x | word.y) != 0u) *reinterpret_cast<uint2*>(grad16 + e) = make_uint2(0u, 0u);      // (the table is left clean)
     } else {
         const float4 gv = *reinterpret_cast<const float4*>(grad + i0);
         g[0] = gv.x; g[1] = gv.y; g[2] = gv.z; g[3] = gv.w;
@@ -2506,7 +2448,7 @@ __global__ __launch_bounds__(256) void k_grid_opt2(float* __restrict__ w, float*
             float mi[4] = {mv.x, mv.y, mv.z, mv.w}, vi[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
             for (int k = 0; k < 4; k++)
-                if (g[k] != 0.0f) adam_value(wi[k], mi[k], vi[k], g[k], a);      // a zero gradient keeps weight and moments, parameter by parameter
+                if (g[k] != 0.0f) adam_value(wi[k], mi[k], vi[k], g[k], false, a);      // a zero gradient keeps weight and moments, parameter by parameter
             *reinterpret_cast<float4*>(m + i0) = make_float4(mi[0], mi[1], mi[2], mi[3]);
             *reinterpret_cast<float4*>(v + i0) = make_float4(vi[0], vi[1], vi[2], vi[3]);
         }
@@ -2608,6 +2550,9 @@ Mlp::Mlp(const nrc_config& cfg) : cfg_(cfg)
         n_grid = o * 2u;
     }
     n_params_ = n_mlp_ + n_grid;
+    // k_grid_opt2 updates four parameters (two entries) per 16-byte access.  Neither can fail: every matrix has a multiple of 16 rows or
+    // columns (widths 16..128, enc_dims_ padded to 16), every level a multiple of 8 or 2^k >= 16 entries.
+    if (n_mlp_ % 4u != 0u || n_grid_entries_ % 2u != 0u) fail("the table optimizer needs n_mlp % 4 == 0 and an even number of table entries");
 
     // tiny-cuda-nn v1.6's initialisation (src/NeuralRadianceCache.cu:39 -> tcnn::create_from_config -> Trainer::initialize_params;
     // recalled from upstream, the submodule is absent -- DESIGN.md section 2): pcg32{seed} on stream 1; the network's matrices first
@@ -3251,7 +3196,7 @@ void Mlp::backward(const float* d_in, const float* d_target, uint32_t n, uint32_
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(THREADS), lds, s, a, (const uint4*)d_pk_fwd_, (const uint4*)d_pk_bwd_);
     } else {
         if (features_ready == nullptr) launch_features(d_in, n, false, 1, s, false);
-        if (hash_ && !grad16_clean_) NRC_HIP(hipMemsetAsync(d_grad16_, 0, (size_t)n_grid_entries_ * 4, s));      // (k_grid_opt leaves it clean)
+        if (hash_ && !grad16_clean_) NRC_HIP(hipMemsetAsync(d_grad16_, 0, (size_t)n_grid_entries_ * 4, s));      // (k_grid_opt2 leaves it clean)
         grad16_clean_ = false;
         TrainArgsGen a;
         a.feat = features_ready != nullptr ? (const half_t*)features_ready : (const half_t*)d_feat_[1];
@@ -3361,7 +3306,7 @@ void Mlp::backward(const float* d_in, const float* d_target, uint32_t n, uint32_
                                    (const uint4*)d_grid_bin_entry0_, grid_bins_total_, (uint32_t*)d_grid_counters_, (const uint2*)d_grid_lists_, (long long*)d_grid_fix_, loose);
             }
             // the fp32 copy in the gradient vector is for whoever reads the vector (exchange, hook, debug read-back): the
-            // optimizer takes the table gradient from grad16 itself (k_grid_opt)
+            // optimizer takes the table gradient from grad16 itself (k_grid_opt2)
             grid16_valid_ = fused_opt_;
             if (widen_grid_grad || !fused_opt_)
                 hipLaunchKernelGGL(k_grid_grad_f32, dim3(ceil_div(n_grid_entries_, 256)), dim3(256), 0, s, (const uint32_t*)d_grad16_,
@@ -3380,12 +3325,12 @@ void Mlp::backward(const float* d_in, const float* d_target, uint32_t n, uint32_
                            (const half_t*)d_deltas_, (const half_t*)d_acts_, n, chunk, depth_ * kw_ + 8, enc_dims_ + depth_ * kw_,
                            (const WgradTask*)d_tasks_, n_wgrad_tasks_, d_slabs_, n_mlp_);
     NRC_HIP(hipGetLastError());
-    if (guard_on_)
-        hipLaunchKernelGGL(k_reduce_grads<GuardArgs>, dim3(ceil_div(n_mlp_, 64)), dim3(256), 0, s, d_slabs_, n_chunks, n_mlp_,
-                           d_grad_, d_loss_part_, n_tiles, d_loss_, guard_scan_args());
-    else
-        hipLaunchKernelGGL(k_reduce_grads<>, dim3(ceil_div(n_mlp_, 64)), dim3(256), 0, s, d_slabs_, n_chunks, n_mlp_,
-                           d_grad_, d_loss_part_, n_tiles, d_loss_);
+    auto reduce = [&](auto... ga) {      // (nothing, or the scan's GuardArgs)
+        hipLaunchKernelGGL(k_reduce_grads<decltype(ga)...>, dim3(ceil_div(n_mlp_, 64)), dim3(256), 0, s, d_slabs_, n_chunks, n_mlp_,
+                           d_grad_, d_loss_part_, n_tiles, d_loss_, ga...);
+    };
+    if (guard_on_) reduce(guard_scan_args());
+    else reduce();
     NRC_HIP(hipGetLastError());
 }
 
@@ -3460,132 +3405,65 @@ static AdamArgs adam_args_of(const nrc_config& cfg, uint32_t step)
     return a;
 }
 
+// a run-time flag as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+static void with_flag(bool on, F&& f)
+{
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// With the non-finite guard on: the same launches in the same order, each instantiated with the GuardArgs pack, behind the verdict of the
+// gradient they read (k_guard_scan here, unless the pass that wrote the gradient has scanned it).
 bool Mlp::optimizer_step(hipStream_t s, uint32_t loss_seq, unsigned long long* loss_cell)
 {
     step += 1;
-    if (guard_on_) return optimizer_step_guarded(s, loss_seq, loss_cell);
     const AdamArgs a = adam_args_of(cfg_, step);
-    if (fused_opt_) {
+    if (guard_on_) {
+        if (!guard_scanned_) {
+            hipLaunchKernelGGL(k_guard_scan, dim3(ceil_div(n_mlp_, 256)), dim3(256), 0, s, (const float*)d_grad_, n_mlp_, (const float*)d_loss_,
+                               guard_scan_args());
+            NRC_HIP(hipGetLastError());
+        }
+        guard_scanned_ = false;      // (the verdict is this step's alone)
+    }
+    const float lr = cfg_.learning_rate;
+    const dim3 b(256);
+    // ga: nothing, or this step's GuardArgs
+    auto enqueue = [&](auto... ga) {
+        if (!fused_opt_) {
+            if (sgd_) hipLaunchKernelGGL(k_sgd_ema<decltype(ga)...>, dim3(ceil_div(n_params_, 256)), b, 0, s, d_w_, d_ema_, d_grad_, n_params_, lr, a, ga...);
+            else hipLaunchKernelGGL(k_adam_ema<decltype(ga)...>, dim3(ceil_div(n_params_, 256)), b, 0, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_params_, n_mlp_, a, ga...);
+            NRC_HIP(hipGetLastError());
+            repack(s);
+            return false;
+        }
         const int next = infer_set_ ^ 1;
         const PackDst d{d_dst_, d_dst_ + n_mlp_, d_dst_ + 2 * (size_t)n_mlp_, (half_t*)d_pk_fwd_, (half_t*)d_pk_infer_[next], (half_t*)d_pk_bwd_};
-        // (the step's last launch takes the armed event along -- launch_last, nrc_common.hpp: k_opt_pack, or the table's optimizer behind it)
-        if (hash_) {
-            if (sgd_)
-                hipLaunchKernelGGL(k_opt_pack<true>, dim3(ceil_div(n_mlp_, 256)), dim3(256), 0, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_,
-                                   cfg_.learning_rate, a, d, (const float*)d_loss_, loss_seq, loss_cell);
-            else
-                hipLaunchKernelGGL(k_opt_pack<false>, dim3(ceil_div(n_mlp_, 256)), dim3(256), 0, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_,
-                                   cfg_.learning_rate, a, d, (const float*)d_loss_, loss_seq, loss_cell);
-        } else if (sgd_)
-            launch_last(k_opt_pack<true>, dim3(ceil_div(n_mlp_, 256)), dim3(256), 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_,
-                        cfg_.learning_rate, a, d, (const float*)d_loss_, loss_seq, loss_cell);
-        else
-            launch_last(k_opt_pack<false>, dim3(ceil_div(n_mlp_, 256)), dim3(256), 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_,
-                        cfg_.learning_rate, a, d, (const float*)d_loss_, loss_seq, loss_cell);
-        if (hash_) {
-            const dim3 g(ceil_div(n_grid_entries_, 256));
-            uint32_t *tt = (uint32_t*)d_t16_train_, *te = (uint32_t*)d_t16_ema_[next];
-            uint32_t* g16 = (uint32_t*)d_grad16_;
-            if (grid16_valid_) grad16_clean_ = true;      // k_grid_opt<., true> clears the entries it reads
-            if (n_mlp_ % 4u == 0u && n_grid_entries_ % 2u == 0u) {      // (two entries per thread, 16-byte accesses; else round 3's kernel)
-                const uint32_t np = n_grid_entries_ / 2u;
-                const dim3 g2(ceil_div(np, 256));
-                if (sgd_ && grid16_valid_)
-                    launch_last(k_grid_opt2<true, true>, g2, dim3(256), 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, np, cfg_.learning_rate, a, tt, te);
-                else if (sgd_)
-                    launch_last(k_grid_opt2<true, false>, g2, dim3(256), 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, np, cfg_.learning_rate, a, tt, te);
-                else if (grid16_valid_)
-                    launch_last(k_grid_opt2<false, true>, g2, dim3(256), 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, np, cfg_.learning_rate, a, tt, te);
-                else
-                    launch_last(k_grid_opt2<false, false>, g2, dim3(256), 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, np, cfg_.learning_rate, a, tt, te);
-            } else
-            if (sgd_ && grid16_valid_)
-                launch_last(k_grid_opt<true, true>, g, dim3(256), 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, n_grid_entries_, cfg_.learning_rate, a, tt, te);
-            else if (sgd_)
-                launch_last(k_grid_opt<true, false>, g, dim3(256), 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, n_grid_entries_, cfg_.learning_rate, a, tt, te);
-            else if (grid16_valid_)
-                launch_last(k_grid_opt<false, true>, g, dim3(256), 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, n_grid_entries_, cfg_.learning_rate, a, tt, te);
-            else
-                launch_last(k_grid_opt<false, false>, g, dim3(256), 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, n_grid_entries_, cfg_.learning_rate, a, tt, te);
-        }
+        const float* loss = d_loss_;
+        with_flag(sgd_, [&](auto sgd) {
+            constexpr bool SGD = decltype(sgd)::value;
+            // (the step's last launch takes the armed event along -- launch_last, nrc_common.hpp: k_opt_pack, or the table's optimizer behind it)
+            const auto pack = k_opt_pack<SGD, decltype(ga)...>;
+            auto launch = [&](auto... args) {
+                if (hash_) hipLaunchKernelGGL(pack, dim3(ceil_div(n_mlp_, 256)), b, 0, s, args...);
+                else launch_last(pack, dim3(ceil_div(n_mlp_, 256)), b, 0u, s, args...);
+            };
+            launch(d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_, lr, a, d, loss, loss_seq, loss_cell, ga...);
+            if (!hash_) return;
+            uint32_t *tt = (uint32_t*)d_t16_train_, *te = (uint32_t*)d_t16_ema_[next], *g16 = (uint32_t*)d_grad16_;
+            const uint32_t np = n_grid_entries_ / 2u;
+            if (grid16_valid_) grad16_clean_ = true;      // k_grid_opt2<., true> clears the entries it reads, on a bad step too
+            with_flag(grid16_valid_, [&](auto from16) {
+                launch_last(k_grid_opt2<SGD, decltype(from16)::value, decltype(ga)...>, dim3(ceil_div(np, 256)), b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_,
+                            g16, n_mlp_, np, lr, a, tt, te, ga...);
+            });
+        });
         NRC_HIP(hipGetLastError());
         infer_set_ = next;
         return loss_cell != nullptr;
-    }
-    if (sgd_)
-        hipLaunchKernelGGL(k_sgd_ema, dim3(ceil_div(n_params_, 256)), dim3(256), 0, s, d_w_, d_ema_, d_grad_, n_params_,
-                           cfg_.learning_rate, a);
-    else
-        hipLaunchKernelGGL(k_adam_ema, dim3(ceil_div(n_params_, 256)), dim3(256), 0, s, d_w_, d_ema_, d_m_, d_v_, d_grad_,
-                           n_params_, n_mlp_, a);
-    NRC_HIP(hipGetLastError());
-    repack(s);
-    return false;
-}
-
-// optimizer_step() with the non-finite guard on: the same launches in the same order, each in its guarded variant, behind the verdict
-// of the gradient they read (k_guard_scan here, unless the pass that wrote the gradient has scanned it)
-bool Mlp::optimizer_step_guarded(hipStream_t s, uint32_t loss_seq, unsigned long long* loss_cell)
-{
-    const AdamArgs a = adam_args_of(cfg_, step);
-    if (!guard_scanned_) {
-        hipLaunchKernelGGL(k_guard_scan, dim3(ceil_div(n_mlp_, 256)), dim3(256), 0, s, (const float*)d_grad_, n_mlp_, (const float*)d_loss_,
-                           guard_scan_args());
-        NRC_HIP(hipGetLastError());
-    }
-    guard_scanned_ = false;      // (the verdict is this step's alone)
-    const GuardArgs ga{d_guard_, d_guard_cell_, guard_stamp_, step};
-    const float lr = cfg_.learning_rate;
-    if (!fused_opt_) {
-        if (sgd_)
-            hipLaunchKernelGGL(k_sgd_ema_guarded, dim3(ceil_div(n_params_, 256)), dim3(256), 0, s, d_w_, d_ema_, d_grad_, n_params_, lr, a, ga);
-        else
-            hipLaunchKernelGGL(k_adam_ema_guarded, dim3(ceil_div(n_params_, 256)), dim3(256), 0, s, d_w_, d_ema_, d_m_, d_v_, d_grad_,
-                               n_params_, n_mlp_, a, ga);
-        NRC_HIP(hipGetLastError());
-        repack(s);
-        return false;
-    }
-    const int next = infer_set_ ^ 1;
-    const PackDst d{d_dst_, d_dst_ + n_mlp_, d_dst_ + 2 * (size_t)n_mlp_, (half_t*)d_pk_fwd_, (half_t*)d_pk_infer_[next], (half_t*)d_pk_bwd_};
-    const dim3 gm(ceil_div(n_mlp_, 256)), b(256);
-    const float* loss = d_loss_;
-    if (hash_) {
-        if (sgd_) hipLaunchKernelGGL((k_opt_pack<true, GuardArgs>), gm, b, 0, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_, lr, a, d, loss, loss_seq, loss_cell, ga);
-        else hipLaunchKernelGGL((k_opt_pack<false, GuardArgs>), gm, b, 0, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_, lr, a, d, loss, loss_seq, loss_cell, ga);
-        uint32_t *tt = (uint32_t*)d_t16_train_, *te = (uint32_t*)d_t16_ema_[next];
-        uint32_t* g16 = (uint32_t*)d_grad16_;
-        if (grid16_valid_) grad16_clean_ = true;      // k_grid_opt<., true> clears the entries it reads, on a bad step too
-        if (n_mlp_ % 4u == 0u && n_grid_entries_ % 2u == 0u) {
-            const uint32_t np = n_grid_entries_ / 2u;
-            const dim3 g2(ceil_div(np, 256));
-            if (sgd_ && grid16_valid_)
-                launch_last((k_grid_opt2<true, true, GuardArgs>), g2, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, np, lr, a, tt, te, ga);
-            else if (sgd_)
-                launch_last((k_grid_opt2<true, false, GuardArgs>), g2, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, np, lr, a, tt, te, ga);
-            else if (grid16_valid_)
-                launch_last((k_grid_opt2<false, true, GuardArgs>), g2, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, np, lr, a, tt, te, ga);
-            else
-                launch_last((k_grid_opt2<false, false, GuardArgs>), g2, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, np, lr, a, tt, te, ga);
-        } else {
-            const dim3 g(ceil_div(n_grid_entries_, 256));
-            const uint32_t ne = n_grid_entries_;
-            if (sgd_ && grid16_valid_)
-                launch_last((k_grid_opt<true, true, GuardArgs>), g, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, ne, lr, a, tt, te, ga);
-            else if (sgd_)
-                launch_last((k_grid_opt<true, false, GuardArgs>), g, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, ne, lr, a, tt, te, ga);
-            else if (grid16_valid_)
-                launch_last((k_grid_opt<false, true, GuardArgs>), g, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, ne, lr, a, tt, te, ga);
-            else
-                launch_last((k_grid_opt<false, false, GuardArgs>), g, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, g16, n_mlp_, ne, lr, a, tt, te, ga);
-        }
-    } else if (sgd_)
-        launch_last((k_opt_pack<true, GuardArgs>), gm, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_, lr, a, d, loss, loss_seq, loss_cell, ga);
-    else
-        launch_last((k_opt_pack<false, GuardArgs>), gm, b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_, lr, a, d, loss, loss_seq, loss_cell, ga);
-    NRC_HIP(hipGetLastError());
-    infer_set_ = next;
-    return loss_cell != nullptr;
+    };
+    return guard_on_ ? enqueue(GuardArgs{d_guard_, d_guard_cell_, guard_stamp_, step}) : enqueue();
 }
 
 }  // namespace nrc

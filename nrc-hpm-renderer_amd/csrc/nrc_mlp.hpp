@@ -128,13 +128,14 @@ public:
     // the gradient vector or the loss cell was rewritten behind backward()'s own scan (exchange, hook, a caller that holds the pointer):
     // optimizer_step() scans again (k_guard_scan, one launch) unless a pass of the caller's does it first with guard_scan_args()
     void guard_stale() { guard_scanned_ = false; }
+    // both: what a writer of the gradient vector that runs behind backward() calls
+    void grad_written_from_outside() { grad_vector_is_source(); guard_stale(); }
     // for a pass that scans the final gradient + loss itself: a fresh stamp; the next optimizer_step() reads that verdict
     GuardArgs guard_scan_args();
     // {skipped steps, number of the last skipped step} as of the last optimizer launch that has completed (a plain host read)
     void guard_stats(uint32_t* skipped, uint32_t* last_step) const;
 
 private:
-    bool optimizer_step_guarded(hipStream_t s, uint32_t loss_seq, unsigned long long* loss_cell);
     bool guard_on_ = false, guard_scanned_ = false;
     uint32_t guard_stamp_ = 0;
     uint32_t* d_guard_ = nullptr;                   // GuardArgs::words

@@ -324,7 +324,7 @@ def test_one_launch_optimizer_equals_the_three_launch_path_bitwise(api, torch_gp
 
 @pytest.mark.parametrize("optimizer", ["Adam", "SGD"])
 def test_hashgrid_one_launch_table_optimizer_equals_the_separate_kernels_bitwise(api, torch_gpu, optimizer, monkeypatch):
-    """HashGrid model: k_opt_pack + k_grid_opt (table gradient read from the packed fp16 table, update, fp16 gather copies) against
+    """HashGrid model: k_opt_pack + k_grid_opt2 (table gradient read from the packed fp16 table, update, fp16 gather copies) against
     k_grid_grad_f32 + k_adam_ema / k_sgd_ema + k_pack + k_pack_grid (NRC_DEBUG=no_fused_opt).  The packed-fp16 atomics of the table
     gradient sum in a different order in every run, so cache B never runs its own backward: it is handed A's gradient vector
     (which also exercises the path that reads the fp32 vector after an exchange) -- weights, EMA, moments and both inference paths

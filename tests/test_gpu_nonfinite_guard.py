@@ -69,14 +69,14 @@ def test_policy_off_keeps_todays_behaviour(api, torch_gpu):
     c.Destroy()
 
 
-# which optimizer kernels a case runs (csrc/nrc_mlp.hip, Mlp::optimizer_step_guarded):
+# which optimizer kernels a case runs (csrc/nrc_mlp.hip, Mlp::optimizer_step with the guard on):
 #   fused     k_opt_pack<sgd, GuardArgs>; HashGrid: + k_grid_opt2<sgd, FROM16 = true, GuardArgs> (the table gradient from the packed fp16 table,
 #             whose entries a bad step must still clear); the verdict from k_reduce_grads<GuardArgs>
-#   unfused   NRC_DEBUG=no_fused_opt: k_adam_ema_guarded / k_sgd_ema_guarded + the repack launches
+#   unfused   NRC_DEBUG=no_fused_opt: k_adam_ema<GuardArgs> / k_sgd_ema<GuardArgs> + the repack launches
 #   vector    the caller holds nrc_cache_grad_ptr (GradTensor()), so the optimizer reads the fp32 vector: HashGrid: k_grid_opt2<sgd, FROM16 = false,
 #             GuardArgs>; the verdict from k_guard_scan, the launch of its own
-# (k_grid_opt, one entry per thread, runs only for a table with an odd number of entries or a matrix block that is no multiple of four
-# parameters: no model the constructor accepts has either)
+# (k_grid_opt2 is the table's only optimizer kernel: an odd number of entries or a matrix block that is no multiple of four parameters is
+# refused by Mlp's constructor, and no model it accepts has either)
 @pytest.mark.parametrize("path", ["fused", "unfused", "vector"])
 @pytest.mark.parametrize("optimizer", ["Adam", "SGD"])
 @pytest.mark.parametrize("model", sorted(MODELS))
