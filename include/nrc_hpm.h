@@ -300,7 +300,9 @@ typedef struct nrc_renderer nrc_renderer_t;
 
 /* NrcHpmRenderer(width, height, blend, camera, appConfig, hpmScene, nrc) (src/NrcHpmRenderer.cu:212-297).
  * The renderer allocates the four NRC I/O buffers and calls nrc_cache_init (as the reference ctor does, :259-266).
- * tile may be NULL. */
+ * tile may be NULL.  Creation also builds the host-side index of the pixels' RNG seeds that the hot-tile search uses (see
+ * nrc_renderer_set_hot_tiles): one hash per pixel and 4 bytes per pixel + 3 MB of host memory -- 84 ms and 11 MB at 1920x1080,
+ * about 0.5 s and 43 MB at 3840x2160 -- whether or not a frame ever uses it; nrc_mc_renderer_create does the same. */
 int nrc_renderer_create(uint32_t width, uint32_t height, int blend, const nrc_camera* camera, const nrc_config* cfg,
                         const nrc_scene* scene, nrc_cache_t* cache, const nrc_tile* tile, void* stream,
                         nrc_renderer_t** out);
@@ -491,13 +493,14 @@ int nrc_renderer_set_cost_order(nrc_renderer_t* r, int on);
 size_t nrc_renderer_tile_order(nrc_renderer_t* r, uint32_t* host_out, size_t capacity);
 /* Hot tiles (on by default): a pixel whose RNG state can run into DeltaTrack's cap of 128 collisions inside a tile the empty-space
  * mask rejects (see set_empty_skip) is ONE lane that walks for ~0.12 ms; started where the launch order has its (empty) tile --
- * at the very end -- it ends the launch that much later (one frame in four on the bench view: mean 0.213 -> 0.232 ms).  Each
- * gen_rays launch therefore also tests its pixels against the NEXT frame's random numbers (drawn one frame early, same sequence;
- * or the ones render_frames was given) -- one more hash per pixel, no launch of its own -- and the next launch starts up to 8 of
- * the tiles found first.  Scheduling only: every tile is traced exactly once either way.  hot_tiles copies the last frame's list
- * -- 8 entries (ty << 16 | tx) and their count -- and returns 1 when the list had been built by the previous frame's launch, 0
- * when by a kernel in front of gen_rays (first frame, pinned random numbers, another camera), -1 when the frame used none, -2 on
- * error. */
+ * at the very end -- it ends the launch that much later (one frame in four on the bench view: mean 0.213 -> 0.232 ms).  The host
+ * therefore finds those pixels when it enqueues a frame, for the random numbers the frame uses, by inverting the RNG's hash (about a
+ * microsecond; the index of the pixels' seeds it uses is built when the renderer is created) and the launch starts up to 8
+ * of their tiles first: no launch of its own, nothing read back.  Scheduling only: every tile is traced exactly once either way.
+ * hot_tiles copies the last frame's list -- 8 entries (ty << 16 | tx), one per such pixel in pixel order, and their count -- from
+ * host memory and returns 1 when the frame's random numbers were known when the frame before it was enqueued (the ones
+ * render_frames was given, or drawn one frame early: same sequence), 0 when not (first frame, pinned random numbers), -1 when the
+ * frame used none, -2 on error. */
 int nrc_renderer_set_hot_tiles(nrc_renderer_t* r, int on);
 int nrc_renderer_hot_tiles(nrc_renderer_t* r, uint32_t* host_out9);
 /* The NRC vertex images (buffers 2 and 3: nrcRayOrigin / nrcRayDir of gen_rays.comp:97-100) are read back only at the pixels of

@@ -59,16 +59,7 @@ __device__ __forceinline__ V3 sel(bool b, V3 x, V3 y) { return v3(b ? x.x : y.x,
 __device__ __forceinline__ V3 madd(V3 d, float t, V3 o) { return v3(nrc_fmaf_(d.x, t, o.x), nrc_fmaf_(d.y, t, o.y), nrc_fmaf_(d.z, t, o.z)); }   // o + d*t
 
 // ---- include/random.glsl:24-70
-__device__ __forceinline__ uint32_t hash1(uint32_t x)
-{
-    x += (x << 10);
-    x ^= (x >> 6);
-    x += (x << 3);
-    x ^= (x >> 11);
-    x += (x << 15);
-    return x;
-}
-__device__ __forceinline__ float float_construct(uint32_t m) { return nrc_u2f((m & 0x007fffffu) | 0x3f800000u) - 1.0f; }
+// (hash1, float_construct: nrc_hot_tiles.hpp)
 __device__ __forceinline__ float random1(float x) { return float_construct(hash1(nrc_f2u(x))); }
 __device__ __forceinline__ float random2(float x, float y) { return float_construct(hash1(nrc_f2u(x) ^ hash1(nrc_f2u(y)))); }
 __device__ __forceinline__ float random4(const float* v)
@@ -841,8 +832,7 @@ __device__ __forceinline__ void nrc_query(const DevScene& s, V3 pos, V3 dir, flo
 // global column of local column lx (nrc_tile: strips of 2^x_block_log2 columns, every x_stride-th strip)
 __device__ __forceinline__ uint32_t global_x(const DevFrame& fr, uint32_t lx)
 {
-    const uint32_t b = fr.x_block_log2;
-    return ((fr.x_offset + (lx >> b) * fr.x_stride) << b) + (lx & ((1u << b) - 1u));
+    return nrc::global_x(fr.x_offset, fr.x_stride, fr.x_block_log2, lx);
 }
 
 // 16x16 pixel tile per 256-thread workgroup, 8x8 per wave (coherent paths inside a wave)
@@ -985,32 +975,7 @@ __global__ __launch_bounds__(256) void k_flight_select(const float* __restrict__
     }
 }
 
-// the tiles with a pixel in a capped RNG state (list mode), for DevFrame::hot_tiles: hot[kHotTilesMax] counts them (zeroed by the
-// caller), the first kHotTilesMax are kept in hot[0..].  Used in front of a camera kernel whose list is not there yet -- k_gen_rays
-// builds the next frame's list itself (DevFrame::hot_next); this kernel serves its first frame, pinned random numbers and
-// k_mc_render.  One-wave workgroups of 10 VGPRs: they find room beside the camera kernels of other renderers, whose five waves
-// per SIMD leave 32 of a lane's 512 VGPRs (1024-thread workgroups waited for such a kernel to thin out: 99 us instead of 3).
-// Eight pixels per thread.
-__global__ __launch_bounds__(64) void k_hot_tiles(DevFrame fr, uint32_t* __restrict__ hot)
-{
-    NRC_RAISE_WAVE_PRIORITY(16);
-    const uint32_t n = fr.w * fr.h;
-    for (uint32_t i = blockIdx.x * 64u + threadIdx.x; i < n; i += gridDim.x * 64u) {
-        const uint32_t y = i / fr.w, lx = i - y * fr.w;
-        const float u = (float)global_x(fr, lx) * fr.inv_gw, v = (float)y * fr.inv_gh;
-        const float rng0 = random2(random2(u, v), random4(fr.random));      // init_random
-        const uint32_t m = nrc_f2u(rng0 + 1.0f) & 0x007fffffu;
-        bool capped = false;
-#pragma unroll
-        for (uint32_t k = 0; k < kFlightListMax; k++) capped |= (k < fr.flight_n) & (m == fr.flight_list[k]);
-        if (capped) {
-            const uint32_t k = atomicAdd(&hot[kHotTilesMax], 1u);
-            if (k < kHotTilesMax) hot[k] = ((y >> 3) << 16) | (lx >> 3);
-        }
-    }
-}
-
-// The tile of a camera kernel's wave.  With a hot-tile list (DevFrame::hot_tiles) the launch has kHotTilesMax waves in front of the
+// The tile of a camera kernel's wave.  With hot tiles (DevFrame::hot_front) the launch has kHotTilesMax waves in front of the
 // ordered ones: wave k traces hot tile k, and the wave the order gives that tile to leaves.  false: the wave has nothing to do.
 __device__ __forceinline__ bool camera_wave_tile(const DevFrame& fr, uint32_t* lx_, uint32_t* y_, uint32_t* slot_, bool* inside_, bool* hot_wave_)
 {
@@ -1019,22 +984,17 @@ __device__ __forceinline__ bool camera_wave_tile(const DevFrame& fr, uint32_t* l
     bool hot_wave = false;
     {
         uint32_t d = __builtin_amdgcn_readfirstlane(blockIdx.x * CAMERA_WAVES_PER_BLOCK + (threadIdx.x >> 6));
-        if (fr.hot_tiles != nullptr) {
+        if (fr.hot_front != 0u) {
             // the launch has kHotTilesMax waves in front of the ordered ones: wave k traces hot tile k, and the wave the order
-            // gives that tile to leaves
-            typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
-            uint32_t hot_n;
-            u32x8 hv;
-            asm volatile("s_load_dword %0, %2, 0x20\n\ts_load_dwordx8 %1, %2, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(hot_n), "=&s"(hv) : "s"(fr.hot_tiles) : "memory");
-            hot_n = min(hot_n, kHotTilesMax);
-            const uint32_t hot[kHotTilesMax] = {hv[0], hv[1], hv[2], hv[3], hv[4], hv[5], hv[6], hv[7]};
+            // gives that tile to leaves.  The list is a kernel argument: scalar registers, no load to wait for.
+            const uint32_t hot_n = fr.hot_n;
+            const uint32_t* hot = fr.hot;
             if (d < kHotTilesMax) {
-                if (d == 0u && fr.hot_reset != nullptr && (threadIdx.x & 63u) == 0u) *fr.hot_reset = 0u;
                 if (d >= hot_n) return false;
                 uint32_t t = 0;
 #pragma unroll
                 for (uint32_t k = 0; k < kHotTilesMax; k++) t = d == k ? hot[k] : t;
-                // k_hot_tiles appends one entry per capped PIXEL: two such pixels in one tile list the tile twice, and the tile must
+                // the list has one entry per capped PIXEL: two such pixels in one tile list the tile twice, and the tile must
                 // still be traced exactly once (k_mc_render blends in place) -- the later duplicate leaves
                 bool dup = false;
 #pragma unroll
@@ -1126,16 +1086,6 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK, NRC_GEN_WAVES_PER_SIMD
     const uint32_t gx = global_x(fr, lx);
     const float u = (float)gx * fr.inv_gw, v = (float)y * fr.inv_gh;
     const float seed_uv = random2(u, v);      // the pixel's part of init_random's seed
-    if (fr.hot_next != nullptr) {             // the next frame's hot tiles (DevFrame::hot_next): is a pixel of this tile in a capped state then?
-        const uint32_t m = nrc_f2u(random2(seed_uv, random4(fr.random_next)) + 1.0f) & 0x007fffffu;
-        bool capped = false;
-#pragma unroll
-        for (uint32_t k = 0; k < kFlightListMax; k++) capped |= (k < fr.flight_n) & (m == fr.flight_list[k]);
-        if (__ballot(inside & capped) != 0ull && (threadIdx.x & 63u) == 0u) {
-            const uint32_t k = atomicAdd(&fr.hot_next[kHotTilesMax], 1u);
-            if (k < kHotTilesMax) fr.hot_next[k] = __builtin_amdgcn_readfirstlane(((y >> 3) << 16) | (lx >> 3));
-        }
-    }
     // Two of three tiles of the bench view miss the medium.  Their waves are the tail of the launch (k_tile_order starts the
     // costliest tiles first): the tile's bit comes through the scalar cache, and the wave is gone before the occupancy table is
     // copied (there is no workgroup barrier in this kernel: load_occupancy_per_wave).  What is left of them is dispatch: ~1000
@@ -2329,19 +2279,13 @@ void launch_gen_rays(const DevScene& sc, const DevCamera& cam, const DevFrame& f
     kernel = k_gen_rays<true>;      // (the profiling build's per-pixel look-up counts, tools/lane_model.py)
 #endif
     dim3 grid = wave_tile_grid(fr.w, fr.h);
-    if (fr.hot_tiles != nullptr) grid.x += kHotTilesMax / CAMERA_WAVES_PER_BLOCK;
+    if (fr.hot_front != 0u) grid.x += kHotTilesMax / CAMERA_WAVES_PER_BLOCK;
     DevFrame fa = fr;
     fa.raise_priority = (g_host_raise_wave_priority != 0 && fr.camera_priority_low == 0u) ? 1u : 0u;
     // (launch_last: the frame's start / "gen_rays done" events ride on the launch when the frame graph armed them -- nrc_common.hpp)
     launch_last(kernel, grid, dim3(64 * CAMERA_WAVES_PER_BLOCK), 0u, s, sc, cam, fa,
                 primary_ray_length, primary_ray_prob, (float4*)primary, info, (float4*)origin, (float4*)dir, infer_in,
                 fetch_counter, tg, full_vertex_images ? 1 : 0);
-    NRC_HIP(hipGetLastError());
-}
-
-void launch_hot_tiles(const DevFrame& fr, uint32_t* hot, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_hot_tiles, dim3(4096), dim3(64), 0, s, fr, hot);
     NRC_HIP(hipGetLastError());
 }
 
@@ -2479,7 +2423,7 @@ void launch_mc_render(const DevScene& sc, const DevCamera& cam, const DevFrame& 
                       float blend_factor, float* out_rgba, float* info, unsigned long long* fetch_counter, hipStream_t s)
 {
     dim3 grid = wave_tile_grid(fr.w, fr.h);
-    if (fr.hot_tiles != nullptr) grid.x += kHotTilesMax / CAMERA_WAVES_PER_BLOCK;
+    if (fr.hot_front != 0u) grid.x += kHotTilesMax / CAMERA_WAVES_PER_BLOCK;
     DevFrame fa = fr;
     fa.raise_priority = (g_host_raise_wave_priority != 0 && fr.camera_priority_low == 0u) ? 1u : 0u;
     hipLaunchKernelGGL(fetch_counter ? k_mc_render<true> : k_mc_render<false>, grid, dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,

@@ -3,6 +3,7 @@
 // data/shader/mc/render.comp and data/shader/include/{random,volume,dir_gen,path_trace}.glsl.
 #pragma once
 #include "nrc_common.hpp"
+#include "nrc_hot_tiles.hpp"
 
 namespace nrc {
 
@@ -59,18 +60,14 @@ struct DevFrame {
     // sampled launches: the costliest-first order is hurt by tiles it under-estimates (a long tile started late ends the launch),
     // not by tiles it over-estimates
     uint32_t tile_cost_keep;
-    // tiles k_gen_rays starts FIRST, whatever the order says: {kHotTilesMax entries (ty << 16 | tx), then their count}, written by
-    // the previous frame's k_gen_rays (hot_next) or by k_hot_tiles for this frame's random numbers; nullptr: none.  A pixel in a capped RNG state (see flight_mode) in a tile the
-    // mask rejects is one lane that walks for ~120 us; its wave would otherwise start among the empty tiles at the end of the
-    // launch and end it that much later (one frame in four on the bench view).  Scheduling only: every tile is traced exactly once
-    // with or without the list.
-    const uint32_t* hot_tiles;
-    // k_gen_rays builds the NEXT frame's list itself: every wave tests its tile's pixels against the next frame's random numbers
-    // (random_next; one more hash per pixel, the pixel's own part of the seed is shared) and appends to hot_next; it also zeroes the
-    // count cell of the list after that one (hot_reset).  Three list buffers rotate; no extra launch, no event.  nullptr: off.
-    uint32_t* hot_next;
-    uint32_t* hot_reset;
-    float random_next[4];
+    // Tiles the camera kernels start FIRST, whatever the order says: hot_front != 0 gives the launch kHotTilesMax waves in front of the
+    // ordered ones, and wave k < hot_n of them traces tile hot[k] (ty << 16 | tx).  A pixel in a capped RNG state (see flight_mode) in a
+    // tile the mask rejects is one lane that walks for ~120 us; its wave would otherwise start among the empty tiles at the end of the
+    // launch and end it that much later (one frame in four on the bench view).  The host finds those pixels when it enqueues the frame
+    // (HotTileFinder, nrc_hot_tiles.hpp) and the list travels here by value.  Scheduling only: every tile is traced exactly once with
+    // or without the list.
+    uint32_t hot_front, hot_n;
+    uint32_t hot[8];
     // the frame's LIVE queries (pixels that scattered: 22 % on the bench view): k_gen_rays appends their query indices to live_list
     // and counts them in *live_count (zeroed by the caller in front of the launch); nullptr: no list.  The order of the
     // list is whatever the waves' atomics made it; its only reader (the HashGrid encoder, Mlp::launch_features) writes by query index.
@@ -87,7 +84,6 @@ struct DevFrame {
     uint32_t skip_dead_queries;
 };
 constexpr uint32_t kOrderSlotMask = 0x00ffffffu;      // (most tiles a launch order can address)
-constexpr uint32_t kHotTilesMax = 8;      // = the waves of the two workgroups the launch gains in front
 
 // forward camera transform for the tile mask: clip = m * (x, y, z, 1), column-major like DevCamera::m
 struct DevProjView {
@@ -105,8 +101,6 @@ void launch_gen_rays(const DevScene& sc, const DevCamera& cam, const DevFrame& f
 
 // marks the 8x8-pixel tiles whose camera rays can meet a non-empty voxel: `boxes` = n axis-aligned world-space boxes
 // {lo.xyz, hi.xyz} that together cover every non-empty voxel with a margin of one voxel.  mask: ceil(tiles/32) + 1 words, zeroed.
-// finds the pixels of the frame whose RNG state is in fr.flight_list (flight_mode 1) and appends their tiles to hot (count zeroed by the caller: hot[kHotTilesMax])
-void launch_hot_tiles(const DevFrame& fr, uint32_t* hot, hipStream_t s);
 // tile-major query order of the renderer's inference buffers (see query_index in nrc_integrator.hip) -> x * H + y
 void launch_query_layout(const DevFrame& fr, uint32_t floats_per_query, const float* tiled, float* linear, hipStream_t s,
                          const float* info = nullptr);
@@ -147,7 +141,6 @@ void launch_volume_rebuild_bricks(const int32_t* origins, const void* bricks, ui
                                   uint32_t* brick_index, hipStream_t s);
 // table[m] = optical distance covered by the 128 free flights a delta walk draws from RNG state m when it rejects every collision
 constexpr uint32_t kFlightStates = 1u << 23;
-constexpr uint32_t kFlightListMax = 8;
 void launch_flight_table(float* table, hipStream_t s);
 // the states whose table entry does not exceed lambda: count_and_list[0] = their number, [1..8] the first eight (any order);
 // bits (kFlightStates / 32 words): bit m set for every such state
