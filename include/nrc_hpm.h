@@ -378,6 +378,40 @@ int nrc_renderer_set_volume(nrc_renderer_t* r, const void* density, uint32_t nx,
  * kept (cache, optimizer state, training ring, schedule key), and in a sharded run every rank calls it with the whole list.  Dense and
  * brick calls may be mixed freely.  The device buffers are the rebuild of the densified list, bit for bit. */
 int nrc_renderer_set_volume_bricks(nrc_renderer_t* r, const int32_t* origins, const void* bricks, uint32_t n_bricks, int format, int on_device);
+/* Volume keyframes (retiming a cached simulation, slow motion, an animated fly-through; the reference has no equivalent): a sequence
+ * of key volumes resident on the device, and the renderer's medium set to the linear in-between of two of them.
+ *   Keys.  A renderer holds n_keys key volumes; key i sits at time i.  volumes is one contiguous [n_keys][nz][ny][nx] array of `format`
+ *     with the dims the renderer was created with; the library keeps its own copy on the device as R8 (n_keys * nx*ny*nz bytes).  A
+ *     NRC_VOLUME_F32 source is quantised once, at upload, by the rule of nrc_renderer_set_volume: exactly the bytes that call would have
+ *     written.  on_device = 0: host memory, the call copies and returns when the copy is done; on_device = 1: device memory, read on the
+ *     stream given at creation, and the call does not wait for that read.  n_keys = 0 drops the sequence (the other arguments are then
+ *     ignored).  Replacing or dropping a sequence may wait for every stream of the renderer (the frames in flight may read the old
+ *     keys): this is NOT a per-frame call.  The renderer's current medium is not touched.  A call that fails -- other dims, volumes ==
+ *     NULL, an unknown format, an allocation failure -- leaves the renderer and the previous keys as they were.
+ *   Time -> key pair and weight.  t must be finite and inside [0, n_keys - 1]; otherwise NRC_ERR_INVALID, and nothing is enqueued
+ *     (no keys: every t fails).  i = min((uint32)t, n_keys - 1); w = t - (float)i in fp32; W = (uint32)(w * 256.0f + 0.5f), so
+ *     0 <= W <= 256, and W = 0 at the last key.
+ *   The in-between voxel is integer arithmetic, bit-exact on every machine: with a, b the R8 voxels of keys i and i + 1,
+ *         q = (a * (256 - W) + b * W + 128) >> 8.
+ *     W = 0 gives a and W = 256 gives b; q lies between a and b, so the majorant (density_factor, texture <= 1) stays valid.  A voxel
+ *     of 1 fading to 0 is 1 up to W = 128 and 0 from W = 129: the occupancy bits and the empty-space boxes follow q, not the keys.
+ *   nrc_renderer_set_volume_time(t) is, by definition, nrc_renderer_set_volume(the in-between volume of t, NRC_VOLUME_U8, on_device = 1):
+ *     the same slot swap, the same three device buffers byte for byte (nrc_renderer_volume_buffer), the same blending restart, the
+ *     cache's weights, optimizer state and ring kept, and no host wait.  The in-between is blended straight into the slot.
+ *   nrc_renderer_render_path_timed is nrc_renderer_render_path with a time per view: it computes, bit for bit, what
+ *         set_volume_time(times[i]); set_camera(cameras[i]); frames_per_camera x render(train); copy to d_frames + i*h*w*4
+ *     per view computes (framebuffer, images and, with train, loss, weights, optimizer state, step and ring), enqueued by one call that
+ *     does not wait for the GPU.  times: n_cameras host floats, every one checked before the first view is enqueued (one bad time:
+ *     NRC_ERR_INVALID, nothing rendered); times == NULL is nrc_renderer_render_path.  A view whose (i, W) is what the sequence last put
+ *     into the renderer (by set_volume_time or a timed path, with no set_volume / set_volume_bricks / set_volume_keys call since) skips
+ *     the rebuild -- the result cannot differ; (i, 256) and (i + 1, 0) count as the same.  Everything else as for nrc_renderer_render_path.
+ *   In a sharded run every rank makes the same calls with the same keys and times. */
+int nrc_renderer_set_volume_keys(nrc_renderer_t* r, const void* volumes, uint32_t n_keys, uint32_t nx, uint32_t ny, uint32_t nz, int format,
+                                 int on_device);
+uint32_t nrc_renderer_volume_key_count(nrc_renderer_t* r);
+int nrc_renderer_set_volume_time(nrc_renderer_t* r, float t);
+int nrc_renderer_render_path_timed(nrc_renderer_t* r, uint32_t n_cameras, const nrc_camera* cameras, const float* times,
+                                   uint32_t frames_per_camera, const float* frame_randoms, int train, float* d_frames);
 /* diagnostics: the current volume's device buffers after synchronising the renderer -- which 0: density [nz][ny][nx] u8, 1: occupancy
  * bits (uint32 words), 2: empty-space boxes float[6 * n] {lo.xyz, hi.xyz}; *bytes = their size (NULL, bytes 0: no boxes) */
 const void* nrc_renderer_volume_buffer(nrc_renderer_t* r, int which, size_t* bytes);
@@ -542,6 +576,13 @@ size_t nrc_mc_renderer_tile_mask(nrc_mc_renderer_t* r, uint32_t* host_out, size_
 int nrc_mc_renderer_set_volume(nrc_mc_renderer_t* r, const void* density, uint32_t nx, uint32_t ny, uint32_t nz, int format, int on_device);
 /* see nrc_renderer_set_volume_bricks */
 int nrc_mc_renderer_set_volume_bricks(nrc_mc_renderer_t* r, const int32_t* origins, const void* bricks, uint32_t n_bricks, int format, int on_device);
+/* see nrc_renderer_set_volume_keys (no train flag in the timed path; one stream: rebuilds, views and copies in stream order) */
+int nrc_mc_renderer_set_volume_keys(nrc_mc_renderer_t* r, const void* volumes, uint32_t n_keys, uint32_t nx, uint32_t ny, uint32_t nz, int format,
+                                    int on_device);
+uint32_t nrc_mc_renderer_volume_key_count(nrc_mc_renderer_t* r);
+int nrc_mc_renderer_set_volume_time(nrc_mc_renderer_t* r, float t);
+int nrc_mc_renderer_render_path_timed(nrc_mc_renderer_t* r, uint32_t n_cameras, const nrc_camera* cameras, const float* times,
+                                      uint32_t frames_per_camera, const float* frame_randoms, float* d_frames);
 const void* nrc_mc_renderer_volume_buffer(nrc_mc_renderer_t* r, int which, size_t* bytes);
 int nrc_mc_renderer_set_frame_random(nrc_mc_renderer_t* r, const float random4[4]);
 const float* nrc_mc_renderer_framebuffer(nrc_mc_renderer_t* r);   /* RGBA32F, alpha = blended didScatter */

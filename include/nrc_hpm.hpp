@@ -456,6 +456,13 @@ public:
     {
         nrc_check(nrc_renderer_render_path(h_, nCameras, cameras, framesPerCamera, frameRandoms, train ? 1 : 0, dFrames));
     }
+    // the same with a time per view into the volume keys (nrc_renderer_render_path_timed): SetVolumeTime(times[i]) in front of view i;
+    // times: nCameras floats, or nullptr for the path above
+    void RenderPath(void* /*queue*/, uint32_t nCameras, const nrc_camera* cameras, const float* times, uint32_t framesPerCamera,
+                    const float* frameRandoms, bool train, float* dFrames)
+    {
+        nrc_check(nrc_renderer_render_path_timed(h_, nCameras, cameras, times, framesPerCamera, frameRandoms, train ? 1 : 0, dFrames));
+    }
     // diagnostics: the empty-space tile mask in use (synchronises; empty: the frame uses none) -- nrc_renderer_tile_mask
     std::vector<uint32_t> TileMask() const
     {
@@ -476,6 +483,15 @@ public:
     {
         nrc_check(nrc_renderer_set_volume_bricks(h_, origins, bricks, nBricks, format, onDevice ? 1 : 0));
     }
+    // volume keyframes (nrc_renderer_set_volume_keys): volumes [nKeys][nz][ny][nx] of the creation dims, kept on the device as R8, key i at
+    // time i (nKeys = 0 drops them; not a per-frame call); SetVolumeTime(t), 0 <= t <= nKeys - 1: the medium becomes the in-between of
+    // keys (uint32)t and (uint32)t + 1, as SetVolume of that volume would make it, without a host wait
+    void SetVolumeKeys(const void* volumes, uint32_t nKeys, uint32_t nx, uint32_t ny, uint32_t nz, int format = NRC_VOLUME_U8, bool onDevice = true)
+    {
+        nrc_check(nrc_renderer_set_volume_keys(h_, volumes, nKeys, nx, ny, nz, format, onDevice ? 1 : 0));
+    }
+    uint32_t VolumeKeyCount() const { return nrc_renderer_volume_key_count(h_); }
+    void SetVolumeTime(float t) { nrc_check(nrc_renderer_set_volume_time(h_, t)); }
     nrc_renderer_t* Handle() const { return h_; }
 
 private:
@@ -519,6 +535,11 @@ public:
     {
         nrc_check(nrc_mc_renderer_render_path(h_, nCameras, cameras, framesPerCamera, frameRandoms, dFrames));
     }
+    void RenderPath(void* /*queue*/, uint32_t nCameras, const nrc_camera* cameras, const float* times, uint32_t framesPerCamera,
+                    const float* frameRandoms, float* dFrames)
+    {
+        nrc_check(nrc_mc_renderer_render_path_timed(h_, nCameras, cameras, times, framesPerCamera, frameRandoms, dFrames));
+    }
     std::vector<uint32_t> TileMask() const
     {
         std::vector<uint32_t> m(nrc_mc_renderer_tile_mask(h_, nullptr, 0));
@@ -537,6 +558,13 @@ public:
     {
         nrc_check(nrc_mc_renderer_set_volume_bricks(h_, origins, bricks, nBricks, format, onDevice ? 1 : 0));
     }
+    // see NrcHpmRenderer::SetVolumeKeys / SetVolumeTime
+    void SetVolumeKeys(const void* volumes, uint32_t nKeys, uint32_t nx, uint32_t ny, uint32_t nz, int format = NRC_VOLUME_U8, bool onDevice = true)
+    {
+        nrc_check(nrc_mc_renderer_set_volume_keys(h_, volumes, nKeys, nx, ny, nz, format, onDevice ? 1 : 0));
+    }
+    uint32_t VolumeKeyCount() const { return nrc_mc_renderer_volume_key_count(h_); }
+    void SetVolumeTime(float t) { nrc_check(nrc_mc_renderer_set_volume_time(h_, t)); }
     nrc_mc_renderer_t* Handle() const { return h_; }
 
 private:

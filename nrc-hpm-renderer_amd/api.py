@@ -11,6 +11,8 @@ PyTorch is plumbing only (device memory, current stream, torch.distributed); all
 There is no CPU fallback: loading fails loudly if the HIP library is missing.
 """
 import ctypes as C
+import functools
+import inspect
 import os
 
 import numpy as np
@@ -85,6 +87,8 @@ ABI_SYMBOLS = [
     "nrc_renderer_set_scene_params", "nrc_mc_renderer_set_scene_params",
     "nrc_renderer_set_volume", "nrc_mc_renderer_set_volume", "nrc_renderer_volume_buffer", "nrc_mc_renderer_volume_buffer",
     "nrc_renderer_set_volume_bricks", "nrc_mc_renderer_set_volume_bricks",
+    "nrc_renderer_set_volume_keys", "nrc_mc_renderer_set_volume_keys", "nrc_renderer_volume_key_count", "nrc_mc_renderer_volume_key_count",
+    "nrc_renderer_set_volume_time", "nrc_mc_renderer_set_volume_time", "nrc_renderer_render_path_timed", "nrc_mc_renderer_render_path_timed",
     "nrc_renderer_render_path", "nrc_mc_renderer_render_path", "nrc_renderer_tile_mask", "nrc_mc_renderer_tile_mask",
     "nrc_renderer_set_show_nrc", "nrc_renderer_set_frame_random", "nrc_renderer_framebuffer", "nrc_renderer_framebuffer_on",
     "nrc_renderer_export_exr",
@@ -164,6 +168,16 @@ def load_library():
     if hasattr(L, "nrc_renderer_render_path"):
         L.nrc_renderer_render_path.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
         L.nrc_mc_renderer_render_path.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    if hasattr(L, "nrc_renderer_set_volume_keys"):      # (an older build loaded through NRC_HPM_LIB has no volume keys)
+        for name in ("nrc_renderer_set_volume_keys", "nrc_mc_renderer_set_volume_keys"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int]
+        for name in ("nrc_renderer_volume_key_count", "nrc_mc_renderer_volume_key_count"):
+            getattr(L, name).restype = C.c_uint32
+            getattr(L, name).argtypes = [C.c_void_p]
+        for name in ("nrc_renderer_set_volume_time", "nrc_mc_renderer_set_volume_time"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_float]
+        L.nrc_renderer_render_path_timed.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
+        L.nrc_mc_renderer_render_path_timed.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.nrc_mc_renderer_frame_time_ms.restype = C.c_float
     for name in ("nrc_cache_get_loss", "nrc_cache_get_loss_blocking", "nrc_renderer_is_blending", "nrc_mc_renderer_is_blending",
                  "nrc_cache_get_infer_batch_count", "nrc_cache_get_train_batch_count",
@@ -356,15 +370,43 @@ def _set_volume_bricks(fn, h, origins, bricks):
     _check(fn(h, _dev_ptr(origins) if n else None, _dev_ptr(bricks) if n else None, n, fmt, 1))
 
 
-def _render_path(call, width, height, cameras, framesPerCamera, frameRandoms, out):
+def _set_volume_keys(fn, h, keys):
+    """SetVolumeKeys of both renderers: keys [n_keys][nz][ny][nx], a C-contiguous numpy array (host memory: the call copies it and waits for
+    the copy) or a contiguous CUDA torch tensor (read on the renderer's stream; the call does not wait for that), uint8 or float32; None
+    or an array of no keys drops the sequence"""
+    if keys is None:
+        _check(fn(h, None, 0, 0, 0, 0, VOLUME_U8, 0))
+        return
+    if isinstance(keys, np.ndarray):
+        if keys.dtype not in (np.uint8, np.float32) or keys.ndim != 4 or not keys.flags.c_contiguous:
+            raise RuntimeError("SkyRenderer ERROR: SetVolumeKeys takes a C-contiguous uint8 or float32 numpy array [n_keys][nz][ny][nx] (got %s %s)"
+                               % (keys.dtype, keys.shape))
+        n, nz, ny, nx = keys.shape
+        _check(fn(h, C.c_void_p(keys.ctypes.data) if n else None, n, nx, ny, nz, VOLUME_F32 if keys.dtype == np.float32 else VOLUME_U8, 0))
+        return
+    import torch
+    if not isinstance(keys, torch.Tensor) or not keys.is_cuda or keys.dim() != 4 or not keys.is_contiguous() \
+            or keys.dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError("SkyRenderer ERROR: SetVolumeKeys takes a contiguous CUDA tensor or a numpy array, uint8 or float32 [n_keys][nz][ny][nx]")
+    n, nz, ny, nx = keys.shape
+    _check(fn(h, _dev_ptr(keys) if n else None, n, nx, ny, nz, VOLUME_F32 if keys.dtype == torch.float32 else VOLUME_U8, 1))
+
+
+def _render_path(call, width, height, cameras, framesPerCamera, frameRandoms, out, times=None):
     """RenderPath of both renderers: cameras is a sequence of scene.make_camera dicts, frameRandoms None or [len(cameras) * framesPerCamera][4],
     out None (a new tensor is returned) or a contiguous float32 CUDA tensor [len(cameras)][height][width][4], or False (no images: the last
-    view stays in GetImage()).  call(n, cameras pointer, frames per camera, randoms pointer, images pointer) makes the library call."""
+    view stays in GetImage()), times None or len(cameras) times into the volume keys.  call(n, cameras pointer, frames per camera, randoms
+    pointer, images pointer[, times pointer]) makes the library call."""
     import torch
     cams = list(cameras)
     n, fpc = len(cams), int(framesPerCamera)
     if fpc < 0:
         raise ValueError("RenderPath: framesPerCamera must not be negative")
+    t = None
+    if times is not None:
+        t = np.ascontiguousarray(times, np.float32).reshape(-1)
+        if t.size != n:
+            raise ValueError("RenderPath: %d times for %d views" % (t.size, n))
     arr = (NrcCamera * max(n, 1))(*[make_c_camera(c) for c in cams])
     r = None
     if frameRandoms is not None:
@@ -377,9 +419,24 @@ def _render_path(call, width, height, cameras, framesPerCamera, frameRandoms, ou
     elif out is not False:
         if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
             raise ValueError("RenderPath: out must be a contiguous float32 CUDA tensor of shape %s" % (shape,))
-    _check(call(C.c_uint32(n), C.cast(arr, C.c_void_p), C.c_uint32(fpc), C.c_void_p(r.ctypes.data) if r is not None else None,
-                _dev_ptr(out) if out is not False and n else None))
+    args = (C.c_uint32(n), C.cast(arr, C.c_void_p), C.c_uint32(fpc), C.c_void_p(r.ctypes.data) if r is not None else None,
+            _dev_ptr(out) if out is not False and n else None)
+    _check(call(*args) if t is None else call(*args, C.c_void_p(t.ctypes.data)))
     return None if out is False else out
+
+
+def _times_keyword(plain):
+    """RenderPath(..., times=None) of both renderers.  The keyword rides on the untimed method: its positional signature is a published
+    one (callers and tests/test_camera_path_host.py name its parameters in order) and stays what inspect.signature reports; a call
+    without times is `plain`'s own, a call with times goes to the renderer's _path with the same arguments."""
+    @functools.wraps(plain)
+    def RenderPath(self, *args, times=None, **kw):
+        if times is None:
+            return plain(self, *args, **kw)
+        bound = inspect.signature(plain).bind(self, *args, **kw)
+        bound.apply_defaults()
+        return self._path(*list(bound.arguments.values())[1:], times)
+    return RenderPath
 
 
 def _tile_mask(fn, h):
@@ -748,9 +805,20 @@ class NrcHpmRenderer:
         """a camera path (include/nrc_hpm.h, nrc_renderer_render_path): for every camera of `cameras` (scene.make_camera / scene.orbit_cameras)
         SetCamera + framesPerCamera Render calls, bit for bit, enqueued by one call that does not wait for the GPU.  Returns the views as a
         torch CUDA tensor [n, height, width, 4] (`out` when given; out=False: no images, the last view stays in GetImage()); the stream given
-        at construction is ordered behind the last view's copy.  frameRandoms: None or [n * framesPerCamera][4]."""
-        return _render_path(lambda n, cams, fpc, rnd, img: self.L.nrc_renderer_render_path(self.h, n, cams, fpc, rnd, C.c_int(int(bool(train))), img),
-                            self.width, self.height, cameras, framesPerCamera, frameRandoms, out)
+        at construction is ordered behind the last view's copy.  frameRandoms: None or [n * framesPerCamera][4].
+        times: None, or one time per view into the volume keys (SetVolumeKeys): SetVolumeTime(times[i]) in front of view i's SetCamera
+        (nrc_renderer_render_path_timed); one time outside [0, VolumeKeyCount() - 1] fails the call before anything is rendered."""
+        return self._path(cameras, framesPerCamera, frameRandoms, train, out, None)
+    RenderPath = _times_keyword(RenderPath)
+
+    def _path(self, cameras, framesPerCamera, frameRandoms, train, out, times):
+        tr = C.c_int(int(bool(train)))
+
+        def call(n, cams, fpc, rnd, img, t=None):
+            if t is None:
+                return self.L.nrc_renderer_render_path(self.h, n, cams, fpc, rnd, tr, img)
+            return self.L.nrc_renderer_render_path_timed(self.h, n, cams, t, fpc, rnd, tr, img)
+        return _render_path(call, self.width, self.height, cameras, framesPerCamera, frameRandoms, out, times)
 
     def TileMask(self):
         """the empty-space tile mask in use (numpy uint32: the bit words + the trailing "off for this camera" word; empty: no mask in use);
@@ -774,6 +842,20 @@ class NrcHpmRenderer:
         """the same from 8^3 bricks (include/nrc_hpm.h, nrc_renderer_set_volume_bricks; scene.volume_to_bricks makes them of a dense volume):
         origins int32 [n][3] (x, y, z: multiples of 8), bricks uint8 or float32 [n][8][8][8]; voxels no brick covers become 0"""
         _set_volume_bricks(self.L.nrc_renderer_set_volume_bricks, self.h, origins, bricks)
+
+    def SetVolumeKeys(self, keys):
+        """volume keyframes (include/nrc_hpm.h, nrc_renderer_set_volume_keys): keys [n_keys][nz][ny][nx] of the creation dims, uint8 or
+        float32, a numpy array or a CUDA tensor; key i sits at time i.  The renderer keeps its own R8 copy on the device.  None drops the
+        sequence.  Not a per-frame call: it may wait for the frames in flight."""
+        _set_volume_keys(self.L.nrc_renderer_set_volume_keys, self.h, keys)
+
+    def VolumeKeyCount(self):
+        return int(self.L.nrc_renderer_volume_key_count(self.h))
+
+    def SetVolumeTime(self, t):
+        """the medium becomes the in-between of the two keys around time t, 0 <= t <= VolumeKeyCount() - 1 (scene.volume_at is the CPU
+        statement): what SetVolume of that volume does, without a host wait"""
+        _check(self.L.nrc_renderer_set_volume_time(self.h, C.c_float(float(t))))
 
     def VolumeBuffer(self, name):
         """device view of the current volume's 'density', 'occ_bits' or 'boxes' (after synchronising the renderer)"""
@@ -971,10 +1053,18 @@ class McHpmRenderer:
 
     def RenderPath(self, cameras, framesPerCamera, frameRandoms=None, train=False, out=None):
         """see NrcHpmRenderer.RenderPath (this renderer does not train: `train` must be False)"""
+        return self._path(cameras, framesPerCamera, frameRandoms, train, out, None)
+    RenderPath = _times_keyword(RenderPath)
+
+    def _path(self, cameras, framesPerCamera, frameRandoms, train, out, times):
         if train:
             raise ValueError("McHpmRenderer.RenderPath: the Monte Carlo renderer has nothing to train")
-        return _render_path(lambda n, cams, fpc, rnd, img: self.L.nrc_mc_renderer_render_path(self.h, n, cams, fpc, rnd, img),
-                            self.width, self.height, cameras, framesPerCamera, frameRandoms, out)
+
+        def call(n, cams, fpc, rnd, img, t=None):
+            if t is None:
+                return self.L.nrc_mc_renderer_render_path(self.h, n, cams, fpc, rnd, img)
+            return self.L.nrc_mc_renderer_render_path_timed(self.h, n, cams, t, fpc, rnd, img)
+        return _render_path(call, self.width, self.height, cameras, framesPerCamera, frameRandoms, out, times)
 
     def TileMask(self):
         """see NrcHpmRenderer.TileMask"""
@@ -1003,6 +1093,17 @@ class McHpmRenderer:
     def SetVolumeBricks(self, origins, bricks):
         """see NrcHpmRenderer.SetVolumeBricks"""
         _set_volume_bricks(self.L.nrc_mc_renderer_set_volume_bricks, self.h, origins, bricks)
+
+    def SetVolumeKeys(self, keys):
+        """see NrcHpmRenderer.SetVolumeKeys"""
+        _set_volume_keys(self.L.nrc_mc_renderer_set_volume_keys, self.h, keys)
+
+    def VolumeKeyCount(self):
+        return int(self.L.nrc_mc_renderer_volume_key_count(self.h))
+
+    def SetVolumeTime(self, t):
+        """see NrcHpmRenderer.SetVolumeTime"""
+        _check(self.L.nrc_mc_renderer_set_volume_time(self.h, C.c_float(float(t))))
 
     def VolumeBuffer(self, name):
         """see NrcHpmRenderer.VolumeBuffer"""

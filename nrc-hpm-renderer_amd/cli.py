@@ -23,6 +23,9 @@ NrcHpmRenderer.RenderPath call -- `--frames` frames per view, trained like the p
 With `--bricks` the sequence is held as brick lists instead: every file's 8^3 leaves are read over the union bbox with its minimum
 snapped down to multiples of 8 (io_vdb.read_vdb_bricks; no dense array per file on the host or the device) and the renderer steps
 through them with NrcHpmRenderer.SetVolumeBricks.  The run prints the device bytes held per file, dense against bricks.
+An animated fly-through (new): `--orbit N --vdb a b c --animate` uploads the files as volume keys (NrcHpmRenderer.SetVolumeKeys; key i
+at time i) and renders view v at time v * (n_keys - 1) / max(N - 1, 1) * `--time-scale` -- the medium in between two files is their
+linear in-between -- with one RenderPath(..., times=...) call.  A --time-scale below 1 is slow motion; times past the last key stay there.
 """
 import argparse
 import math
@@ -53,12 +56,33 @@ def check_orbit_args(args):
         raise SystemExit("SkyRenderer ERROR: --orbit needs --frames of at least 1 (frames per view)")
     if args.benchmark:
         raise SystemExit("SkyRenderer ERROR: --orbit and --benchmark exclude each other (the reference image belongs to one camera)")
-    if args.vdb and len(args.vdb) > 1:
+    if args.vdb and len(args.vdb) > 1 and not getattr(args, "animate", False):
         raise SystemExit("SkyRenderer ERROR: --orbit takes one volume, not a --vdb sequence")
     if args.gpus > 1 and args.export and "%" in args.export:
         raise SystemExit("SkyRenderer ERROR: one file per view (--export with %) is not available with --gpus")
     export_paths(args.export, args.orbit)
     return args.orbit
+
+
+def check_animate_args(args):
+    """what --animate needs (raises SystemExit); returns whether the run is an animated fly-through"""
+    if not getattr(args, "animate", False):
+        return False
+    if args.orbit is None or not (args.vdb and len(args.vdb) > 1):
+        raise SystemExit("SkyRenderer ERROR: --animate goes with --orbit and a --vdb sequence (several files: the keys)")
+    if getattr(args, "bricks", False):
+        raise SystemExit("SkyRenderer ERROR: --animate and --bricks exclude each other (volume keys are dense)")
+    scale = getattr(args, "time_scale", 1.0)
+    if not (math.isfinite(scale) and scale >= 0.0):
+        raise SystemExit("SkyRenderer ERROR: --time-scale must be a finite number, at least 0")
+    return True
+
+
+def animate_times(n_views, n_keys, time_scale=1.0):
+    """--animate: the time of every view into n_keys keys -- view v at v * (n_keys - 1) / max(n_views - 1, 1) * time_scale, clamped at the
+    last key (float32, what RenderPath takes)"""
+    last = float(n_keys - 1)
+    return np.array([min(v * last / max(n_views - 1, 1) * time_scale, last) for v in range(n_views)], np.float32)
 
 
 DEFAULT_ARGV = ["RelativeL2Luminance", "Adam", "0.01", "0.99", "0", "0", "64", "6", "21", "14", "4", "4", "1.0", "1", "1", "0.0", "32"]
@@ -85,6 +109,10 @@ def main(argv=None):
     ap.add_argument("--orbit", type=int, default=None, metavar="N",
                     help="render an N-view turntable around the volume with one RenderPath call (include/nrc_hpm.h, nrc_renderer_render_path): "
                          "--frames frames per view")
+    ap.add_argument("--animate", action="store_true",
+                    help="with --orbit and a --vdb sequence: the files are volume keys and the medium moves through them along the turntable "
+                         "(include/nrc_hpm.h, nrc_renderer_render_path_timed)")
+    ap.add_argument("--time-scale", type=float, default=1.0, help="--animate: the medium's speed (below 1: slow motion; times stop at the last key)")
     ap.add_argument("--orbit-radius", type=float, default=64.0)
     ap.add_argument("--orbit-height", type=float, default=0.0)
     ap.add_argument("--gpus", type=int, default=1, help="ranks the frame is sharded over (one GPU each)")
@@ -100,6 +128,7 @@ def main(argv=None):
         raise SystemExit("SkyRenderer ERROR: --bricks goes with a --vdb sequence (several files)")
     if args.frames_per_volume < 1:
         raise SystemExit("SkyRenderer ERROR: --frames-per-volume must be at least 1")
+    animate = check_animate_args(args)
     n_views = check_orbit_args(args)
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -168,7 +197,7 @@ def main(argv=None):
             nrc.SetCollectiveHooks(rank, world)      # (with the native communicator the gather / metric reduction use RCCL too)
     nrc_renderer = api.NrcHpmRenderer(lw, H, False, camera, cfg, scene, nrc, tile=tile)
     # a sequence: every volume uploaded once, swapped in on the device (every rank swaps the whole volume before the same frame)
-    seq_dev = [torch.from_numpy(np.ascontiguousarray(v)).cuda() for v in sequence] if len(sequence) > 1 else []
+    seq_dev = [torch.from_numpy(np.ascontiguousarray(v)).cuda() for v in sequence] if len(sequence) > 1 and not animate else []
     # --bricks: every file's list uploaded once (float32 bricks, quantised by the rebuild as the dense path quantises on the host)
     seq_bricks = [(torch.from_numpy(o).cuda(), torch.from_numpy(b).cuda()) for o, b in brick_lists]
     if seq_bricks and rank == 0:
@@ -208,7 +237,11 @@ def main(argv=None):
         # a turntable: every view's frames enqueued by one call that does not wait for the GPU; every rank makes the same call
         views = sc.orbit_cameras(n_views, args.orbit_radius, args.orbit_height, aspect=W / H)
         per_view = args.export is not None and "%" in args.export
-        images = nrc_renderer.RenderPath(views, args.frames, train=True, out=None if per_view else False)
+        times = None
+        if animate:      # the files are the keys (uploaded once, from the host), the views' times run through them
+            nrc_renderer.SetVolumeKeys(np.ascontiguousarray(np.stack(sequence)))
+            times = animate_times(n_views, len(sequence), args.time_scale)
+        images = nrc_renderer.RenderPath(views, args.frames, train=True, out=None if per_view else False, times=times)
         loss = nrc.GetLoss(wait=True)
         failed = (math.isnan(loss) or math.isinf(loss)) and not args.skip_nonfinite      # (the all-reduced loss: the same on every rank)
         if failed:

@@ -19,6 +19,7 @@
 #include <string>
 
 #include "nrc_math.h"
+#include "nrc_volume_keys.hpp"
 
 // 1: the tracking loops carry their predicates as uniform 64-bit lane masks (round 4); 0: as per-lane bools (round 3)
 // 1: every look-up tests the LDS occupancy bits unconditionally; 0 (product): behind a wave-uniform test for the table, as in round 3.
@@ -2045,6 +2046,64 @@ __global__ __launch_bounds__(256) void k_vol_ingest(const void* __restrict__ src
     if (t < 32u && cx < gx) cell_mask[((size_t)cz * gy + cy) * gx + cx] = lmask[t];
 }
 
+// NRC_VOLUME_F32 key volumes -> R8 at upload (nrc_renderer_set_volume_keys): the bytes k_vol_ingest<true, ...> would write, nothing else
+__global__ __launch_bounds__(256) void k_vol_quantize(const float* __restrict__ src, uint8_t* __restrict__ dst, size_t n)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    const size_t stride = (size_t)gridDim.x * 256u;
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += stride) dst[i] = (uint8_t)vol_quantize(src[i]);
+}
+
+// k_vol_ingest's decomposition and outputs with the voxels blended from two R8 keys (nrc_renderer_set_volume_time): voxel = lerp_voxel(a, b, W),
+// 0 < W < 256 (nrc_volume_keys.hpp; an end of the range is k_vol_ingest on one key).  Four bytes of each key per lane and row, blended as
+// two pairs of 16-bit fields; the touch masks follow the blended voxel, not the keys.  vec: nx % 4 == 0 and both keys 4-byte aligned.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_vol_ingest_lerp(const uint8_t* __restrict__ key_a, const uint8_t* __restrict__ key_b, uint32_t W,
+                                                        uint8_t* __restrict__ density, uint32_t* __restrict__ cell_mask, uint32_t nx, uint32_t ny,
+                                                        uint32_t nz, uint32_t gx, uint32_t gy, uint32_t n_chunks)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    __shared__ uint32_t lmask[32];
+    const uint32_t t = threadIdx.x;
+    if (t < 32u) lmask[t] = 0u;
+    __syncthreads();
+    const uint32_t chunk = blockIdx.x % n_chunks, crow = blockIdx.x / n_chunks;
+    const uint32_t cy = crow % gy, cz = crow / gy;
+    const uint32_t x = chunk * 256u + 4u * (t & 63u);
+    uint32_t m = 0u;
+    if (x < nx) {
+        uint32_t xs_q[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) xs_q[k] = x + k < nx ? vol_axis_set(x + k, nx) : 0u;
+        for (uint32_t r = t >> 6; r < 64u; r += 4u) {
+            const uint32_t y = cy * 8u + (r & 7u), z = cz * 8u + (r >> 3);
+            if (y >= ny || z >= nz) continue;
+            const size_t idx = ((size_t)z * ny + y) * nx + x;
+            uint32_t q[4];
+            if (VEC) {
+                const uint32_t w = lerp_voxels4(*(const uint32_t*)(key_a + idx), *(const uint32_t*)(key_b + idx), W);
+                *(uint32_t*)(density + idx) = w;
+                q[0] = w & 255u; q[1] = (w >> 8) & 255u; q[2] = (w >> 16) & 255u; q[3] = w >> 24;
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; k++) {
+                    q[k] = 0u;
+                    if (x + k < nx) {
+                        q[k] = lerp_voxel(key_a[idx + k], key_b[idx + k], W);
+                        density[idx + k] = (uint8_t)q[k];
+                    }
+                }
+            }
+            const uint32_t xs = (q[0] ? xs_q[0] : 0u) | (q[1] ? xs_q[1] : 0u) | (q[2] ? xs_q[2] : 0u) | (q[3] ? xs_q[3] : 0u);
+            if (xs) m |= vol_touch_mask(xs, vol_axis_set(y, ny), vol_axis_set(z, nz));
+        }
+    }
+    if (m) atomicOr(&lmask[(t & 63u) >> 1], m);
+    __syncthreads();
+    const uint32_t cx = chunk * 32u + t;
+    if (t < 32u && cx < gx) cell_mask[((size_t)cz * gy + cy) * gx + cx] = lmask[t];
+}
+
 // Blocks [0, n_cell_blocks): one lane per 8^3 cell -- occupied (build_occupancy's dilation) when a neighbour's touch mask, or its own,
 // names it.  Blocks from n_cell_blocks on: one lane per bit of the exact occupancy table (cells of 2^occ_shift voxels, occ_shift >= 3:
 // the OR of the own-cell bits of the 8^3 cells inside), a 64-bit ballot per wave = two whole words (occ_words is a multiple of four).
@@ -2361,6 +2420,29 @@ void launch_volume_rebuild(const void* src, int format, const VolumeRebuild& v, 
     auto ingest = format == NRC_VOLUME_F32 ? (vec ? k_vol_ingest<true, true> : k_vol_ingest<true, false>)
                                            : (vec ? k_vol_ingest<false, true> : k_vol_ingest<false, false>);
     hipLaunchKernelGGL(ingest, grid, dim3(256), 0, s, src, v.density, cell_mask, v.nx, v.ny, v.nz, gx, gy, n_chunks);
+    NRC_HIP(hipGetLastError());
+    launch_volume_cells_rows(v, scratch, s);
+}
+
+void launch_volume_quantize(const float* src, uint8_t* dst, size_t n, hipStream_t s)
+{
+    if (n == 0) return;
+    const size_t blocks = std::min<size_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_vol_quantize, dim3((uint32_t)blocks), dim3(256), 0, s, src, dst, n);
+    NRC_HIP(hipGetLastError());
+}
+
+void launch_volume_rebuild_lerp(const uint8_t* key_a, const uint8_t* key_b, uint32_t W, const VolumeRebuild& v, void* scratch, hipStream_t s)
+{
+    if (W == 0u || W >= 256u) {      // one key as it is (key_b may be null at W == 0: the last key has no successor)
+        launch_volume_rebuild(W == 0u ? key_a : key_b, NRC_VOLUME_U8, v, scratch, s);
+        return;
+    }
+    const uint32_t gx = ceil_div(v.nx, 8), gy = ceil_div(v.ny, 8), gz = ceil_div(v.nz, 8);
+    const uint32_t n_chunks = ceil_div(gx, 32);
+    const bool vec = v.nx % 4 == 0 && (uintptr_t)key_a % 4 == 0 && (uintptr_t)key_b % 4 == 0;
+    hipLaunchKernelGGL(vec ? k_vol_ingest_lerp<true> : k_vol_ingest_lerp<false>, dim3(n_chunks * gy * gz), dim3(256), 0, s, key_a, key_b, W, v.density,
+                       (uint32_t*)scratch, v.nx, v.ny, v.nz, gx, gy, n_chunks);
     NRC_HIP(hipGetLastError());
     launch_volume_cells_rows(v, scratch, s);
 }

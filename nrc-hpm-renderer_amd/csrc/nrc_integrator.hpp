@@ -139,6 +139,12 @@ void launch_volume_rebuild(const void* src, int format, const VolumeRebuild& v, 
 size_t volume_brick_index_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
 void launch_volume_rebuild_bricks(const int32_t* origins, const void* bricks, uint32_t n_bricks, int format, const VolumeRebuild& v, void* scratch,
                                   uint32_t* brick_index, hipStream_t s);
+// n NRC_VOLUME_F32 voxels -> R8, the quantisation of launch_volume_rebuild (key volumes are kept as R8: nrc_renderer_set_volume_keys)
+void launch_volume_quantize(const float* src, uint8_t* dst, size_t n, hipStream_t s);
+// the same from two R8 key volumes in device memory (nrc_renderer_set_volume_time): every voxel lerp_voxel(a, b, W) of nrc_volume_keys.hpp,
+// 0 <= W <= 256 -- the result is what launch_volume_rebuild makes of that in-between volume, bit for bit.  W == 0 reads key_a alone (key_b
+// may be null), W == 256 key_b alone.  Three launches; both keys must stay unchanged until they have run.
+void launch_volume_rebuild_lerp(const uint8_t* key_a, const uint8_t* key_b, uint32_t W, const VolumeRebuild& v, void* scratch, hipStream_t s);
 // table[m] = optical distance covered by the 128 free flights a delta walk draws from RNG state m when it rejects every collision
 constexpr uint32_t kFlightStates = 1u << 23;
 void launch_flight_table(float* table, hipStream_t s);

@@ -137,6 +137,40 @@ def bricks_to_volume(origins, bricks, dims, ignore_invalid=False):
     return vol
 
 
+def key_of_time(t, n_keys):
+    """Volume keyframes (include/nrc_hpm.h, nrc_renderer_set_volume_keys): key i sits at time i.  Returns (i, W) of time t -- the in-between
+    is made of keys i and i + 1 with weight W / 256 on the latter -- with the library's fp32 roundings: i = min(int(t), n_keys - 1),
+    w = t - i, W = int(w * 256 + 0.5), so 0 <= W <= 256 and W = 0 at the last key.  ValueError unless t (as fp32) is finite and inside
+    [0, n_keys - 1]."""
+    n_keys = int(n_keys)
+    t32 = np.float32(t)
+    if n_keys < 1 or not np.isfinite(t32) or t32 < np.float32(0.0) or t32 > np.float32(n_keys - 1):
+        raise ValueError("key_of_time: time %r is not inside [0, %d] (%d keys)" % (t, n_keys - 1, n_keys))
+    i = min(int(t32), n_keys - 1)
+    w = np.float32(t32 - np.float32(i))
+    return i, int(np.float32(np.float32(w * np.float32(256.0)) + np.float32(0.5)))
+
+
+def lerp_volume(a, b, W):
+    """The in-between of two uint8 volumes, in integers: (a * (256 - W) + b * W + 128) >> 8 per voxel, 0 <= W <= 256 (0: a, 256: b)."""
+    W = int(W)
+    if not 0 <= W <= 256:
+        raise ValueError("lerp_volume: W must be inside [0, 256] (got %d)" % W)
+    a, b = np.asarray(a), np.asarray(b)
+    if a.dtype != np.uint8 or b.dtype != np.uint8 or a.shape != b.shape:
+        raise ValueError("lerp_volume: two uint8 arrays of one shape (got %s %s and %s %s)" % (a.dtype, a.shape, b.dtype, b.shape))
+    return ((a.astype(np.uint32) * np.uint32(256 - W) + b.astype(np.uint32) * np.uint32(W) + np.uint32(128)) >> np.uint32(8)).astype(np.uint8)
+
+
+def volume_at(keys, t):
+    """The CPU statement of SetVolumeTime: the uint8 volume at time t of the key sequence keys[n_keys][nz][ny][nx] (uint8)."""
+    keys = np.asarray(keys)
+    if keys.ndim != 4 or keys.dtype != np.uint8:
+        raise ValueError("volume_at: keys uint8 [n_keys][nz][ny][nx] (got %s %s)" % (keys.dtype, keys.shape))
+    i, W = key_of_time(t, keys.shape[0])
+    return np.ascontiguousarray(keys[i]) if W == 0 else lerp_volume(keys[i], keys[i + 1], W)
+
+
 def white_env(value=1.0):
     """Quirk Q9 (src/read_file.cpp:129-130): every loaded env texel is overwritten with 1.0."""
     return np.full((1, 1, 4), value, np.float32)
