@@ -1415,22 +1415,14 @@ __device__ __forceinline__ void tile_mask_box(const float* __restrict__ boxes, u
         }
 }
 
-__global__ __launch_bounds__(256) void k_tile_mask(const float* __restrict__ boxes, uint32_t n_boxes, DevProjView pv, DevFrame fr,
-                                                  uint32_t* __restrict__ mask)
+// n = *n_dev when the count lives in device memory (a volume rebuilt on the device, k_vol_rows; the grid covers the capacity), else n_host
+__global__ __launch_bounds__(256) void k_tile_mask(const float* __restrict__ boxes, uint32_t n_host, const uint32_t* __restrict__ n_dev, DevProjView pv,
+                                                  DevFrame fr, uint32_t* __restrict__ mask)
 {
     NRC_RAISE_WAVE_PRIORITY(16);
+    const uint32_t n = n_dev != nullptr ? *n_dev : n_host;
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_boxes) return;
-    tile_mask_box(boxes, i, pv, fr, mask);
-}
-
-// the same with the box count in device memory (a volume rebuilt on the device, k_vol_rows): the grid covers the box capacity
-__global__ __launch_bounds__(256) void k_tile_mask_dev(const float* __restrict__ boxes, const uint32_t* __restrict__ n_boxes, DevProjView pv,
-                                                      DevFrame fr, uint32_t* __restrict__ mask)
-{
-    NRC_RAISE_WAVE_PRIORITY(16);
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= *n_boxes) return;
+    if (i >= n) return;
     tile_mask_box(boxes, i, pv, fr, mask);
 }
 
@@ -1442,7 +1434,6 @@ __global__ __launch_bounds__(256) void k_tile_mask_dev(const float* __restrict__
 // once, by a plain store: no atomics, and the buffer needs no clear.
 constexpr uint32_t kTileRectChunk = 1024u;
 
-// n = *n_dev when the count lives in device memory (a volume rebuilt on the device; the grid covers the capacity), else n_host
 __global__ __launch_bounds__(256) void k_tile_rects(const float* __restrict__ boxes, uint32_t n_host, const uint32_t* __restrict__ n_dev, DevProjView pv,
                                                    DevFrame fr, unsigned long long* __restrict__ rects)
 {
@@ -1992,23 +1983,143 @@ __device__ __forceinline__ uint32_t vol_quantize(float v)
     return (uint32_t)(v * 255.0f);
 }
 
+// ---- voxel sources of k_vol_ingest: where a lane's four voxels come from, nothing else.  fetch<VEC>() fills q[k] with the quantised voxels
+// x + k of one voxel row (idx: the first one's element in the volume, r = 8 * dz + dy: the row inside the lane's cell).  VEC (nx % 4 == 0
+// and the source readable four elements at a time): returns the four as the word the kernel stores.  Otherwise no voxel of the volume
+// with x + k >= nx is read (q[k] = 0) and the source stores the others itself through vol_scalar4.  stage(): lane t < 32 in front of the
+// workgroup's barrier, for the workgroup's cell t (`in`: it exists); lane(): a lane's own state behind the barrier.
+struct VolNoLane {};
+__device__ __forceinline__ void vol_unpack4(uint32_t w, uint32_t q[4])
+{
+    q[0] = w & 255u; q[1] = (w >> 8) & 255u; q[2] = (w >> 16) & 255u; q[3] = w >> 24;
+}
+__device__ __forceinline__ uint32_t vol_pack4(const uint32_t q[4]) { return q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24); }
+// the scalar path: voxel k = one(k) is read and stored only inside the volume (the load and its store under one guard: docs/MEASUREMENT_LOG.md)
+template <typename One>
+__device__ __forceinline__ uint32_t vol_scalar4(One one, uint32_t x, uint32_t nx, uint32_t q[4], uint8_t* __restrict__ row)
+{
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) {
+        q[k] = 0u;
+        if (x + k < nx) {
+            q[k] = one(k);
+            row[k] = (uint8_t)q[k];
+        }
+    }
+    return 0u;
+}
+
+// a dense volume (nrc_renderer_set_volume): element idx + k.  VEC: src aligned to 4 elements (one 4- / 16-byte load per lane and row)
+template <bool F32>
+struct VolDense {
+    const void* src;
+    __device__ __forceinline__ void stage(uint32_t, size_t, bool) const {}
+    __device__ __forceinline__ VolNoLane lane(uint32_t) const { return {}; }
+    template <bool VEC>
+    __device__ __forceinline__ uint32_t fetch(VolNoLane, size_t idx, uint32_t, uint32_t x, uint32_t nx, uint32_t q[4], uint8_t* __restrict__ density) const
+    {
+        if (!VEC)
+            return vol_scalar4([&](uint32_t k) { return F32 ? vol_quantize(((const float*)src)[idx + k]) : (uint32_t)((const uint8_t*)src)[idx + k]; },
+                               x, nx, q, density + idx);
+        if (F32) {
+            const float4 f = *(const float4*)((const float*)src + idx);
+            q[0] = vol_quantize(f.x); q[1] = vol_quantize(f.y); q[2] = vol_quantize(f.z); q[3] = vol_quantize(f.w);
+        } else vol_unpack4(*(const uint32_t*)((const uint8_t*)src + idx), q);
+        return vol_pack4(q);
+    }
+};
+
+// two R8 keys blended (nrc_renderer_set_volume_time): voxel = lerp_voxel(a, b, W), 0 < W < 256 (nrc_volume_keys.hpp; an end of the range is
+// VolDense on one key).  VEC: both keys 4-byte aligned -- four bytes of each key per lane and row, blended as two pairs of 16-bit fields.
+// The touch masks follow the blended voxel, not the keys.
+struct VolLerp {
+    const uint8_t *key_a, *key_b;
+    uint32_t W;
+    __device__ __forceinline__ void stage(uint32_t, size_t, bool) const {}
+    __device__ __forceinline__ VolNoLane lane(uint32_t) const { return {}; }
+    template <bool VEC>
+    __device__ __forceinline__ uint32_t fetch(VolNoLane, size_t idx, uint32_t, uint32_t x, uint32_t nx, uint32_t q[4], uint8_t* __restrict__ density) const
+    {
+        if (!VEC) return vol_scalar4([&](uint32_t k) { return lerp_voxel(key_a[idx + k], key_b[idx + k], W); }, x, nx, q, density + idx);
+        const uint32_t w = lerp_voxels4(*(const uint32_t*)(key_a + idx), *(const uint32_t*)(key_b + idx), W);
+        vol_unpack4(w, q);
+        return w;
+    }
+};
+
+// the 8^3 bricks k_vol_brick_index named (nrc_renderer_set_volume_bricks; cell_brick[cell] = 1 + the brick, 0 = none): element
+// 64 * dz + 8 * dy + dx of brick b, a lane's four are half a brick row (one 4- / 16-byte load when `aligned`: the brick base is aligned to 4
+// elements, whatever nx is).  Voxels of a cell without a brick are 0: every voxel of the volume is written, nothing of the density's old
+// contents is read or kept.  A brick voxel past the volume's edge is read and ignored.
+template <bool F32>
+struct VolBricks {
+    const void* bricks;
+    const uint32_t* cell_brick;
+    uint32_t aligned;
+    struct Lane { uint32_t b; size_t base; };
+    // the brick ids of the workgroup's 32 cells: a function-local __shared__ has static storage, so stage() and lane() see one LDS array
+    // per kernel instantiation (128 of its 256 bytes)
+    static __device__ __forceinline__ uint32_t* lbrick() { __shared__ uint32_t l[32]; return l; }
+    __device__ __forceinline__ void stage(uint32_t t, size_t cell, bool in) const { lbrick()[t] = in ? cell_brick[cell] : 0u; }
+    __device__ __forceinline__ Lane lane(uint32_t t) const
+    {
+        const uint32_t b = lbrick()[(t & 63u) >> 1];
+        return {b, b ? (size_t)(b - 1u) * 512u + 4u * (t & 1u) : 0u};
+    }
+    template <bool VEC>
+    __device__ __forceinline__ uint32_t fetch(const Lane& ln, size_t idx, uint32_t r, uint32_t x, uint32_t nx, uint32_t q[4], uint8_t* __restrict__ density) const
+    {
+        uint32_t b[4] = {0u, 0u, 0u, 0u};
+        if (ln.b) fetch_brick(ln.base + 8u * r, b);      // 64 * dz + 8 * dy: r = 8 * dz + dy
+        if (!VEC) return vol_scalar4([&](uint32_t k) { return b[k]; }, x, nx, q, density + idx);
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) q[k] = b[k];
+        return vol_pack4(q);
+    }
+    __device__ __forceinline__ void fetch_brick(size_t e, uint32_t q[4]) const
+    {
+        if (F32) {
+            float f[4];
+            if (aligned) {
+                const float4 v = *(const float4*)((const float*)bricks + e);
+                f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; k++) f[k] = ((const float*)bricks)[e + k];
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) q[k] = vol_quantize(f[k]);
+        } else if (aligned) vol_unpack4(*(const uint32_t*)((const uint8_t*)bricks + e), q);
+        else {
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) q[k] = (uint32_t)((const uint8_t*)bricks)[e + k];
+        }
+    }
+};
+
 // One workgroup per (32 cells along x) x (one 8x8 row of cells in y, z): 256 lanes, a lane owns four consecutive voxels of x (in one
 // cell) in 16 of the 64 voxel rows.  Writes the density and every cell's 27-bit touch mask (the workgroup owns its cells: no global atomics).
-// vec: nx % 4 == 0 and the source aligned to 4 elements (one 4- / 16-byte load per lane and row).
-template <bool F32, bool VEC>
-__global__ __launch_bounds__(256) void k_vol_ingest(const void* __restrict__ src, uint8_t* __restrict__ density, uint32_t* __restrict__ cell_mask,
-                                                   uint32_t nx, uint32_t ny, uint32_t nz, uint32_t gx, uint32_t gy, uint32_t n_chunks)
+// VEC: nx % 4 == 0 and what the source asks for (one 4-byte store per lane and row; otherwise the source stores, vol_scalar4).
+template <typename Src, bool VEC>
+__global__ __launch_bounds__(256) void k_vol_ingest(Src src, uint8_t* __restrict__ density, uint32_t* __restrict__ cell_mask, uint32_t nx, uint32_t ny,
+                                                   uint32_t nz, uint32_t gx, uint32_t gy, uint32_t n_chunks)
 {
     NRC_RAISE_WAVE_PRIORITY(16);
     __shared__ uint32_t lmask[32];
     const uint32_t t = threadIdx.x;
-    if (t < 32u) lmask[t] = 0u;
-    __syncthreads();
     const uint32_t chunk = blockIdx.x % n_chunks, crow = blockIdx.x / n_chunks;
     const uint32_t cy = crow % gy, cz = crow / gy;
+    const uint32_t cx = chunk * 32u + t;      // (t < 32: the workgroup's cells)
+    const size_t cell = ((size_t)cz * gy + cy) * gx + cx;
+    if (t < 32u) {
+        lmask[t] = 0u;
+        src.stage(t, cell, cx < gx);
+    }
+    __syncthreads();
     const uint32_t x = chunk * 256u + 4u * (t & 63u);
     uint32_t m = 0u;
     if (x < nx) {
+        const auto ln = src.lane(t);
         uint32_t xs_q[4];
 #pragma unroll
         for (uint32_t k = 0; k < 4u; k++) xs_q[k] = x + k < nx ? vol_axis_set(x + k, nx) : 0u;
@@ -2017,91 +2128,23 @@ __global__ __launch_bounds__(256) void k_vol_ingest(const void* __restrict__ src
             if (y >= ny || z >= nz) continue;
             const size_t idx = ((size_t)z * ny + y) * nx + x;
             uint32_t q[4];
-            if (VEC) {
-                if (F32) {
-                    const float4 f = *(const float4*)((const float*)src + idx);
-                    q[0] = vol_quantize(f.x); q[1] = vol_quantize(f.y); q[2] = vol_quantize(f.z); q[3] = vol_quantize(f.w);
-                } else {
-                    const uint32_t w = *(const uint32_t*)((const uint8_t*)src + idx);
-                    q[0] = w & 255u; q[1] = (w >> 8) & 255u; q[2] = (w >> 16) & 255u; q[3] = w >> 24;
-                }
-                *(uint32_t*)(density + idx) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
-            } else {
-#pragma unroll
-                for (uint32_t k = 0; k < 4u; k++) {
-                    q[k] = 0u;
-                    if (x + k < nx) {
-                        q[k] = F32 ? vol_quantize(((const float*)src)[idx + k]) : (uint32_t)((const uint8_t*)src)[idx + k];
-                        density[idx + k] = (uint8_t)q[k];
-                    }
-                }
-            }
+            const uint32_t w = src.template fetch<VEC>(ln, idx, r, x, nx, q, density);
+            if (VEC) *(uint32_t*)(density + idx) = w;
             const uint32_t xs = (q[0] ? xs_q[0] : 0u) | (q[1] ? xs_q[1] : 0u) | (q[2] ? xs_q[2] : 0u) | (q[3] ? xs_q[3] : 0u);
             if (xs) m |= vol_touch_mask(xs, vol_axis_set(y, ny), vol_axis_set(z, nz));
         }
     }
     if (m) atomicOr(&lmask[(t & 63u) >> 1], m);
     __syncthreads();
-    const uint32_t cx = chunk * 32u + t;
-    if (t < 32u && cx < gx) cell_mask[((size_t)cz * gy + cy) * gx + cx] = lmask[t];
+    if (t < 32u && cx < gx) cell_mask[cell] = lmask[t];
 }
 
-// NRC_VOLUME_F32 key volumes -> R8 at upload (nrc_renderer_set_volume_keys): the bytes k_vol_ingest<true, ...> would write, nothing else
+// NRC_VOLUME_F32 key volumes -> R8 at upload (nrc_renderer_set_volume_keys): the bytes k_vol_ingest<VolDense<true>, ...> would write, nothing else
 __global__ __launch_bounds__(256) void k_vol_quantize(const float* __restrict__ src, uint8_t* __restrict__ dst, size_t n)
 {
     NRC_RAISE_WAVE_PRIORITY(16);
     const size_t stride = (size_t)gridDim.x * 256u;
     for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += stride) dst[i] = (uint8_t)vol_quantize(src[i]);
-}
-
-// k_vol_ingest's decomposition and outputs with the voxels blended from two R8 keys (nrc_renderer_set_volume_time): voxel = lerp_voxel(a, b, W),
-// 0 < W < 256 (nrc_volume_keys.hpp; an end of the range is k_vol_ingest on one key).  Four bytes of each key per lane and row, blended as
-// two pairs of 16-bit fields; the touch masks follow the blended voxel, not the keys.  vec: nx % 4 == 0 and both keys 4-byte aligned.
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_vol_ingest_lerp(const uint8_t* __restrict__ key_a, const uint8_t* __restrict__ key_b, uint32_t W,
-                                                        uint8_t* __restrict__ density, uint32_t* __restrict__ cell_mask, uint32_t nx, uint32_t ny,
-                                                        uint32_t nz, uint32_t gx, uint32_t gy, uint32_t n_chunks)
-{
-    NRC_RAISE_WAVE_PRIORITY(16);
-    __shared__ uint32_t lmask[32];
-    const uint32_t t = threadIdx.x;
-    if (t < 32u) lmask[t] = 0u;
-    __syncthreads();
-    const uint32_t chunk = blockIdx.x % n_chunks, crow = blockIdx.x / n_chunks;
-    const uint32_t cy = crow % gy, cz = crow / gy;
-    const uint32_t x = chunk * 256u + 4u * (t & 63u);
-    uint32_t m = 0u;
-    if (x < nx) {
-        uint32_t xs_q[4];
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; k++) xs_q[k] = x + k < nx ? vol_axis_set(x + k, nx) : 0u;
-        for (uint32_t r = t >> 6; r < 64u; r += 4u) {
-            const uint32_t y = cy * 8u + (r & 7u), z = cz * 8u + (r >> 3);
-            if (y >= ny || z >= nz) continue;
-            const size_t idx = ((size_t)z * ny + y) * nx + x;
-            uint32_t q[4];
-            if (VEC) {
-                const uint32_t w = lerp_voxels4(*(const uint32_t*)(key_a + idx), *(const uint32_t*)(key_b + idx), W);
-                *(uint32_t*)(density + idx) = w;
-                q[0] = w & 255u; q[1] = (w >> 8) & 255u; q[2] = (w >> 16) & 255u; q[3] = w >> 24;
-            } else {
-#pragma unroll
-                for (uint32_t k = 0; k < 4u; k++) {
-                    q[k] = 0u;
-                    if (x + k < nx) {
-                        q[k] = lerp_voxel(key_a[idx + k], key_b[idx + k], W);
-                        density[idx + k] = (uint8_t)q[k];
-                    }
-                }
-            }
-            const uint32_t xs = (q[0] ? xs_q[0] : 0u) | (q[1] ? xs_q[1] : 0u) | (q[2] ? xs_q[2] : 0u) | (q[3] ? xs_q[3] : 0u);
-            if (xs) m |= vol_touch_mask(xs, vol_axis_set(y, ny), vol_axis_set(z, nz));
-        }
-    }
-    if (m) atomicOr(&lmask[(t & 63u) >> 1], m);
-    __syncthreads();
-    const uint32_t cx = chunk * 32u + t;
-    if (t < 32u && cx < gx) cell_mask[((size_t)cz * gy + cy) * gx + cx] = lmask[t];
 }
 
 // Blocks [0, n_cell_blocks): one lane per 8^3 cell -- occupied (build_occupancy's dilation) when a neighbour's touch mask, or its own,
@@ -2229,8 +2272,8 @@ __global__ __launch_bounds__(1024) void k_vol_rows(const uint8_t* __restrict__ c
     if (t == 0u) *n_boxes = base;
 }
 
-// ---- the same rebuild from a list of 8^3 bricks (nrc_renderer_set_volume_bricks): k_vol_brick_index + k_vol_ingest_bricks take
-// k_vol_ingest's place, k_vol_cells and k_vol_rows run behind them unchanged.
+// ---- the same rebuild from a list of 8^3 bricks (nrc_renderer_set_volume_bricks): k_vol_brick_index runs in front of k_vol_ingest, whose
+// VolBricks source reads what it wrote; k_vol_cells and k_vol_rows run behind them unchanged.
 //
 // One lane per brick: cell_brick[cell] = 1 + the highest index of the bricks that name the cell (cleared to 0 = none by the caller).
 // atomicMax on integers: which brick wins does not depend on the order the lanes run in.  An origin that is not a multiple of 8 or
@@ -2245,79 +2288,6 @@ __global__ __launch_bounds__(256) void k_vol_brick_index(const int32_t* __restri
     if ((x0 | y0 | z0) < 0 || ((x0 | y0 | z0) & 7) != 0) return;
     if ((uint32_t)x0 >= nx || (uint32_t)y0 >= ny || (uint32_t)z0 >= nz) return;
     atomicMax(&cell_brick[((size_t)((uint32_t)z0 >> 3) * gy + ((uint32_t)y0 >> 3)) * gx + ((uint32_t)x0 >> 3)], i + 1u);
-}
-
-// k_vol_ingest's decomposition -- one workgroup per (32 cells along x) x (one cell row), a lane owns four consecutive voxels of x in 16
-// of the 64 voxel rows -- with the voxels fetched from the bricks k_vol_brick_index named: element 64 * dz + 8 * dy + dx of brick b,
-// a lane's four are half a brick row (one 4- / 16-byte load when `aligned`: the brick base is aligned to 4 elements).  Every voxel of
-// the volume is written exactly once, zeros where no brick covers it: nothing of the density's old contents is read or kept.
-// vec: nx % 4 == 0 (one 4-byte store per lane and row).
-template <bool F32, bool VEC>
-__global__ __launch_bounds__(256) void k_vol_ingest_bricks(const void* __restrict__ bricks, const uint32_t* __restrict__ cell_brick,
-                                                          uint8_t* __restrict__ density, uint32_t* __restrict__ cell_mask, uint32_t nx, uint32_t ny,
-                                                          uint32_t nz, uint32_t gx, uint32_t gy, uint32_t n_chunks, uint32_t aligned)
-{
-    NRC_RAISE_WAVE_PRIORITY(16);
-    __shared__ uint32_t lmask[32];
-    __shared__ uint32_t lbrick[32];
-    const uint32_t t = threadIdx.x;
-    const uint32_t chunk = blockIdx.x % n_chunks, crow = blockIdx.x / n_chunks;
-    const uint32_t cy = crow % gy, cz = crow / gy;
-    if (t < 32u) {
-        const uint32_t cx = chunk * 32u + t;
-        lmask[t] = 0u;
-        lbrick[t] = cx < gx ? cell_brick[((size_t)cz * gy + cy) * gx + cx] : 0u;
-    }
-    __syncthreads();
-    const uint32_t x = chunk * 256u + 4u * (t & 63u);
-    uint32_t m = 0u;
-    if (x < nx) {
-        const uint32_t b = lbrick[(t & 63u) >> 1];
-        const size_t base = b ? (size_t)(b - 1u) * 512u + 4u * (t & 1u) : 0u;
-        uint32_t xs_q[4];
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; k++) xs_q[k] = x + k < nx ? vol_axis_set(x + k, nx) : 0u;
-        for (uint32_t r = t >> 6; r < 64u; r += 4u) {
-            const uint32_t y = cy * 8u + (r & 7u), z = cz * 8u + (r >> 3);
-            if (y >= ny || z >= nz) continue;
-            uint32_t q[4] = {0u, 0u, 0u, 0u};
-            if (b) {
-                const size_t e = base + 8u * r;      // 64 * dz + 8 * dy: r = 8 * dz + dy
-                if (F32) {
-                    float f[4];
-                    if (aligned) {
-                        const float4 v = *(const float4*)((const float*)bricks + e);
-                        f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-                    } else {
-#pragma unroll
-                        for (uint32_t k = 0; k < 4u; k++) f[k] = ((const float*)bricks)[e + k];
-                    }
-#pragma unroll
-                    for (uint32_t k = 0; k < 4u; k++) q[k] = vol_quantize(f[k]);
-                } else if (aligned) {
-                    const uint32_t w = *(const uint32_t*)((const uint8_t*)bricks + e);
-                    q[0] = w & 255u; q[1] = (w >> 8) & 255u; q[2] = (w >> 16) & 255u; q[3] = w >> 24;
-                } else {
-#pragma unroll
-                    for (uint32_t k = 0; k < 4u; k++) q[k] = (uint32_t)((const uint8_t*)bricks)[e + k];
-                }
-            }
-            const size_t idx = ((size_t)z * ny + y) * nx + x;
-            if (VEC) *(uint32_t*)(density + idx) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
-            else {
-#pragma unroll
-                for (uint32_t k = 0; k < 4u; k++) {
-                    if (x + k < nx) density[idx + k] = (uint8_t)q[k];      // (a brick voxel past the volume's edge is ignored: xs_q 0)
-                }
-            }
-            const uint32_t xs = (q[0] ? xs_q[0] : 0u) | (q[1] ? xs_q[1] : 0u) | (q[2] ? xs_q[2] : 0u) | (q[3] ? xs_q[3] : 0u);
-            if (xs) m |= vol_touch_mask(xs, vol_axis_set(y, ny), vol_axis_set(z, nz));
-        }
-    }
-    if (m) atomicOr(&lmask[(t & 63u) >> 1], m);
-    __syncthreads();
-    const uint32_t cx = chunk * 32u + t;
-    if (t < 32u && cx < gx) cell_mask[((size_t)cz * gy + cy) * gx + cx] = lmask[t];
 }
 
 }  // namespace
@@ -2366,33 +2336,22 @@ void launch_tile_order(const uint32_t* cost, uint32_t n_slots, uint32_t* order, 
 
 uint32_t tile_mask_words(uint32_t w, uint32_t h) { return (ceil_div(w, 8) * ceil_div(h, 8) + 31u) / 32u + 1u; }
 
-void launch_tile_mask(const float* boxes, uint32_t n_boxes, const DevProjView& pv, const DevFrame& fr, uint32_t* mask, hipStream_t s)
+void launch_tile_mask(const BoxList& b, const DevProjView& pv, const DevFrame& fr, uint32_t* mask, hipStream_t s)
 {
     NRC_HIP(hipMemsetAsync(mask, 0, (size_t)tile_mask_words(fr.w, fr.h) * 4, s));
-    if (n_boxes == 0) return;
-    hipLaunchKernelGGL(k_tile_mask, dim3(ceil_div(n_boxes, 256)), dim3(256), 0, s, boxes, n_boxes, pv, fr, mask);
+    if (b.grid == 0) return;
+    hipLaunchKernelGGL(k_tile_mask, dim3(ceil_div(b.grid, 256)), dim3(256), 0, s, b.boxes, b.n_host, b.n_dev, pv, fr, mask);
     NRC_HIP(hipGetLastError());
 }
 
-void launch_tile_mask_dev(const float* boxes, const uint32_t* n_boxes, uint32_t capacity, const DevProjView& pv, const DevFrame& fr, uint32_t* mask,
-                         hipStream_t s)
+void launch_tile_mask_tiles(const BoxList& b, const DevProjView& pv, const DevFrame& fr, void* rects, uint32_t* mask, hipStream_t s)
 {
-    NRC_HIP(hipMemsetAsync(mask, 0, (size_t)tile_mask_words(fr.w, fr.h) * 4, s));
-    if (capacity == 0) return;
-    hipLaunchKernelGGL(k_tile_mask_dev, dim3(ceil_div(capacity, 256)), dim3(256), 0, s, boxes, n_boxes, pv, fr, mask);
-    NRC_HIP(hipGetLastError());
-}
-
-void launch_tile_mask_tiles(const float* boxes, uint32_t n_boxes, const uint32_t* n_boxes_dev, uint32_t capacity, const DevProjView& pv,
-                            const DevFrame& fr, void* rects, uint32_t* mask, hipStream_t s)
-{
-    const uint32_t grid_boxes = n_boxes_dev != nullptr ? capacity : n_boxes;      // (no box: k_tile_mask_words alone writes an all-clear mask)
-    if (grid_boxes > 0) {
-        hipLaunchKernelGGL(k_tile_rects, dim3(ceil_div(grid_boxes, 256)), dim3(256), 0, s, boxes, n_boxes, n_boxes_dev, pv, fr, (unsigned long long*)rects);
+    if (b.grid > 0) {      // (no box: k_tile_mask_words alone writes an all-clear mask)
+        hipLaunchKernelGGL(k_tile_rects, dim3(ceil_div(b.grid, 256)), dim3(256), 0, s, b.boxes, b.n_host, b.n_dev, pv, fr, (unsigned long long*)rects);
         NRC_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_tile_mask_words, dim3(ceil_div(tile_mask_words(fr.w, fr.h), 4)), dim3(256), 0, s, (const unsigned long long*)rects,
-                       grid_boxes > 0 ? n_boxes : 0u, grid_boxes > 0 ? n_boxes_dev : nullptr, fr, mask);
+                       b.grid > 0 ? b.n_host : 0u, b.grid > 0 ? b.n_dev : nullptr, fr, mask);
     NRC_HIP(hipGetLastError());
 }
 
@@ -2409,19 +2368,23 @@ size_t volume_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t nz)
 
 static void launch_volume_cells_rows(const VolumeRebuild& v, void* scratch, hipStream_t s);
 
-void launch_volume_rebuild(const void* src, int format, const VolumeRebuild& v, void* scratch, hipStream_t s)
+// the rebuild's three launches from a voxel source; vec: nx % 4 == 0 and the source's own condition (k_vol_ingest)
+template <typename Src>
+static void launch_volume_ingest(const Src& src, bool vec, const VolumeRebuild& v, void* scratch, hipStream_t s)
 {
     const uint32_t gx = ceil_div(v.nx, 8), gy = ceil_div(v.ny, 8), gz = ceil_div(v.nz, 8);
-    uint32_t* cell_mask = (uint32_t*)scratch;
     const uint32_t n_chunks = ceil_div(gx, 32);
-    const dim3 grid(n_chunks * gy * gz);
-    const size_t align = format == NRC_VOLUME_F32 ? 16 : 4;
-    const bool vec = v.nx % 4 == 0 && (uintptr_t)src % align == 0;
-    auto ingest = format == NRC_VOLUME_F32 ? (vec ? k_vol_ingest<true, true> : k_vol_ingest<true, false>)
-                                           : (vec ? k_vol_ingest<false, true> : k_vol_ingest<false, false>);
-    hipLaunchKernelGGL(ingest, grid, dim3(256), 0, s, src, v.density, cell_mask, v.nx, v.ny, v.nz, gx, gy, n_chunks);
+    auto ingest = vec ? k_vol_ingest<Src, true> : k_vol_ingest<Src, false>;
+    hipLaunchKernelGGL(ingest, dim3(n_chunks * gy * gz), dim3(256), 0, s, src, v.density, (uint32_t*)scratch, v.nx, v.ny, v.nz, gx, gy, n_chunks);
     NRC_HIP(hipGetLastError());
     launch_volume_cells_rows(v, scratch, s);
+}
+
+void launch_volume_rebuild(const void* src, int format, const VolumeRebuild& v, void* scratch, hipStream_t s)
+{
+    const bool f32 = format == NRC_VOLUME_F32, vec = v.nx % 4 == 0 && (uintptr_t)src % (f32 ? 16 : 4) == 0;
+    if (f32) launch_volume_ingest(VolDense<true>{src}, vec, v, scratch, s);
+    else launch_volume_ingest(VolDense<false>{src}, vec, v, scratch, s);
 }
 
 void launch_volume_quantize(const float* src, uint8_t* dst, size_t n, hipStream_t s)
@@ -2438,13 +2401,8 @@ void launch_volume_rebuild_lerp(const uint8_t* key_a, const uint8_t* key_b, uint
         launch_volume_rebuild(W == 0u ? key_a : key_b, NRC_VOLUME_U8, v, scratch, s);
         return;
     }
-    const uint32_t gx = ceil_div(v.nx, 8), gy = ceil_div(v.ny, 8), gz = ceil_div(v.nz, 8);
-    const uint32_t n_chunks = ceil_div(gx, 32);
     const bool vec = v.nx % 4 == 0 && (uintptr_t)key_a % 4 == 0 && (uintptr_t)key_b % 4 == 0;
-    hipLaunchKernelGGL(vec ? k_vol_ingest_lerp<true> : k_vol_ingest_lerp<false>, dim3(n_chunks * gy * gz), dim3(256), 0, s, key_a, key_b, W, v.density,
-                       (uint32_t*)scratch, v.nx, v.ny, v.nz, gx, gy, n_chunks);
-    NRC_HIP(hipGetLastError());
-    launch_volume_cells_rows(v, scratch, s);
+    launch_volume_ingest(VolLerp{key_a, key_b, W}, vec, v, scratch, s);
 }
 
 size_t volume_brick_index_bytes(uint32_t nx, uint32_t ny, uint32_t nz)
@@ -2455,24 +2413,19 @@ size_t volume_brick_index_bytes(uint32_t nx, uint32_t ny, uint32_t nz)
 void launch_volume_rebuild_bricks(const int32_t* origins, const void* bricks, uint32_t n_bricks, int format, const VolumeRebuild& v, void* scratch,
                                   uint32_t* brick_index, hipStream_t s)
 {
-    const uint32_t gx = ceil_div(v.nx, 8), gy = ceil_div(v.ny, 8), gz = ceil_div(v.nz, 8);
     NRC_HIP(hipMemsetAsync(brick_index, 0, volume_brick_index_bytes(v.nx, v.ny, v.nz), s));
     if (n_bricks) {
-        hipLaunchKernelGGL(k_vol_brick_index, dim3(ceil_div(n_bricks, 256)), dim3(256), 0, s, origins, n_bricks, brick_index, v.nx, v.ny, v.nz, gx, gy);
+        hipLaunchKernelGGL(k_vol_brick_index, dim3(ceil_div(n_bricks, 256)), dim3(256), 0, s, origins, n_bricks, brick_index, v.nx, v.ny, v.nz,
+                           ceil_div(v.nx, 8), ceil_div(v.ny, 8));
         NRC_HIP(hipGetLastError());
     }
-    const uint32_t n_chunks = ceil_div(gx, 32);
     const bool f32 = format == NRC_VOLUME_F32, vec = v.nx % 4 == 0;
     const uint32_t aligned = (uintptr_t)bricks % (f32 ? 16 : 4) == 0 ? 1u : 0u;
-    auto ingest = f32 ? (vec ? k_vol_ingest_bricks<true, true> : k_vol_ingest_bricks<true, false>)
-                      : (vec ? k_vol_ingest_bricks<false, true> : k_vol_ingest_bricks<false, false>);
-    hipLaunchKernelGGL(ingest, dim3(n_chunks * gy * gz), dim3(256), 0, s, bricks, (const uint32_t*)brick_index, v.density, (uint32_t*)scratch,
-                       v.nx, v.ny, v.nz, gx, gy, n_chunks, aligned);
-    NRC_HIP(hipGetLastError());
-    launch_volume_cells_rows(v, scratch, s);
+    if (f32) launch_volume_ingest(VolBricks<true>{bricks, brick_index, aligned}, vec, v, scratch, s);
+    else launch_volume_ingest(VolBricks<false>{bricks, brick_index, aligned}, vec, v, scratch, s);
 }
 
-// the two launches behind either ingest: scratch holds the cells' touch masks, then their occupancy flags
+// the two launches behind k_vol_ingest: scratch holds the cells' touch masks, then their occupancy flags
 static void launch_volume_cells_rows(const VolumeRebuild& v, void* scratch, hipStream_t s)
 {
     const uint32_t gx = ceil_div(v.nx, 8), gy = ceil_div(v.ny, 8), gz = ceil_div(v.nz, 8);

@@ -99,26 +99,30 @@ void launch_gen_rays(const DevScene& sc, const DevCamera& cam, const DevFrame& f
                      float primary_ray_prob, float* primary, float* info, float* origin, float* dir, float* infer_in,
                      unsigned long long* fetch_counter, const TrainGrid& tg, bool full_vertex_images, hipStream_t s);
 
-// marks the 8x8-pixel tiles whose camera rays can meet a non-empty voxel: `boxes` = n axis-aligned world-space boxes
-// {lo.xyz, hi.xyz} that together cover every non-empty voxel with a margin of one voxel.  mask: ceil(tiles/32) + 1 words, zeroed.
 // tile-major query order of the renderer's inference buffers (see query_index in nrc_integrator.hip) -> x * H + y
 void launch_query_layout(const DevFrame& fr, uint32_t floats_per_query, const float* tiled, float* linear, hipStream_t s,
                          const float* info = nullptr);
 uint32_t query_count(uint32_t w, uint32_t h);      // queries in tile-major order: whole 8x8 tiles
-void launch_tile_mask(const float* boxes, uint32_t n_boxes, const DevProjView& pv, const DevFrame& fr, uint32_t* mask, hipStream_t s);
+// marks the 8x8-pixel tiles whose camera rays can meet a non-empty voxel: `boxes` = n axis-aligned world-space boxes
+// {lo.xyz, hi.xyz} that together cover every non-empty voxel with a margin of one voxel.  mask: ceil(tiles/32) + 1 words, zeroed here.
+// The boxes of the active volume: n_host of them, or *n_dev (<= grid, the capacity) when the count lives in device memory, as
+// launch_volume_rebuild leaves it (n_dev not null); grid: the boxes a launch has to cover, 0: none
+struct BoxList {
+    const float* boxes;
+    uint32_t n_host;
+    const uint32_t* n_dev;
+    uint32_t grid;
+};
+void launch_tile_mask(const BoxList& b, const DevProjView& pv, const DevFrame& fr, uint32_t* mask, hipStream_t s);
 uint32_t tile_mask_words(uint32_t w, uint32_t h);
-// the same with the box count in device memory (*n_boxes <= capacity), as launch_volume_rebuild leaves it
-void launch_tile_mask_dev(const float* boxes, const uint32_t* n_boxes, uint32_t capacity, const DevProjView& pv, const DevFrame& fr, uint32_t* mask,
-                         hipStream_t s);
 // the same words (the trailing "off" word included) from a build that runs in parallel over the mask instead of over the boxes, without
-// atomics and without a clear of `mask` (nrc_renderer_render_path: one mask per view).  The box count is n_boxes, or *n_boxes_dev
-// (<= capacity) when n_boxes_dev is not null; rects: 8 bytes per box (n_boxes, or capacity), scratch between the two launches.
-void launch_tile_mask_tiles(const float* boxes, uint32_t n_boxes, const uint32_t* n_boxes_dev, uint32_t capacity, const DevProjView& pv,
-                            const DevFrame& fr, void* rects, uint32_t* mask, hipStream_t s);
+// atomics and without a clear of `mask` (nrc_renderer_render_path: one mask per view).  rects: 8 bytes per box (b.grid), scratch between
+// the two launches.
+void launch_tile_mask_tiles(const BoxList& b, const DevProjView& pv, const DevFrame& fr, void* rects, uint32_t* mask, hipStream_t s);
 
 // ---- device-side volume rebuild (nrc_renderer_set_volume): from a density volume in device memory (NRC_VOLUME_U8 / NRC_VOLUME_F32,
 // index i + nx*(j + ny*k)) the R8 density, the exact occupancy bits (DevScene::occ_bits) and the dilated 8^3-cell boxes of the tile mask,
-// bit-identical to what renderer creation builds on the host.  The box count stays in device memory (launch_tile_mask_dev).
+// bit-identical to what renderer creation builds on the host.  The box count stays in device memory (BoxList::n_dev).
 struct VolumeRebuild {
     uint8_t* density;             // nx*ny*nz bytes
     uint32_t* occ_bits;           // occ_words words

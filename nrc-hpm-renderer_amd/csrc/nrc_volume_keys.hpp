@@ -1,5 +1,5 @@
 // nrc_volume_keys.hpp -- the arithmetic of volume keyframes (include/nrc_hpm.h, nrc_renderer_set_volume_keys): a time's key pair and
-// integer weight, and the in-between voxel.  Device-free: standard library only, shared by the host layer and k_vol_ingest_lerp
+// integer weight, and the in-between voxel.  Device-free: standard library only, shared by the host layer and k_vol_ingest's VolLerp source
 // (tests/cpp/volume_keys_main.cpp runs it on the CPU under the sanitizers).
 #pragma once
 #include <cmath>

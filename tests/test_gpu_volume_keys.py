@@ -9,11 +9,12 @@ import numpy as np
 import pytest
 
 from conftest import nrc_debug
+from volume_common import _make as _small, assert_same_volume, volume_buffers
 
 pytestmark = pytest.mark.gpu
 
 CFG = dict(train_batch_count=1, log2_train_batch_size=10, log2_infer_batch_size=14)
-# (nz, ny, nx): the smallest shapes at which k_vol_ingest_lerp takes another path
+# (nz, ny, nx): the smallest shapes at which k_vol_ingest takes another path with the blended source (VolLerp)
 SHAPES = {"61x45x70-ragged-no-vec": (70, 45, 61), "64^3-vec": (64, 64, 64), "264x9x10-two-chunks-vec": (10, 9, 264),
           "261x9x10-two-chunks-no-vec": (10, 9, 261)}
 N_KEYS = 5      # cloud, rolled cloud, zeros, synthetic A, synthetic B
@@ -116,27 +117,6 @@ def test_the_inputs_are_not_vacuous(sc, cloud16, name):
         vanishes = max(vanishes, int(gone.sum()))
     assert differs >= 0.01, differs
     assert vanishes >= 1
-
-
-def volume_buffers(ren):
-    return {k: ren.VolumeBuffer(k).cpu().numpy().copy() for k in ("density", "occ_bits", "boxes")}
-
-
-def assert_same_volume(got, want, name=""):
-    assert np.array_equal(got["density"], want["density"]), name
-    assert np.array_equal(got["occ_bits"], want["occ_bits"]), name
-    assert got["boxes"].shape == want["boxes"].shape, (name, got["boxes"].shape, want["boxes"].shape)
-    assert np.array_equal(got["boxes"].view(np.uint32), want["boxes"].view(np.uint32)), name
-
-
-def _small(api, sc, kind, vol, W=32, H=16):
-    scene = sc.make_scene(vol, scene_id=4)
-    cam = sc.make_camera(aspect=W / H)
-    if kind == "mc":
-        return api.McHpmRenderer(W, H, 8, False, cam, scene), None
-    cfg = api.AppConfig(train_batch_count=1, log2_train_batch_size=8, log2_infer_batch_size=12)
-    nrc = api.NeuralRadianceCache(cfg)
-    return api.NrcHpmRenderer(W, H, False, cam, cfg, scene, nrc), nrc
 
 
 def _destroy(*pairs):

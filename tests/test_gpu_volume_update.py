@@ -8,24 +8,9 @@ import numpy as np
 import pytest
 
 from conftest import FRAME_RANDOM, nrc_debug
+from volume_common import _make, _sparse_512, _to_f32, assert_same_volume, same_bits, volume_buffers
 
 pytestmark = pytest.mark.gpu
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
-
-
-def volume_buffers(ren):
-    return {k: ren.VolumeBuffer(k).cpu().numpy().copy() for k in ("density", "occ_bits", "boxes")}
-
-
-def assert_same_volume(got, want, name=""):
-    assert np.array_equal(got["density"], want["density"]), name
-    assert np.array_equal(got["occ_bits"], want["occ_bits"]), name
-    assert got["boxes"].shape == want["boxes"].shape, (name, got["boxes"].shape, want["boxes"].shape)
-    assert np.array_equal(got["boxes"].view(np.uint32), want["boxes"].view(np.uint32)), name
 
 
 def _single_voxels(n=24):
@@ -44,25 +29,6 @@ def _volumes(cloud16):
     odd = (rng.random((29, 7, 13)) < 0.02).astype(np.uint8) * rng.integers(1, 256, (29, 7, 13)).astype(np.uint8)
     return [("zeros", np.zeros_like(cloud16)), ("full", np.full_like(cloud16, 255)), ("cloud16", cloud16),
             ("cloud16_rolled", np.ascontiguousarray(np.roll(cloud16, (17, -9, 40), axis=(0, 1, 2)))), ("odd13x7x29", odd)] + _single_voxels()
-
-
-def _sparse_512():
-    rng = np.random.default_rng(11)
-    v = np.zeros((160, 512, 512), np.uint8)
-    idx = rng.integers(0, v.size, 4000)
-    v.reshape(-1)[idx] = rng.integers(1, 256, idx.size).astype(np.uint8)
-    v[40:56, 100:140, 300:331] = 90       # a block across cell borders
-    return v
-
-
-def _make(api, sc, kind, vol, W=32, H=16):
-    scene = sc.make_scene(vol, scene_id=4)
-    cam = sc.make_camera(aspect=W / H)
-    if kind == "mc":
-        return api.McHpmRenderer(W, H, 8, False, cam, scene), None
-    cfg = api.AppConfig(train_batch_count=1, log2_train_batch_size=8, log2_infer_batch_size=12)
-    nrc = api.NeuralRadianceCache(cfg)
-    return api.NrcHpmRenderer(W, H, False, cam, cfg, scene, nrc), nrc
 
 
 def _as_source(vol, source):
@@ -108,6 +74,44 @@ def test_device_rebuild_equals_creation_build(api, sc, cloud16, torch_gpu, kind,
         ren.SetVolume(src)
         assert_same_volume(volume_buffers(ren), want)
         ren.SetVolume(np.zeros_like(v))
+    ren.Destroy()
+
+
+# (nz, ny, nx), nx % 4 == 0: one workgroup per cell row, and two x-chunks with ragged y / z
+UNALIGNED_SHAPES = {"64^3": (64, 64, 64), "264x9x10-two-chunks": (10, 9, 264)}
+
+
+def _edge_volume(shape):
+    """seeded sparse voxels, a block across cell borders and the volume's first and last voxels (the last four of x in the last row)"""
+    rng = np.random.default_rng(shape[2])
+    v = np.zeros(shape, np.uint8)
+    idx = rng.integers(0, v.size, v.size // 200)
+    v.reshape(-1)[idx] = rng.integers(1, 256, idx.size).astype(np.uint8)
+    nz, ny, nx = shape
+    v[nz // 2 - 1:nz // 2 + 2, 6:ny, 30:41] = 90
+    v[0, 0, 0] = 1
+    v[-1, -1, -4:] = (255, 3, 0, 7)
+    return v
+
+
+@pytest.mark.parametrize("fmt", ["u8", "f32"])
+@pytest.mark.parametrize("name", list(UNALIGNED_SHAPES))
+def test_unaligned_device_source_with_nx_a_multiple_of_four(api, sc, torch_gpu, name, fmt):
+    """a device volume at element offset 1 of a larger tensor: nx % 4 == 0, but the source cannot be read four elements at a time, so the
+    rebuild takes the scalar path with every lane's four voxels in range; the buffers equal those of a renderer created with the volume"""
+    import torch
+    v = _edge_volume(UNALIGNED_SHAPES[name])
+    fresh, _ = _make(api, sc, "mc", v)
+    want = volume_buffers(fresh)
+    fresh.Destroy()
+    host = v if fmt == "u8" else _to_f32(v)
+    flat = torch.full((v.size + 8,), 1, dtype=torch.from_numpy(host).dtype, device="cuda")      # (non-zero around the volume)
+    flat[1:1 + v.size] = torch.from_numpy(host.reshape(-1)).cuda()
+    src = flat[1:1 + v.size].view(v.shape)
+    assert src.data_ptr() % (4 * src.element_size()) != 0 and src.is_contiguous()
+    ren, _ = _make(api, sc, "mc", np.zeros_like(v))
+    ren.SetVolume(src)
+    assert_same_volume(volume_buffers(ren), want, name)
     ren.Destroy()
 
 

@@ -14,7 +14,7 @@ for line in out.splitlines():
     if m:
         cur = m.group(1); rows[cur] = {}
         continue
-    m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/\w+\])?: (\d+)", line)
+    m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[\w/]+\])?: (\d+)", line)
     if m and cur:
         rows[cur][m.group(1).strip()] = int(m.group(2))
 for name, r in rows.items():

@@ -6,7 +6,8 @@ nrc_renderer_set_volume), on three subjects: the fBm cloud at 256^3, the smoke p
   python tools/volume_bricks_rate.py --subject S --frames 200 --mc-frames 40           (d) ms/frame with a swap before every frame
   rocprofv3 --kernel-trace --stats -d <dir> -- python tools/volume_bricks_rate.py --subject S --rebuild-only 200 --path dense|bricks
       (a) only the device-source calls of one path on a small MC renderer: the rebuild kernels' GPU time, in a trace of its own
-      (k_vol_cells / k_vol_rows run in both paths, so each path gets a trace of its own)
+      (k_vol_ingest<VolDense<..>, ..> against k_vol_brick_index + k_vol_ingest<VolBricks<..>, ..>; k_vol_cells / k_vol_rows run in both
+      paths, so each path gets a trace of its own)
 
 Prints one JSON line per measurement; profiles/volume_bricks_rate.txt is the record of a run."""
 import argparse

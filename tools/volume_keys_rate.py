@@ -1,9 +1,9 @@
 """What volume keyframes cost and buy (nrc_renderer_set_volume_keys / _set_volume_time / _render_path_timed), on an MI355X.
 
   (a) rocprofv3 --kernel-trace --stats -d <dir> -- python tools/volume_keys_rate.py --rebuild-only lerp|dense --dims 256|512 [--calls 200]
-      only the rebuild runs, on a small MC renderer: `lerp` is SetVolumeTime at weights strictly between two keys (k_vol_ingest_lerp +
-      k_vol_cells + k_vol_rows), `dense` is SetVolume of a device u8 volume (k_vol_ingest + the same two) -- the baseline, whose kernels
-      this build leaves as they were.  Each in a trace of its own: the two share k_vol_cells and k_vol_rows.  512 is the 256^3 cloud
+      only the rebuild runs, on a small MC renderer: `lerp` is SetVolumeTime at weights strictly between two keys (k_vol_ingest<VolLerp, ...> +
+      k_vol_cells + k_vol_rows), `dense` is SetVolume of a device u8 volume (k_vol_ingest<VolDense<false>, ...> + the same two) -- the
+      baseline: one kernel template, two voxel sources.  Each in a trace of its own: the two share k_vol_cells and k_vol_rows.  512 is the 256^3 cloud
       doubled along every axis.  The in-between reads twice the source bytes; the ratio is reported, not bounded.
   (b) python tools/volume_keys_rate.py [--renderer nrc|mc|both] [--views 64] [--frames-per-view 4] [--keys 8] [--reps 7]
       a 64-view orbit, 4 frames per view, of the default preset (1920 x 1080, 6x64 cache, training on) and of the MC renderer at 32
