@@ -613,8 +613,11 @@ int nrc_image_destroy(float* d_image);
  * (the list and what each does: csrc/nrc_common.hpp, debug_switch).
  * diagnostics (read when the library first allocates): NRC_DEBUG=poison_alloc fills every device allocation with 0xFF
  * bytes at creation; NRC_DEBUG=guard_alloc puts 4 KiB canaries around every allocation.  nrc_debug_check_guards returns -1 when the
- * guard mode is off, otherwise the number of allocations whose canaries were overwritten (0 = clean) and, in message, the first. */
+ * guard mode is off, otherwise the number of allocations whose canaries were overwritten (0 = clean) and, in message, the first.
+ * nrc_debug_live_allocations (always on): device allocations the library holds right now, nrc_image_create's included -- what it was
+ * before an object was created is what it is again after the object is destroyed, or after its creation failed. */
 int nrc_debug_check_guards(char* message, size_t message_bytes);
+int nrc_debug_live_allocations(void);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Test hooks (bit-parity of the math spec and RNG against the oracle; device pointers) */

@@ -97,7 +97,7 @@ ABI_SYMBOLS = [
     "nrc_mc_renderer_create", "nrc_mc_renderer_render", "nrc_mc_renderer_set_camera", "nrc_mc_renderer_set_blend",
     "nrc_mc_renderer_set_frame_random", "nrc_mc_renderer_framebuffer", "nrc_mc_renderer_export_exr",
     "nrc_mc_renderer_frame_time_ms", "nrc_mc_renderer_count_fetches", "nrc_mc_renderer_destroy",
-    "nrc_compare_images", "nrc_test_math", "nrc_test_rng", "nrc_debug_check_guards", "nrc_image_create", "nrc_image_destroy",
+    "nrc_compare_images", "nrc_test_math", "nrc_test_rng", "nrc_debug_check_guards", "nrc_debug_live_allocations", "nrc_image_create", "nrc_image_destroy",
 ]
 
 _lib = None
@@ -1171,6 +1171,11 @@ def check_guards():
     buf = C.create_string_buffer(512)
     n = load_library().nrc_debug_check_guards(buf, C.c_size_t(512))
     return int(n), buf.value.decode()
+
+
+def live_allocations():
+    """device allocations the library holds right now (nrc_debug_live_allocations): unchanged by an object's whole life, or a failed creation"""
+    return int(load_library().nrc_debug_live_allocations())
 
 
 def test_math(fn, a, b=None):

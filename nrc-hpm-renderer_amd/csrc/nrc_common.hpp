@@ -12,6 +12,7 @@
 
 #include "../../include/nrc_hpm.h"
 #include "nrc_fail.hpp"      // fail(): the error convention, shared with the device-free headers
+#include "nrc_owned.hpp"     // Owned / DevBuf, dev_alloc / dev_free: device-free too
 
 namespace nrc {
 
@@ -129,12 +130,30 @@ inline int device_xcds()
     return n;
 }
 
-// Every device allocation of the library goes through these two (nrc_api.hip); NRC_DEBUG=poison_alloc / guard_alloc (above) make them
-// fill what they hand out with NaN bytes / fence it with canaries that nrc_debug_check_guards() and every dev_free verify.
-void dev_alloc(void** p, size_t bytes, const char* what = "");
-void dev_free(void* p);
-template <class T>
-inline void dev_alloc(T** p, size_t bytes, const char* what = "") { dev_alloc(reinterpret_cast<void**>(p), bytes, what); }
+// ---- owners of HIP resources (nrc_owned.hpp: Owned, DevBuf, dev_alloc / dev_free).  A member of one of these types releases itself.
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+inline void free_pinned(unsigned long long* p) { (void)hipHostFree(p); }
+using PinnedCell = Owned<unsigned long long*, free_pinned>;      // one 8-byte host-mapped pinned cell (loss cell, guard cell)
+inline Event make_event(unsigned flags)
+{
+    hipEvent_t e = nullptr;
+    NRC_HIP(hipEventCreateWithFlags(&e, flags));
+    return Event(e);
+}
+inline Stream make_stream(int priority)
+{
+    hipStream_t s = nullptr;
+    NRC_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority));
+    return Stream(s);
+}
+inline PinnedCell make_pinned_cell()
+{
+    unsigned long long* p = nullptr;
+    NRC_HIP(hipHostMalloc((void**)&p, sizeof(unsigned long long), hipHostMallocMapped));
+    *p = 0ull;
+    return PinnedCell(p);
+}
 
 // O'Neill's pcg32 (XSH-RR) as tiny-cuda-nn vendors it (pcg32.h): its Trainer seeds pcg32{1337}, i.e. stream initseq = 1
 struct Pcg32 {

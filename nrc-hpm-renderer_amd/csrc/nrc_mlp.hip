@@ -2586,12 +2586,12 @@ Mlp::Mlp(const nrc_config& cfg) : cfg_(cfg)
     }
 
     const size_t pb = (size_t)n_params_ * sizeof(float);
-    dev_alloc(&d_w_, pb, "d_w_");
-    dev_alloc(&d_ema_, pb, "d_ema_");
-    dev_alloc(&d_m_, pb, "d_m_");
-    dev_alloc(&d_v_, pb, "d_v_");
+    d_w_.alloc(pb, "d_w_");
+    d_ema_.alloc(pb, "d_ema_");
+    d_m_.alloc(pb, "d_m_");
+    d_v_.alloc(pb, "d_v_");
     // gradient vector and the {loss, pad} cell share one allocation so that the multi-GPU driver all-reduces both at once
-    dev_alloc(&d_grad_, pb + 4 * sizeof(float), "d_grad_");
+    d_grad_.alloc(pb + 4 * sizeof(float), "d_grad_");
     d_loss_ = d_grad_ + n_params_;
     NRC_HIP(hipMemcpy(d_w_, w.data(), pb, hipMemcpyHostToDevice));
     NRC_HIP(hipMemcpy(d_ema_, w.data(), pb, hipMemcpyHostToDevice));
@@ -2636,8 +2636,8 @@ Mlp::Mlp(const nrc_config& cfg) : cfg_(cfg)
             }
         }
     }
-    dev_alloc(&d_src_fwd_, sf.size() * 4, "d_src_fwd_");
-    dev_alloc(&d_src_bwd_, sb.size() * 4, "d_src_bwd_");
+    d_src_fwd_.alloc(sf.size() * 4, "d_src_fwd_");
+    d_src_bwd_.alloc(sb.size() * 4, "d_src_bwd_");
     NRC_HIP(hipMemcpy(d_src_fwd_, sf.data(), sf.size() * 4, hipMemcpyHostToDevice));
     // Generic models with the Frequency(12) + OneBlob(4) input (configs[4]'s 8x128): EMA inference encodes inside k_infer_gen as
     // k_infer does, so its image takes layer 0's inputs in that encoder's order (fmap80); training keeps k_encode's natural order
@@ -2651,12 +2651,13 @@ Mlp::Mlp(const nrc_config& cfg) : cfg_(cfg)
                     for (int s = 0; s < ks0; s++)
                         if (32 * mt + (lane & 31) < W)
                             si[slot(mt * ks0 + s, lane, j)] = (int32_t)(layers_[0].off + (32 * mt + (lane & 31)) * E + fmap80(s, lane >> 5, j));
-        dev_alloc(&d_src_inf_, si.size() * 4, "d_src_inf_");
+        d_src_inf_own_.alloc(si.size() * 4, "d_src_inf_");
+        d_src_inf_ = d_src_inf_own_;
         NRC_HIP(hipMemcpy(d_src_inf_, si.data(), si.size() * 4, hipMemcpyHostToDevice));
     }
     NRC_HIP(hipMemcpy(d_src_bwd_, sb.data(), sb.size() * 4, hipMemcpyHostToDevice));
     for (auto& p : d_pk_infer_) {
-        dev_alloc(&p, sf.size() * 2, "p");
+        p.alloc(sf.size() * 2, "d_pk_infer_");
         NRC_HIP(hipMemset(p, 0, sf.size() * 2));      // k_opt_pack never writes the padding slots
     }
     // inverse maps for the one-launch optimizer step (k_opt_pack): parameter -> its slot in each image
@@ -2676,32 +2677,19 @@ Mlp::Mlp(const nrc_config& cfg) : cfg_(cfg)
         if (fused_opt_) invert(si_host.data(), si_host.size(), dst.data() + n_mlp_);
         if (fused_opt_) invert(sb.data(), sb.size(), dst.data() + 2 * (size_t)n_mlp_);
         if (fused_opt_) {
-            dev_alloc(&d_dst_, dst.size() * 4, "d_dst_");
+            d_dst_.alloc(dst.size() * 4, "d_dst_");
             NRC_HIP(hipMemcpy(d_dst_, dst.data(), dst.size() * 4, hipMemcpyHostToDevice));
         }
     }
-    dev_alloc(&d_pk_fwd_, sf.size() * 2, "d_pk_fwd_");
-    dev_alloc(&d_pk_bwd_, sb.size() * 2, "d_pk_bwd_");
+    d_pk_fwd_.alloc(sf.size() * 2, "d_pk_fwd_");
+    d_pk_bwd_.alloc(sb.size() * 2, "d_pk_bwd_");
     if (hash_) {
-        dev_alloc(&d_t16_train_, (size_t)n_grid_entries_ * 4, "d_t16_train_");
-        for (auto& p : d_t16_ema_) dev_alloc(&p, (size_t)n_grid_entries_ * 4, "p");
-        dev_alloc(&d_grad16_, (size_t)n_grid_entries_ * 4, "d_grad16_");
+        d_t16_train_.alloc((size_t)n_grid_entries_ * 4, "d_t16_train_");
+        for (auto& p : d_t16_ema_) p.alloc((size_t)n_grid_entries_ * 4, "d_t16_ema_");
+        d_grad16_.alloc((size_t)n_grid_entries_ * 4, "d_grad16_");
     }
     repack(nullptr);
     NRC_HIP(hipStreamSynchronize(nullptr));
-}
-
-Mlp::~Mlp()
-{
-    if (d_src_inf_ != d_src_fwd_ && d_src_inf_) dev_free(d_src_inf_);
-    if (d_dst_) dev_free(d_dst_);
-    void* ptrs[] = {d_w_, d_ema_, d_m_, d_v_, d_grad_, d_pk_infer_[0], d_pk_infer_[1], d_pk_fwd_, d_pk_bwd_, d_src_fwd_,
-                    d_src_bwd_, d_acts_, d_deltas_, d_slabs_, d_loss_part_, d_tiles_, d_tasks_, d_feat_[0], d_feat_[1], d_feat_[2], d_feat_[3], d_feat_[4], d_t16_train_,
-                    d_t16_ema_[0], d_t16_ema_[1], d_denc_, d_grad16_, d_grid_lists_, d_grid_counters_, d_grid_bin_entry0_, d_grid_fix_};
-    for (void* p : ptrs)
-        if (p) dev_free(p);
-    if (d_guard_) dev_free(d_guard_);
-    if (h_guard_) (void)hipHostFree(h_guard_);
 }
 
 float* Mlp::buffer(int which)
@@ -2747,7 +2735,7 @@ void Mlp::repack(hipStream_t s)
                        (half_t*)d_pk_infer_[next], (half_t*)d_pk_fwd_, (half_t*)d_pk_bwd_);
     if (hash_)
         hipLaunchKernelGGL(k_pack_grid, dim3(ceil_div(n_grid_entries_, 256)), dim3(256), 0, s, d_w_ + n_mlp_, d_ema_ + n_mlp_,
-                           (uint32_t*)d_t16_train_, (uint32_t*)d_t16_ema_[next], n_grid_entries_);
+                           d_t16_train_, d_t16_ema_[next], n_grid_entries_);
     NRC_HIP(hipGetLastError());
     infer_set_ = next;
 }
@@ -2766,7 +2754,7 @@ void Mlp::launch_features(const float* d_in, uint32_t n, bool use_ema, int slot,
     }
     HashLevels lv;
     for (uint32_t l = 0; l <= HG_LEVELS; l++) lv.off[l] = hg_off_[l];
-    const uint32_t* tab = (const uint32_t*)(use_ema ? d_t16_ema_[infer_set_] : d_t16_train_);
+    const uint32_t* tab = use_ema ? d_t16_ema_[infer_set_] : d_t16_train_;
     if (slot == 0 && live_list != nullptr && skip_zero) {      // renderer inference with the frame's live-query list
         const uint32_t n_slots = enc_dims_ / 2;
         dim3 g((uint32_t)num_cus() * 2u, n_slots);
@@ -2837,12 +2825,8 @@ static void launch_infer(uint32_t blocks, size_t lds, hipStream_t s, const float
 void Mlp::ensure_features(uint32_t n, int slot)
 {
     if (n <= feat_n_[slot]) return;
-    if (d_feat_[slot]) {
-        NRC_HIP(hipDeviceSynchronize());      // a kernel on another stream may still read the old buffer
-        dev_free(d_feat_[slot]);
-    }
-    d_feat_[slot] = nullptr;
-    dev_alloc(&d_feat_[slot], (size_t)n * enc_dims_ * 2, "d_feat_[slot]");
+    if (d_feat_[slot]) NRC_HIP(hipDeviceSynchronize());      // a kernel on another stream may still read the old buffer
+    d_feat_[slot].alloc((size_t)n * enc_dims_ * 2, "d_feat_[slot]");
     feat_n_[slot] = n;
 }
 
@@ -3060,7 +3044,7 @@ void Mlp::build_wgrad_tasks()
             }
     }
     n_wgrad_tasks_ = (int)tasks.size();
-    dev_alloc(&d_tasks_, tasks.size() * sizeof(WgradTask), "d_tasks_");
+    d_tasks_.alloc(tasks.size() * sizeof(WgradTask), "d_tasks_");
     NRC_HIP(hipMemcpy(d_tasks_, tasks.data(), tasks.size() * sizeof(WgradTask), hipMemcpyHostToDevice));
 }
 // samples per K-chunk of the weight-gradient launch: ~2 workgroups per CU, a multiple of 32 samples, at least 64
@@ -3076,33 +3060,22 @@ uint32_t Mlp::wgrad_chunk(uint32_t n)
 void Mlp::ensure_train_workspace(uint32_t n)
 {
     if (n <= ws_n_) return;
-    if (d_acts_) dev_free(d_acts_);
-    if (d_deltas_) dev_free(d_deltas_);
-    if (d_slabs_) dev_free(d_slabs_);
-    if (d_loss_part_) dev_free(d_loss_part_);
-    d_acts_ = d_deltas_ = nullptr;
-    d_slabs_ = d_loss_part_ = nullptr;
     const size_t rows_a = enc_dims_ + (size_t)depth_ * kw_, rows_d = (size_t)depth_ * kw_ + 8;
-    dev_alloc(&d_acts_, rows_a * n * 2, "d_acts_");
-    dev_alloc(&d_deltas_, rows_d * n * 2, "d_deltas_");
+    d_acts_.alloc(rows_a * n * 2, "d_acts_");
+    d_deltas_.alloc(rows_d * n * 2, "d_deltas_");
     NRC_HIP(hipMemset(d_deltas_, 0, rows_d * n * 2));
     build_wgrad_tasks();
     // (k_wgrad2: a smaller batch has a smaller chunk, never more chunks than the launch's target count)
     const uint32_t max_chunks = wgrad_old_ ? ceil_div(n, WGRAD_CHUNK)
                                            : std::max(ceil_div(n, wgrad_chunk(n)), std::max(1u, 2u * (uint32_t)num_cus() / std::max(1u, ceil_div((uint32_t)n_wgrad_tasks_, (uint32_t)WGRAD2_WAVES))));
-    dev_alloc(&d_slabs_, (size_t)max_chunks * n_mlp_ * 4, "d_slabs_");
+    d_slabs_.alloc((size_t)max_chunks * n_mlp_ * 4, "d_slabs_");
     if (hash_) {
-        if (d_denc_) dev_free(d_denc_);
-        d_denc_ = nullptr;
-        dev_alloc(&d_denc_, (size_t)n * 32 * 2, "d_denc_");
+        d_denc_.alloc((size_t)n * 32 * 2, "d_denc_");
         // bin lists of the table gradient (k_grid_scatter): levels of at least GB_MIN_BINS bins of GB_BIN entries; a level's lists hold twice
         // what the level sends a bin on average (n * 8 / bins pairs); the rest goes into the fixed-point shadow
-        if (d_grid_lists_) dev_free(d_grid_lists_);
-        d_grid_lists_ = nullptr;
-        if (d_grid_bin_entry0_) dev_free(d_grid_bin_entry0_);
-        d_grid_bin_entry0_ = nullptr;
-        if (d_grid_counters_) dev_free(d_grid_counters_);
-        d_grid_counters_ = nullptr;
+        d_grid_lists_.reset();
+        d_grid_bin_entry0_.reset();
+        d_grid_counters_.reset();
         grid_bins_total_ = 0;
         const bool no_bins = debug_switch("grid_no_bins");      // tests: every pair through the fixed-point shadow
         std::vector<uint32_t> info;      // uint4 per bin: {first entry, pair offset of the list, capacity, 0}
@@ -3122,19 +3095,19 @@ void Mlp::ensure_train_workspace(uint32_t n)
         }
         if (pairs > 0xffffffffull) fail("train batch too large for the table gradient's bin lists");
         if (grid_bins_total_ != 0u) {
-            dev_alloc(&d_grid_lists_, pairs * 8, "d_grid_lists_");
-            dev_alloc(&d_grid_counters_, (size_t)grid_bins_total_ * 4, "d_grid_counters_");
+            d_grid_lists_.alloc(pairs * 8, "d_grid_lists_");
+            d_grid_counters_.alloc((size_t)grid_bins_total_ * 4, "d_grid_counters_");
             NRC_HIP(hipMemset(d_grid_counters_, 0, (size_t)grid_bins_total_ * 4));
-            dev_alloc(&d_grid_bin_entry0_, info.size() * 4, "d_grid_bin_info_");
+            d_grid_bin_entry0_.alloc(info.size() * 4, "d_grid_bin_info_");
             NRC_HIP(hipMemcpy(d_grid_bin_entry0_, info.data(), info.size() * 4, hipMemcpyHostToDevice));
         }
         // the fixed-point shadow of the table: two int64 per entry, all zero between two steps (k_grid_gather clears what it folds in)
         if (!d_grid_fix_) {
-            dev_alloc(&d_grid_fix_, (size_t)n_grid_entries_ * 16, "d_grid_fix_");
+            d_grid_fix_.alloc((size_t)n_grid_entries_ * 16, "d_grid_fix_");
             NRC_HIP(hipMemset(d_grid_fix_, 0, (size_t)n_grid_entries_ * 16));
         }
     }
-    dev_alloc(&d_loss_part_, (size_t)(n / 32) * 4, "d_loss_part_");
+    d_loss_part_.alloc((size_t)(n / 32) * 4, "d_loss_part_");
     ws_n_ = n;
     if (!d_tiles_) {
         std::vector<WgradTile> tiles;
@@ -3156,7 +3129,7 @@ void Mlp::ensure_train_workspace(uint32_t n)
                 }
         }
         n_wgrad_tiles_ = (int)tiles.size();
-        dev_alloc(&d_tiles_, tiles.size() * sizeof(WgradTile), "d_tiles_");
+        d_tiles_.alloc(tiles.size() * sizeof(WgradTile), "d_tiles_");
         NRC_HIP(hipMemcpy(d_tiles_, tiles.data(), tiles.size() * sizeof(WgradTile), hipMemcpyHostToDevice));
     }
 }
@@ -3209,7 +3182,7 @@ void Mlp::backward(const float* d_in, const float* d_target, uint32_t n, uint32_
         a.loss_part = d_loss_part_;
         a.depth = (int)depth_;
         a.ks0 = (int)enc_dims_ / 16;
-        a.d_enc = hash_ ? (half_t*)d_denc_ : nullptr;
+        a.d_enc = hash_ ? d_denc_.get() : nullptr;
         // a training batch is a few hundred 32-sample tiles (16 384 rays = 512): four-wave workgroups (128 of them) stream each
         // layer once per four tiles; large batches use eight waves, two workgroups per CU
         const bool small = n_tiles <= (uint32_t)num_cus() * 8u;
@@ -3300,16 +3273,16 @@ void Mlp::backward(const float* d_in, const float* d_target, uint32_t n, uint32_
                     attr_gather_set_ = true;
                 }
                 const bool level_major = !xcd8_;
-                hipLaunchKernelGGL(k_grid_scatter, level_major ? dim3(ceil_div(n, 256), HG_LEVELS) : dim3(ceil_div(n, 256) * HG_LEVELS, 1), dim3(256), 0, s, d_in, (const half_t*)d_denc_, (long long*)d_grid_fix_, n, lv,
-                                   gb, (uint32_t*)d_grid_counters_, (uint2*)d_grid_lists_);
-                hipLaunchKernelGGL(k_grid_gather, dim3(grid_bins_total_ + loose_chunks), dim3(NRC_GB_GATHER_THREADS), GB_BIN * 16u, s, (uint32_t*)d_grad16_,
-                                   (const uint4*)d_grid_bin_entry0_, grid_bins_total_, (uint32_t*)d_grid_counters_, (const uint2*)d_grid_lists_, (long long*)d_grid_fix_, loose);
+                hipLaunchKernelGGL(k_grid_scatter, level_major ? dim3(ceil_div(n, 256), HG_LEVELS) : dim3(ceil_div(n, 256) * HG_LEVELS, 1), dim3(256), 0, s, d_in, d_denc_, d_grid_fix_, n, lv,
+                                   gb, d_grid_counters_, d_grid_lists_);
+                hipLaunchKernelGGL(k_grid_gather, dim3(grid_bins_total_ + loose_chunks), dim3(NRC_GB_GATHER_THREADS), GB_BIN * 16u, s, d_grad16_,
+                                   d_grid_bin_entry0_, grid_bins_total_, d_grid_counters_, d_grid_lists_, d_grid_fix_, loose);
             }
             // the fp32 copy in the gradient vector is for whoever reads the vector (exchange, hook, debug read-back): the
             // optimizer takes the table gradient from grad16 itself (k_grid_opt2)
             grid16_valid_ = fused_opt_;
             if (widen_grid_grad || !fused_opt_)
-                hipLaunchKernelGGL(k_grid_grad_f32, dim3(ceil_div(n_grid_entries_, 256)), dim3(256), 0, s, (const uint32_t*)d_grad16_,
+                hipLaunchKernelGGL(k_grid_grad_f32, dim3(ceil_div(n_grid_entries_, 256)), dim3(256), 0, s, d_grad16_,
                                    d_grad_ + n_mlp_, n_grid_entries_);
         }
     }
@@ -3337,10 +3310,9 @@ void Mlp::backward(const float* d_in, const float* d_target, uint32_t n, uint32_
 void Mlp::set_guard(bool on)
 {
     if (on && !d_guard_) {
-        dev_alloc((void**)&d_guard_, 4 * sizeof(uint32_t), "d_guard_");
+        d_guard_.alloc(4 * sizeof(uint32_t), "d_guard_");
         NRC_HIP(hipMemset(d_guard_, 0, 4 * sizeof(uint32_t)));
-        NRC_HIP(hipHostMalloc((void**)&h_guard_, sizeof(unsigned long long), hipHostMallocMapped));
-        *h_guard_ = 0ull;
+        h_guard_ = make_pinned_cell();
         NRC_HIP(hipHostGetDevicePointer((void**)&d_guard_cell_, h_guard_, 0));
     }
     guard_on_ = on;
@@ -3356,7 +3328,7 @@ GuardArgs Mlp::guard_scan_args()
 
 void Mlp::guard_stats(uint32_t* skipped, uint32_t* last_step) const
 {
-    const unsigned long long bits = h_guard_ ? __atomic_load_n(h_guard_, __ATOMIC_ACQUIRE) : 0ull;
+    const unsigned long long bits = h_guard_ ? __atomic_load_n(h_guard_.get(), __ATOMIC_ACQUIRE) : 0ull;
     *skipped = (uint32_t)bits;
     *last_step = (uint32_t)(bits >> 32);
 }
@@ -3373,7 +3345,7 @@ void Mlp::grid_grad_pack(uint32_t* d_list, uint32_t cap, hipStream_t s)
     if (!hash_) fail("grid_grad_pack: this model has no trainable encoding");
     NRC_HIP(hipMemsetAsync(d_list, 0xff, grid_list_words(cap) * 4, s));        // entry 0xffffffff: padding
     NRC_HIP(hipMemsetAsync(d_list, 0, 8, s));
-    hipLaunchKernelGGL(k_grid_pack, dim3(ceil_div(n_grid_entries_, 4096)), dim3(256), 0, s, (const uint32_t*)d_grad16_,
+    hipLaunchKernelGGL(k_grid_pack, dim3(ceil_div(n_grid_entries_, 4096)), dim3(256), 0, s, d_grad16_,
                        n_grid_entries_, d_list, cap);
     NRC_HIP(hipGetLastError());
 }
@@ -3449,13 +3421,13 @@ bool Mlp::optimizer_step(hipStream_t s, uint32_t loss_seq, unsigned long long* l
                 if (hash_) hipLaunchKernelGGL(pack, dim3(ceil_div(n_mlp_, 256)), b, 0, s, args...);
                 else launch_last(pack, dim3(ceil_div(n_mlp_, 256)), b, 0u, s, args...);
             };
-            launch(d_w_, d_ema_, d_m_, d_v_, d_grad_, n_mlp_, lr, a, d, loss, loss_seq, loss_cell, ga...);
+            launch(d_w_.get(), d_ema_.get(), d_m_.get(), d_v_.get(), d_grad_.get(), n_mlp_, lr, a, d, loss, loss_seq, loss_cell, ga...);
             if (!hash_) return;
-            uint32_t *tt = (uint32_t*)d_t16_train_, *te = (uint32_t*)d_t16_ema_[next], *g16 = (uint32_t*)d_grad16_;
+            uint32_t *tt = d_t16_train_, *te = d_t16_ema_[next], *g16 = d_grad16_;
             const uint32_t np = n_grid_entries_ / 2u;
             if (grid16_valid_) grad16_clean_ = true;      // k_grid_opt2<., true> clears the entries it reads, on a bad step too
             with_flag(grid16_valid_, [&](auto from16) {
-                launch_last(k_grid_opt2<SGD, decltype(from16)::value, decltype(ga)...>, dim3(ceil_div(np, 256)), b, 0u, s, d_w_, d_ema_, d_m_, d_v_, d_grad_,
+                launch_last(k_grid_opt2<SGD, decltype(from16)::value, decltype(ga)...>, dim3(ceil_div(np, 256)), b, 0u, s, d_w_.get(), d_ema_.get(), d_m_.get(), d_v_.get(), d_grad_.get(),
                             g16, n_mlp_, np, lr, a, tt, te, ga...);
             });
         });

@@ -58,7 +58,6 @@ void mlp_set_wave_priority_raise(int on);      // nrc_common.hpp: NRC_RAISE_WAVE
 class Mlp {
 public:
     explicit Mlp(const nrc_config& cfg);
-    ~Mlp();
     Mlp(const Mlp&) = delete;
     Mlp& operator=(const Mlp&) = delete;
 
@@ -138,8 +137,8 @@ public:
 private:
     bool guard_on_ = false, guard_scanned_ = false;
     uint32_t guard_stamp_ = 0;
-    uint32_t* d_guard_ = nullptr;                   // GuardArgs::words
-    unsigned long long* h_guard_ = nullptr;         // GuardArgs::host_cell (pinned, host-mapped)
+    DevBuf<uint32_t> d_guard_;                      // GuardArgs::words
+    PinnedCell h_guard_;                            // GuardArgs::host_cell (pinned, host-mapped)
     unsigned long long* d_guard_cell_ = nullptr;    // its device address
     int num_cus();
     int num_cus_ = 0;
@@ -160,7 +159,7 @@ private:
     bool sgd_ = false;           // nested optimizer: Adam (default) or SGD
     bool fused_ = false;         // north-star model (Frequency+OneBlob, 6x64): fully fused kernels; otherwise the generic path
     std::vector<MlpLayer> layers_;
-    void* d_feat_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};     // generic path: fp16 features [n][enc_dims]; [0] inference, [1] training (encoded by backward), [2] [3] training (pre_encode, by parity), [4] side inference (kSideSlot)
+    DevBuf<void> d_feat_[5];     // generic path: fp16 features [n][enc_dims]; [0] inference, [1] training (encoded by backward), [2] [3] training (pre_encode, by parity), [4] side inference (kSideSlot)
     uint32_t feat_n_[5] = {0, 0, 0, 0, 0};
     int infer_set_ = 0;          // which of the double-buffered inference (EMA) image / table sets is current
     uint32_t n_mlp_ = 0;         // matrix parameters; (posID 0) the hash-grid table [entry][2] follows them in every vector
@@ -168,37 +167,42 @@ private:
     bool xcd8_ = true;           // the device has eight XCDs: the level-per-XCD launch mappings of the HashGrid kernels apply
     uint32_t hg_off_[17] = {0};  // per-level entry offsets
     uint32_t n_grid_entries_ = 0;
-    void *d_t16_train_ = nullptr, *d_t16_ema_[2] = {nullptr, nullptr};   // half2-per-entry gather copies of the table
-    void* d_denc_ = nullptr;     // fp16 [n][32] dL/d(grid features)
-    void* d_grad16_ = nullptr;   // half2 per table entry: target of the packed gradient atomics
+    DevBuf<uint32_t> d_t16_train_, d_t16_ema_[2];   // half2-per-entry gather copies of the table
+    DevBuf<_Float16> d_denc_;    // fp16 [n][32] dL/d(grid features)
+    DevBuf<uint32_t> d_grad16_;  // half2 per table entry: target of the packed gradient atomics
     // bin lists of the table gradient (k_grid_scatter / k_grid_gather): (entry, value) pairs per bin of 4 096 entries, pair counters, per-bin
     // {first entry, list offset, capacity}; d_grid_fix_: the table's fixed-point shadow (two int64 per entry) for what bypasses the lists
-    void *d_grid_lists_ = nullptr, *d_grid_counters_ = nullptr, *d_grid_bin_entry0_ = nullptr, *d_grid_fix_ = nullptr;
+    DevBuf<uint2> d_grid_lists_;
+    DevBuf<uint32_t> d_grid_counters_;
+    DevBuf<uint4> d_grid_bin_entry0_;
+    DevBuf<long long> d_grid_fix_;
     uint32_t grid_bin_first_[16] = {}, grid_bin_count_[16] = {}, grid_bin_cap_[16] = {}, grid_list0_[16] = {}, grid_bins_total_ = 0;
     bool attr_gather_set_ = false;
 
-    float *d_w_ = nullptr, *d_ema_ = nullptr, *d_m_ = nullptr, *d_v_ = nullptr, *d_grad_ = nullptr, *d_loss_ = nullptr;
+    DevBuf<float> d_w_, d_ema_, d_m_, d_v_, d_grad_;
+    float* d_loss_ = nullptr;            // inside d_grad_, behind the parameters
     std::vector<float> tcnn_dead_rows_[4];      // rows 3..15 of tiny-cuda-nn's 16 x width output matrix, per buffer 0..3
     // fp16 MFMA A-operand fragment images ([frag][lane][8 halfs]): inference (EMA), training forward, training dgrad (W^T)
-    void *d_pk_infer_[2] = {nullptr, nullptr}, *d_pk_fwd_ = nullptr, *d_pk_bwd_ = nullptr;
-    int32_t *d_src_fwd_ = nullptr, *d_src_bwd_ = nullptr;   // packed slot -> canonical index (-1 = zero)
-    int32_t* d_dst_ = nullptr;           // [3][n_mlp_] parameter -> slot in the forward / EMA inference / backward image (k_opt_pack)
+    DevBuf<void> d_pk_infer_[2], d_pk_fwd_, d_pk_bwd_;
+    DevBuf<int32_t> d_src_fwd_, d_src_bwd_;   // packed slot -> canonical index (-1 = zero)
+    DevBuf<int32_t> d_dst_;              // [3][n_mlp_] parameter -> slot in the forward / EMA inference / backward image (k_opt_pack)
     bool fused_opt_ = false;
     bool grad16_clean_ = false;          // d_grad16_ is all zero (the optimizer cleared what the last backward() touched)
     bool grid16_valid_ = false;          // the packed fp16 table gradient of the last backward() is what the optimizer should read
     int32_t* d_src_inf_ = nullptr;       // the same for the EMA inference image (= d_src_fwd_ unless enc80_generic_)
+    DevBuf<int32_t> d_src_inf_own_;      // what d_src_inf_ points at when it is not d_src_fwd_
     bool enc80_generic_ = false;         // generic model whose EMA inference encodes Frequency(12)+OneBlob(4) inside k_infer_gen
     uint32_t n_frag_fwd_ = 0, n_frag_bwd_ = 0;
 
     // training workspace
     uint32_t ws_n_ = 0;
-    void* d_acts_ = nullptr;     // fp16 [enc + depth*width][n]   (transposed: neuron-major)
-    void* d_deltas_ = nullptr;   // fp16 [depth*width + 32][n]
-    float* d_slabs_ = nullptr;   // fp32 [n_chunks][n_params]
-    float* d_loss_part_ = nullptr;
-    void* d_tiles_ = nullptr;    // WgradTile[] (output tiles of the weight-gradient GEMMs)
+    DevBuf<void> d_acts_;        // fp16 [enc + depth*width][n]   (transposed: neuron-major)
+    DevBuf<void> d_deltas_;      // fp16 [depth*width + 32][n]
+    DevBuf<float> d_slabs_;      // fp32 [n_chunks][n_params]
+    DevBuf<float> d_loss_part_;
+    DevBuf<void> d_tiles_;       // WgradTile[] (output tiles of the weight-gradient GEMMs)
     int n_wgrad_tiles_ = 0;
-    void* d_tasks_ = nullptr;    // WgradTask[] (row-block tasks of k_wgrad2)
+    DevBuf<void> d_tasks_;       // WgradTask[] (row-block tasks of k_wgrad2)
     int n_wgrad_tasks_ = 0;
     bool wgrad_old_ = false;     // round 3's k_wgrad (up to 64 neurons; NRC_DEBUG=wgrad_old=0|1)
     void build_wgrad_tasks();

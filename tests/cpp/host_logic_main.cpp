@@ -1,7 +1,8 @@
-// host_logic_main.cpp -- the library's device-free host logic (csrc/nrc_schedule.hpp, nrc_checkpoint.hpp, nrc_occupancy.hpp) driven on
+// host_logic_main.cpp -- the library's device-free host logic (csrc/nrc_schedule.hpp, nrc_checkpoint.hpp, nrc_occupancy.hpp, nrc_owned.hpp) driven on
 // the CPU; tests/test_host_logic_asan.py builds this with AddressSanitizer + UndefinedBehaviorSanitizer and runs it.
 //   host_logic_main <scratch directory> <path of nrc-hpm-renderer_amd/schedules.txt>
 // Every CHECK compares a value; the last line printed is "host_logic: <n> cases, <m> checks" (exit status 1 if any check failed).
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,6 +13,7 @@
 
 #include "../../nrc-hpm-renderer_amd/csrc/nrc_checkpoint.hpp"
 #include "../../nrc-hpm-renderer_amd/csrc/nrc_occupancy.hpp"
+#include "../../nrc-hpm-renderer_amd/csrc/nrc_owned.hpp"
 #include "../../nrc-hpm-renderer_amd/csrc/nrc_schedule.hpp"
 
 using namespace nrc;
@@ -563,6 +565,143 @@ static void key_cases(const char* schedules_txt)
     CHECK(schedule_key("gfx942", 304, 4, cfg, 1, 960, 1080, 1920, 1080, 4096, 8) == "gfx942:304cu:4xcd|pos0.dir2.w32.d4.hg15|vol2^0|960x1080.of1920x1080|train4x4096.len8");
 }
 
+// ---- nrc_owned.hpp: the link seam -- dev_alloc / dev_free of this program, over malloc / free with a live count, a log of the calls
+// ('a' allocation requested, 'f' free) and a switch that fails the next allocation
+static int g_live = 0;
+static bool g_fail_next_alloc = false;
+static std::string g_alloc_log;
+namespace nrc {
+void dev_alloc(void** p, size_t bytes, const char*)
+{
+    g_alloc_log += 'a';
+    if (g_fail_next_alloc) { g_fail_next_alloc = false; fail("out of memory (the test's)"); }
+    *p = std::malloc(bytes ? bytes : 1);
+    g_live++;
+}
+void dev_free(void* p)
+{
+    if (!p) return;
+    g_alloc_log += 'f';
+    g_live--;
+    std::free(p);
+}
+}  // namespace nrc
+static int g_destroyed[64];
+static void count_destroy(int h) { g_destroyed[h]++; }
+using CountedHandle = nrc::Owned<int, count_destroy>;
+
+static void owned_cases()
+{
+    using nrc::DevBuf;
+    const int live0 = g_live;
+    begin_case("owned: move construct");
+    {
+        DevBuf<float> a;
+        CHECK(!a && a.get() == nullptr);
+        a.alloc(64, "a");
+        float* const p = a;
+        CHECK(a && p != nullptr && g_live == live0 + 1);
+        DevBuf<float> b(std::move(a));
+        CHECK(!a && a.get() == nullptr && b.get() == p && g_live == live0 + 1);
+    }
+    CHECK(g_live == live0);      // (a second release of p: the sanitizer's double free as well)
+    begin_case("owned: move assign");
+    {
+        DevBuf<char> a, b;
+        a.alloc(16, "a");
+        b.alloc(32, "b");
+        char* const pb = b;
+        g_alloc_log.clear();
+        a = std::move(b);
+        CHECK(g_alloc_log == "f" && g_live == live0 + 1);      // the target's old buffer went, nothing else
+        CHECK(a.get() == pb && !b);
+    }
+    CHECK(g_live == live0);
+    begin_case("owned: self-move-assign");
+    {
+        DevBuf<int> a;
+        a.alloc(8, "a");
+        int* const p = a;
+        DevBuf<int>& same = a;
+        g_alloc_log.clear();
+        a = std::move(same);
+        CHECK(a.get() == p && g_alloc_log.empty() && g_live == live0 + 1);
+        std::memset(g_destroyed, 0, sizeof g_destroyed);
+        CountedHandle h(7);
+        CountedHandle& same_h = h;
+        h = std::move(same_h);
+        CHECK(h.get() == 7 && g_destroyed[7] == 0);
+    }
+    CHECK(g_live == live0 && g_destroyed[7] == 1);
+    begin_case("owned: alloc on a full buffer");
+    {
+        DevBuf<void> a;
+        a.alloc(16, "a");
+        g_alloc_log.clear();
+        a.alloc(4096, "a");
+        CHECK(g_alloc_log == "fa" && a && g_live == live0 + 1);      // released BEFORE the new one is requested
+        std::memset(a, 0xA5, 4096);
+        CHECK(((const unsigned char*)a)[4095] == 0xA5);      // (the cast a DevBuf<void>'s reader writes)
+        a.reset();
+        CHECK(!a && g_live == live0);
+        a.reset();
+        CHECK(g_live == live0);
+    }
+    begin_case("owned: failing allocation");
+    {
+        DevBuf<float> a;
+        g_fail_next_alloc = true;
+        CHECK(has(message_of([&] { a.alloc(16, "a"); }), "out of memory"));
+        CHECK(!a && g_live == live0);
+        a.alloc(16, "a");
+        g_fail_next_alloc = true;
+        g_alloc_log.clear();
+        CHECK(has(message_of([&] { a.alloc(32, "a"); }), "out of memory"));
+        CHECK(g_alloc_log == "fa" && !a && a.get() == nullptr && g_live == live0);      // empty, not dangling
+    }
+    CHECK(g_live == live0);
+    begin_case("owned: partially built object");
+    {
+        struct Two {
+            DevBuf<float> first, second;
+            explicit Two(bool fail_between)
+            {
+                first.alloc(16, "first");
+                if (fail_between) nrc::fail("the constructor's own check");
+                second.alloc(16, "second");
+            }
+        };
+        CHECK(has(message_of([] { Two t(true); }), "the constructor's own check"));
+        CHECK(g_live == live0);
+        g_alloc_log.clear();
+        CHECK(message_of([] { Two t(false); }).empty());
+        CHECK(g_alloc_log == "aaff" && g_live == live0);
+        struct FailsInSecond {
+            DevBuf<float> first, second;
+            FailsInSecond() { first.alloc(16, "first"); g_fail_next_alloc = true; second.alloc(16, "second"); }
+        };
+        CHECK(has(message_of([] { FailsInSecond t; }), "out of memory"));
+        CHECK(g_live == live0);
+    }
+    begin_case("owned: vector regrow");
+    {
+        std::memset(g_destroyed, 0, sizeof g_destroyed);
+        {
+            std::vector<std::array<CountedHandle, 10>> pool;
+            for (int set = 0; set < 5; set++) {      // (capacity 1, 2, 4, 8: three regrows move every array)
+                std::array<CountedHandle, 10> fresh;
+                for (int k = 0; k < 10; k++) fresh[k] = CountedHandle(1 + set * 10 + k);
+                pool.push_back(std::move(fresh));
+                pool.shrink_to_fit();      // every push regrows
+            }
+            for (int h = 1; h <= 50; h++) CHECK(g_destroyed[h] == 0);
+            CHECK(pool[4][9].get() == 50 && pool[0][0] == 1);
+        }
+        CHECK(g_destroyed[0] == 0);      // the empty state is never destroyed
+        for (int h = 1; h <= 50; h++) CHECK(g_destroyed[h] == 1);
+    }
+}
+
 int main(int argc, char** argv)
 {
     if (argc != 3) { std::printf("usage: host_logic_main <scratch directory> <schedules.txt>\n"); return 2; }
@@ -572,6 +711,7 @@ int main(int argc, char** argv)
     occupancy_cases();
     tuner_cases();
     key_cases(argv[2]);
+    owned_cases();
     std::printf("host_logic: %d cases, %d checks%s\n", g_cases, g_checks, g_failed ? ", FAILED" : "");
     return g_failed ? 1 : 0;
 }

@@ -1,15 +1,16 @@
 """Sanitizer run of the library's device-free host logic (VERDICT.md weak point 15): the schedule-cache text parser, the schedule key, the
 event-pool bookkeeping and the schedule tuner (csrc/nrc_schedule.hpp), the checkpoint file reader / writer (nrc_checkpoint.hpp) and the
-occupancy builders (nrc_occupancy.hpp) are plain C++17 that nrc_api.hip includes; tests/cpp/host_logic_main.cpp drives them on the CPU
-under ASan + UBSan (no recovery) -- the tuner against a scripted clock, reset in mid-trial and event-pool wrap included."""
+occupancy builders (nrc_occupancy.hpp) and the move-only owners of handles and device memory (nrc_owned.hpp) are plain C++17 that
+nrc_api.hip includes; tests/cpp/host_logic_main.cpp drives them on the CPU under ASan + UBSan (no recovery) -- the tuner against a
+scripted clock, reset in mid-trial and event-pool wrap included; the owners against an allocator of the program's own."""
 import os
 import re
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "nrc-hpm-renderer_amd", "csrc")
-HOST_HEADERS = ["nrc_fail.hpp", "nrc_schedule.hpp", "nrc_checkpoint.hpp", "nrc_occupancy.hpp"]
-CASES = 20      # begin_case calls of host_logic_main.cpp
+HOST_HEADERS = ["nrc_fail.hpp", "nrc_owned.hpp", "nrc_schedule.hpp", "nrc_checkpoint.hpp", "nrc_occupancy.hpp"]
+CASES = 27      # begin_case calls of host_logic_main.cpp
 
 
 def test_host_headers_compile_without_rocm():
