@@ -1147,3 +1147,61 @@ def test_schedule_cache_file_roundtrip(api, sc, cloud16, torch_gpu, tmp_path):
     api.clear_schedule_cache()
     with pytest.raises(RuntimeError, match="cannot read schedule cache"):
         api.load_schedule_cache(str(tmp_path / "missing.txt"))
+
+
+def _raw_buffer(api, ren, which):
+    """nrc_renderer_buffer(which) through raw ctypes: (pointer, bytes, host copy as uint32 words), or the error text when it fails"""
+    import ctypes as C
+    import torch
+    n = C.c_size_t(0)
+    p = ren.L.nrc_renderer_buffer(ren.h, C.c_int(which), C.byref(n))
+    if not p:
+        return ren.L.nrc_last_error().decode()
+    return p, n.value, api._wrap_device(p, n.value, torch.int32, (n.value // 4,)).cpu().numpy().view(np.uint32).copy()
+
+
+def test_per_set_buffer_ids_name_the_last_frames_set(api, sc, cloud16, torch_gpu):
+    """nrc_renderer_buffer ids 0-4 mean "the last rendered frame's gen_rays set", and that set is (frames - 1) % n_sets: after every one
+    of n_sets + 2 trained frames (the sets wrap once) ids 0-3 are the very buffers of ids 16 * (set + 1) + 0..3, id 4 holds what the set's
+    id holds, and every id has the size its element type and count give.  Before the first frame the ids mean set 0."""
+    W, H = 128, 80
+    px = W * H
+    scene = sc.make_scene(cloud16, scene_id=4)
+    cfg, nrc, cam, ren = _nrc_setup(api, sc, scene, W, H)
+    n_sets = 0
+    while n_sets < 64 and not isinstance(_raw_buffer(api, ren, 16 * (n_sets + 1)), str):
+        n_sets += 1
+    assert 2 <= n_sets < 64 and "bad buffer id" in _raw_buffer(api, ren, 16 * (n_sets + 1))
+    tg = ren.TrainGrid()
+    T = tg["tw"] * tg["th"]
+    sizes = [px * 16, px * 4, px * 16, px * 16, px * 20, px * 12, T * 20, T * 12, 8 + max(T, tg["ring_size"]) * 24]
+
+    def check(cur):
+        for i in range(4):
+            p, n, _ = _raw_buffer(api, ren, i)
+            ps, ns, _ = _raw_buffer(api, ren, 16 * (cur + 1) + i)
+            assert (p, n) == (ps, ns), (cur, i)
+        _, n, q = _raw_buffer(api, ren, 4)
+        _, ns, qs = _raw_buffer(api, ren, 16 * (cur + 1) + 4)
+        assert n == ns and np.array_equal(q, qs), cur
+        assert [_raw_buffer(api, ren, i)[1] for i in range(9)] == sizes
+
+    check(0)                                            # before the first frame: set 0
+    frs = sc.frame_randoms(n_sets + 2, seed=11)
+    seen = []
+    for N in range(1, n_sets + 3):
+        ren.SetFrameRandom(frs[N - 1])
+        ren.Render(None, True)
+        check((N - 1) % n_sets)
+        seen.append(_raw_buffer(api, ren, 0)[0])
+    assert len(set(seen[:n_sets])) == n_sets and seen[n_sets:] == seen[:2]      # every set once, then round again
+    assert "buffers 9-11 belong to a self-training renderer" in _raw_buffer(api, ren, 9)
+    ren.Destroy()
+    nrc.Destroy()
+    cfg, nrc, cam, ren = _nrc_setup(api, sc, scene, W, H, self_train=1)
+    ren.SetFrameRandom(frs[0])
+    ren.Render(None, True)
+    spp = cfg.c.train_spp
+    assert [_raw_buffer(api, ren, i)[1] for i in (9, 10, 11)] == [T * spp * 20, T * spp * 16, T * spp * 12]
+    ren.Destroy()
+    nrc.Destroy()
