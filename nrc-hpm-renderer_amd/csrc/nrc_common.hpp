@@ -38,7 +38,7 @@ inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 // ---- THE environment switch of the product build: NRC_DEBUG="name[=value],name[=value],..." --------------------------------------------
 // Diagnostic and test switches only -- nothing a host needs in order to use the library, nothing that changes a result (the tests that set
 // them compare the two sides bit for bit).  Read when the object that consults it is created (a cache, a renderer), so a test can change
-// it between two objects of one process.  (-DNRC_DIAG builds add the NRC_INFER_* shape sweeps of tools/bench_mlp.py.)
+// it between two objects of one process.
 //   poison_alloc        every device allocation is filled with 0xFF bytes at creation (fp32 / fp16 NaN, index 0xFFFFFFFF): what a kernel reads
 //                       without anyone having written it shows up instead of hiding behind the zeros of a freshly booted box
 //   guard_alloc         4 KiB of 0xA5 canaries around every allocation; nrc_debug_check_guards() and every free verify them
@@ -46,7 +46,6 @@ inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 //   single_stream       the renderer's frame on ONE stream in the reference's order (the four-stream graph must equal it bit for bit)
 //   no_live_list        renderer inference over the whole query buffer instead of the frame's live-query list
 //   zero_dead_queries   gen_rays writes the zero queries of pixels that did not scatter (the reference's zero-filled buffer)
-//   fused_composite     compositing as the epilogue of the inference launch (6 x 64 model; measured slower in the frame)
 //   dense_grid_exchange the HashGrid table gradient through the dense all-reduce instead of the all-gathered lists
 //   no_fused_opt        three optimizer launches (k_adam_ema / k_sgd_ema, k_pack, k_pack_grid) instead of the fused ones (k_opt_pack, k_grid_opt2)
 //   grid_no_bins        every pair of the table gradient through the fixed-point shadow (no per-bin lists)
@@ -208,12 +207,8 @@ struct Pcg32 {
 namespace nrc {
 static __device__ int g_raise_wave_priority = 1;
 }
-#ifdef NRC_NO_PRIORITY_SWITCH      // A/B build: the raise unconditional, as before the switch
-#define NRC_RAISE_WAVE_PRIORITY(bit) do { if (!((NRC_DIAG_LOWPRIO) & (bit))) __builtin_amdgcn_s_setprio(NRC_WAVE_PRIORITY); } while (0)
-#else
 #define NRC_RAISE_WAVE_PRIORITY(bit)                                                                    \
     do {                                                                                                \
         if (!((NRC_DIAG_LOWPRIO) & (bit)) && nrc::g_raise_wave_priority != 0) __builtin_amdgcn_s_setprio(NRC_WAVE_PRIORITY); \
     } while (0)
-#endif
 #endif

@@ -21,17 +21,6 @@
 #include "nrc_math.h"
 #include "nrc_volume_keys.hpp"
 
-// 1: the tracking loops carry their predicates as uniform 64-bit lane masks (round 4); 0: as per-lane bools (round 3)
-// 1: every look-up tests the LDS occupancy bits unconditionally; 0 (product): behind a wave-uniform test for the table, as in round 3.
-// Round 4 measured both: without the test k_gen_rays is 1 % faster alone (0.2092 against 0.2117 ms: one branch and four mask merges
-// fewer per trip) and 12 % faster inside the configs[4] frame (0.283 against 0.318 ms) -- and the FRAMES are slower, 7 730 against 7 850
-// Msamples/s on the default preset and 4 160 against 4 810 on configs[4]: a camera kernel that issues more densely leaves the
-// inference / training kernels beside it fewer issue slots (train stage 0.18 -> 0.23 ms, configs[4] train rays 0.53 -> 0.98 ms), and
-// those set the frame rate wherever they are the longer chain.  (tools/ab_config.sh, same box, lib / lib_o0 / lib_m0o0 / round 3's.)
-#ifndef NRC_OCC_ALWAYS
-#define NRC_OCC_ALWAYS 0
-#endif
-// 1 (product): software-pipelined, predicated tracking loops; 0 (diagnostic A/B build): the plain two-collision loops
 // waves per SIMD the camera kernels are register-allocated for
 #ifndef NRC_CAMERA_WAVES_PER_SIMD
 #define NRC_CAMERA_WAVES_PER_SIMD 5
@@ -168,9 +157,6 @@ struct CtxT {
 #ifdef NRC_LOOP_PROFILE
     uint32_t useful[8] = {0, 0, 0, 0, 0, 0, 0, 0}, issued[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t fee_kind = 1;
-#endif
-#ifdef NRC_DIAG_CUT_TAIL2
-    uint32_t cut2 = 0;      // DIAGNOSTIC (wrong frames): the second vertex's delta walk stops when at most this many lanes still walk
 #endif
     __device__ __forceinline__ float rand(float max_val)
     {
@@ -341,11 +327,15 @@ __device__ __forceinline__ Addr2 fetch2_addr(const C& c, V3 dir, V3 start, float
     const uint32_t x1 = (uint32_t)fx.y, y1 = (uint32_t)fy.y, z1 = (uint32_t)fz.y;
     const uint32_t idx0 = index24(z0, s.ny, y0, s.nx, x0);
     const uint32_t idx1 = index24(z1, s.ny, y1, s.nx, x1);
-#if !NRC_OCC_ALWAYS
-    if (c.occ != nullptr)
-#endif
-    {      // occupancy bit of the voxel's cell from LDS: an empty cell's byte is 0 without asking memory.  (The table always exists --
-           // Scene::build_occupancy_bits; all ones under NRC_NO_OCCUPANCY.)
+    // The LDS occupancy bits are tested behind a wave-uniform test for the table, as in round 3.  Round 4 measured both: without the test
+    // k_gen_rays is 1 % faster alone (0.2092 against 0.2117 ms: one branch and four mask merges fewer per trip) and 12 % faster inside the
+    // configs[4] frame (0.283 against 0.318 ms) -- and the FRAMES are slower, 7 730 against 7 850 Msamples/s on the default preset and 4 160
+    // against 4 810 on configs[4]: a camera kernel that issues more densely leaves the inference / training kernels beside it fewer issue
+    // slots (train stage 0.18 -> 0.23 ms, configs[4] train rays 0.53 -> 0.98 ms), and those set the frame rate wherever they are the
+    // longer chain.  (tools/ab_config.sh, same box, lib / lib_o0 / lib_m0o0 / round 3's.)
+    if (c.occ != nullptr) {
+        // occupancy bit of the voxel's cell from LDS: an empty cell's byte is 0 without asking memory.  (The table always exists --
+        // Scene::build_occupancy_bits.)
         const uint32_t sh = s.occ_shift;
         uint32_t c0 = index24(z0 >> sh, s.occ_gy, y0 >> sh, s.occ_gx, x0 >> sh);
         uint32_t c1 = index24(z1 >> sh, s.occ_gy, y1 >> sh, s.occ_gx, x1 >> sh);
@@ -451,7 +441,7 @@ __device__ __forceinline__ RatioTrip ratio_trip(float rng, float t, float t_max,
 }
 // ---- thin trips: two lanes per surviving walk ---------------------------------------------------------------------------------
 // A tracking loop runs until its last walk ends: the trips issued with at most 32 of the 64 lanes still walking cost 28 % of the
-// launch (NRC_DIAG_CUT_TAIL).  When a loop is down to 32 walks or fewer they are handed to lane PAIRS (lane p and p + 32, state pushed
+// launch (round 2's cut-tail build, docs/MEASUREMENT_LOG.md).  When a loop is down to 32 walks or fewer they are handed to lane PAIRS (lane p and p + 32, state pushed
 // there with ds_permute): an iteration then advances a walk by FOUR collisions -- the hash chain is drawn by both lanes (it is the
 // only serial part, a quarter of a trip's instructions), the two free-flight logs, positions, look-ups and transmittance factors
 // of collisions 1, 2 are lane p's work and those of 3, 4 lane p + 32's, exchanged with v_permlane32_swap, and the free-flight sums
@@ -574,11 +564,7 @@ __device__ __forceinline__ float ratio_track(C& c, V3 start, V3 end, bool valid 
     for (uint32_t i = 0;; i += 2) {            // i counts collisions: at most 128 (path_trace.glsl:34)
         rng = lane_bool(alive_m & ~live1_m) ? a.s1 : rng;             // collision 1 beyond the segment: the walk ends on this draw
         alive_m &= live1_m;
-#ifdef NRC_DIAG_CUT_TAIL
-        if (__popcll(alive_m) <= NRC_DIAG_CUT_TAIL) break;      // DIAGNOSTIC (wrong frames): what the trips with few live lanes cost
-#else
         if (alive_m == 0ull) break;
-#endif
         if constexpr (UNI) {
             if (__popcll(alive_m) <= 31) {        // few walks left: two lanes each (ratio_pairs; lanes 31 and 63 stay free as push targets)
                 ratio_pairs(c, alive_m, lane_bool(alive_m), start, dir, t_max, inv, bs, bt, i, tr, rng);
@@ -750,14 +736,7 @@ __device__ __forceinline__ V3 delta_track(C& c, V3 ro, V3 rd, bool* volume_exit,
         rng = lane_bool(out1_m) ? a.s1 : rng;
         vexit_m |= out1_m;
         alive_m &= live1_m;
-#ifdef NRC_DIAG_CUT_TAIL
-        if (__popcll(alive_m) <= NRC_DIAG_CUT_TAIL) break;      // DIAGNOSTIC (wrong frames): what the trips with few live lanes cost
-#else
         if (alive_m == 0ull) break;
-#endif
-#ifdef NRC_DIAG_CUT_TAIL2
-        if ((uint32_t)__popcll(alive_m) <= c.cut2) break;      // DIAGNOSTIC (wrong frames): the same for the second vertex's delta walk alone
-#endif
         const bool alive = lane_bool(alive_m);
         if (alive) NRC_PROF(c, 2);
         NRC_PROF_LIVE(2, alive_m);
@@ -1148,9 +1127,6 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK, NRC_GEN_WAVES_PER_SIMD
     for (int i = 0;; i++) {
         if (__ballot(walking) == 0ull) break;
         bool vexit = false;
-#ifdef NRC_DIAG_CUT_TAIL2
-        c.cut2 = i >= 1 ? (uint32_t)(NRC_DIAG_CUT_TAIL2) : 0u;
-#endif
         const V3 nc = delta_track<true>(c, cur, dir, &vexit, walking);
         cur = sel(walking, nc, cur);
         walking &= !vexit;

@@ -289,25 +289,7 @@ __device__ __forceinline__ void stage_lds(uint4* dst, const uint4* src, int n16,
 // ------------------------------------------------------------------------------------------------ inference
 // forward chain for NT independent 32-sample tiles of one wave: every weight fragment read from LDS feeds NT MFMAs, and
 // the ReLU/convert VALU work of one tile overlaps the MFMAs of the other inside the wave (in-order issue needs the ILP).
-// ABL (diagnostic builds only, never the default): bit 0 = trivial encoding, bit 1 = no ReLU/convert work
-template <int ABL>
-__device__ __forceinline__ void relu_pack_abl(const f32x16& acc, half8& lo, half8& hi)
-{
-    if constexpr ((ABL & 2) != 0) {
-        uint4v l = {__builtin_bit_cast(uint32_t, acc[0]), __builtin_bit_cast(uint32_t, acc[1]),
-                    __builtin_bit_cast(uint32_t, acc[2]), __builtin_bit_cast(uint32_t, acc[3])};
-        uint4v h = {__builtin_bit_cast(uint32_t, acc[8]), __builtin_bit_cast(uint32_t, acc[9]),
-                    __builtin_bit_cast(uint32_t, acc[10]), __builtin_bit_cast(uint32_t, acc[11])};
-        lo = __builtin_bit_cast(half8, l);
-        hi = __builtin_bit_cast(half8, h);
-    } else {
-        relu_pack(acc, lo, hi);
-    }
-}
-
-// forward chain for NT independent 32-sample tiles of one wave: every weight fragment read from LDS feeds NT MFMAs, and
-// the ReLU/convert VALU work of one tile can overlap the MFMAs of the other inside the wave (in-order issue needs the ILP).
-template <int DEPTH, int NT, int ABL, int S>
+template <int DEPTH, int NT, int S>
 __device__ __forceinline__ void layer0_steps(const uint4* lw, int lane, int h, const float (&x)[NT][5], f32x16 (&acc0)[NT], f32x16 (&acc1)[NT])
 {
     if constexpr (S < KS0) {
@@ -315,32 +297,26 @@ __device__ __forceinline__ void layer0_steps(const uint4* lw, int lane, int h, c
         const half8 a1 = ld_frag(lw, FRAG_L0 + KS0 + S, lane);
 #pragma unroll
         for (int t = 0; t < NT; t++) {
-            half8 bs;
-            if constexpr ((ABL & 1) != 0) {
-#pragma unroll
-                for (int j = 0; j < 8; j++) bs[j] = (half_t)x[t][(S + j) % 5];
-            } else {
-                bs = encode80_frag<S>(x[t], h);
-            }
+            const half8 bs = encode80_frag<S>(x[t], h);
             acc0[t] = mfma(a0, bs, acc0[t]);
             acc1[t] = mfma(a1, bs, acc1[t]);
         }
-        layer0_steps<DEPTH, NT, ABL, S + 1>(lw, lane, h, x, acc0, acc1);
+        layer0_steps<DEPTH, NT, S + 1>(lw, lane, h, x, acc0, acc1);
     }
 }
 
-template <int DEPTH, int NT, int ABL = 0>
+template <int DEPTH, int NT>
 __device__ __forceinline__ void forward_tiles(const uint4* lw, int lane, int h, const float (&x)[NT][5], f32x16 (&y)[NT])
 {
     f32x16 acc0[NT], acc1[NT];
     half8 b[NT][KSH];
 #pragma unroll
     for (int t = 0; t < NT; t++) { acc0[t] = zero16(); acc1[t] = zero16(); }
-    layer0_steps<DEPTH, NT, ABL, 0>(lw, lane, h, x, acc0, acc1);      // the encoding is built fragment by fragment beside the MFMAs
+    layer0_steps<DEPTH, NT, 0>(lw, lane, h, x, acc0, acc1);      // the encoding is built fragment by fragment beside the MFMAs
 #pragma unroll
     for (int t = 0; t < NT; t++) {
-        relu_pack_abl<ABL>(acc0[t], b[t][0], b[t][1]);
-        relu_pack_abl<ABL>(acc1[t], b[t][2], b[t][3]);
+        relu_pack(acc0[t], b[t][0], b[t][1]);
+        relu_pack(acc1[t], b[t][2], b[t][3]);
     }
 #pragma unroll
     for (int l = 1; l < DEPTH; l++) {
@@ -359,8 +335,8 @@ __device__ __forceinline__ void forward_tiles(const uint4* lw, int lane, int h, 
         }
 #pragma unroll
         for (int t = 0; t < NT; t++) {
-            relu_pack_abl<ABL>(acc0[t], b[t][0], b[t][1]);
-            relu_pack_abl<ABL>(acc1[t], b[t][2], b[t][3]);
+            relu_pack(acc0[t], b[t][0], b[t][1]);
+            relu_pack(acc1[t], b[t][2], b[t][3]);
         }
     }
 #pragma unroll
@@ -382,57 +358,21 @@ __device__ __forceinline__ void forward_tiles(const uint4* lw, int lane, int h, 
 // this one at every batch size, so the simpler order stayed.)
 // persistent workgroups; NT 32-sample tiles per wave per iteration; the next iteration's queries are loaded (20 B per
 // sample, straight from HBM/L2 into registers) before the current tiles are computed, so their latency is hidden.
-// nrc/render.comp:23-41 for the pixel of query q (tile-major order): c = primary.rgb + (showNrc && scattered ? max(0, nrc) * primary.w : 0),
-// out = blend * c + (1 - blend) * out_prev, alpha likewise towards 1.  The arithmetic is k_composite's, operation for operation
-// and without contraction, so the fused and the separate pass give the same bits.
-__device__ __forceinline__ void composite_query(const CompositeArgs& ca, uint32_t q, float nr, float ng, float nb)
-{
-#pragma clang fp contract(off)
-    const uint32_t tiles_x = (ca.w + 7u) >> 3;
-    const uint32_t tile = q >> 6, in_tile = q & 63u;
-    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const uint32_t lx = tx * 8u + (in_tile & 7u), y = ty * 8u + (in_tile >> 3);
-    if (lx >= ca.w || y >= ca.h) return;
-    const size_t pix = (size_t)y * ca.w + lx;
-    const float4 p = reinterpret_cast<const float4*>(ca.primary)[pix];
-    float cr = p.x, cg = p.y, cb = p.z;
-    if (ca.show_nrc == 1u && ca.info[pix] == 1.0f) {
-        cr += fmaxf(0.0f, nr) * p.w;
-        cg += fmaxf(0.0f, ng) * p.w;
-        cb += fmaxf(0.0f, nb) * p.w;
-    }
-    float4* fb = reinterpret_cast<float4*>(ca.framebuffer) + pix;
-    const float4 prev = *fb;
-    const float ib = 1.0f - ca.blend_factor;
-    *fb = make_float4(ca.blend_factor * cr + ib * prev.x, ca.blend_factor * cg + ib * prev.y,
-                      ca.blend_factor * cb + ib * prev.z, ca.blend_factor * 1.0f + ib * prev.w);
-}
-
-template <int DEPTH, int THREADS, int NT, int ABL = 0, bool FUSE = false, bool LISTED = false>
+template <int DEPTH, int THREADS, int NT, bool LISTED = false>
 // (second launch bound.  With ONE wave per SIMD the compiler assumes the 512-register budget is split into 256 architectural + 256
 // accumulation registers, puts the MFMA accumulators into AGPRs and copies every one of them out with v_accvgpr_read_b32 before the
 // ReLU / pack: 384 of the 1 346 instructions of the renderer-mode loop of the 4-wave form.  Two waves per SIMD = 256 registers, all
 // architectural on this target: 122 of them, no copies, 29 % fewer instructions -- and the default preset's frame 1.9 % SLOWER (8 125 ->
 // 7 980 Msamples/s, three alternating runs: gen_rays 0.234 -> 0.238 ms beside the denser kernel; the frame is a balance, DESIGN.md
-// section 4).  NRC_INFER_MIN_WAVES=2 builds it.  The generic kernels -- k_infer_gen, k_train_gen2, k_wgrad2 -- do ask for two: configs[4]
-// + 1 %, HashGrid + 0.6 %.)
-#ifndef NRC_INFER_MIN_WAVES
-#define NRC_INFER_MIN_WAVES 1
-#endif
-__global__ __launch_bounds__(THREADS, THREADS == 512 && NT == 2 ? 4 : NRC_INFER_MIN_WAVES) void k_infer(const float* __restrict__ in, float* __restrict__ out, uint32_t n,
-                                                  const uint4* __restrict__ image, unsigned long long* __restrict__ stamps = nullptr,
-                                                  int skip_zero = 0, CompositeArgs ca = CompositeArgs{},
+// section 4).  The generic kernels -- k_infer_gen, k_train_gen2, k_wgrad2 -- do ask for two: configs[4] + 1 %, HashGrid + 0.6 %.)
+__global__ __launch_bounds__(THREADS, THREADS == 512 && NT == 2 ? 4 : 1) void k_infer(const float* __restrict__ in, float* __restrict__ out, uint32_t n,
+                                                  const uint4* __restrict__ image, int skip_zero = 0,
                                                   const uint32_t* __restrict__ live_list = nullptr,
                                                   const uint32_t* __restrict__ live_count = nullptr)
 {
     NRC_RAISE_WAVE_PRIORITY(1);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint4* lw = reinterpret_cast<uint4*>(smem);
-    unsigned long long t0 = 0, r0 = 0;
-    if constexpr ((ABL & 4) != 0) {     // diagnostic: shader clock vs 100 MHz wall clock (MI355X_MICROARCH.md DVFS item 6)
-        t0 = __builtin_amdgcn_s_memtime();
-        r0 = __builtin_amdgcn_s_memrealtime();
-    }
     stage_lds(lw, image, n_frag_fwd(DEPTH) * 64, threadIdx.x, THREADS);
 
     const int lane = threadIdx.x & 63;
@@ -443,14 +383,13 @@ __global__ __launch_bounds__(THREADS, THREADS == 512 && NT == 2 ? 4 : NRC_INFER_
     // pixel that did not scatter (the list-free renderer mode reads all 2 M queries of a 1080p frame and stores zeros for the dead
     // tiles: 66 MB), and the tiles that run are full (87 % on the bench cloud otherwise, tools/live_tiles.py).  Results are per query.
     // (LISTED is a template parameter: the list-free instantiations are the code they were)
-    constexpr bool listed = LISTED && !FUSE;
     uint32_t n_q = n;
-    if constexpr (listed) {
+    if constexpr (LISTED) {
         n_q = __builtin_amdgcn_readfirstlane((int)*live_count);
         n_q = n_q < n ? n_q : n;
     }
     auto query_of = [&](uint32_t sx) -> uint32_t {      // (slots beyond the end repeat the last query: in bounds, never stored)
-        if constexpr (listed) return live_list[sx < n_q ? sx : (n_q != 0u ? n_q - 1u : 0u)];
+        if constexpr (LISTED) return live_list[sx < n_q ? sx : (n_q != 0u ? n_q - 1u : 0u)];
         else return sx < n ? sx : n - 1u;
     };
     const uint32_t n_tiles = (n_q + 31u) >> 5;
@@ -466,8 +405,6 @@ __global__ __launch_bounds__(THREADS, THREADS == 512 && NT == 2 ? 4 : NRC_INFER_
         for (int i = 0; i < 5; i++) x[t][i] = __builtin_nontemporal_load(p + i);
     }
     __syncthreads();
-    unsigned long long r_staged = 0;
-    if constexpr ((ABL & 4) != 0) r_staged = __builtin_amdgcn_s_memrealtime();
     for (; tile < n_tiles; tile += stride) {
         // the weight image in LDS is loop invariant: keep hipcc from hoisting all 54 fragments (216 VGPRs) out of
         // the tile loop -- fragments are meant to be re-read from LDS, one ds_read_b128 per NT MFMAs
@@ -485,7 +422,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 512 && NT == 2 ? 4 : NRC_INFER_
         // renderer mode WITHOUT the live-query list: gen_rays writes an all-zero query for every pixel that did not scatter (the reference's
         // zero-filled slots, whose network output render.comp never reads); tiles made only of such queries skip the network and store 0
         bool live = true;
-        if (skip_zero && !listed) {
+        if (skip_zero && !LISTED) {
             bool nz = false;
 #pragma unroll
             for (int t = 0; t < NT; t++)
@@ -494,7 +431,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 512 && NT == 2 ? 4 : NRC_INFER_
             live = __ballot(nz) != 0ull;
         }
         if (live) {
-            forward_tiles<DEPTH, NT, ABL>(lw, lane, h, x, y);
+            forward_tiles<DEPTH, NT>(lw, lane, h, x, y);
         } else {
 #pragma unroll
             for (int t = 0; t < NT; t++) y[t] = zero16();
@@ -502,26 +439,17 @@ __global__ __launch_bounds__(THREADS, THREADS == 512 && NT == 2 ? 4 : NRC_INFER_
 #pragma unroll
         for (int t = 0; t < NT; t++) {
             const uint32_t sidx = (tile + t) * 32u + r;
-            if (sidx < n_q && h == 0 && ((ABL & 8) == 0 || sidx < 64u)) {
+            if (sidx < n_q && h == 0) {
                 // streamed once: non-temporal, so the 12 B/sample leave the L2 while the kernel runs instead of in the
                 // end-of-kernel write-back
-                float* o = out + (size_t)(listed ? qi[t] : sidx) * 3u;
+                float* o = out + (size_t)(LISTED ? qi[t] : sidx) * 3u;
                 __builtin_nontemporal_store(y[t][0], o);
                 __builtin_nontemporal_store(y[t][1], o + 1);
                 __builtin_nontemporal_store(y[t][2], o + 2);
-                if constexpr (FUSE) composite_query(ca, ca.q_base + sidx, y[t][0], y[t][1], y[t][2]);
             }
 #pragma unroll
             for (int i = 0; i < 5; i++) x[t][i] = xn[t][i];
             qi[t] = qn[t];
-        }
-    }
-    if constexpr ((ABL & 4) != 0) {
-        if (threadIdx.x == 0) {
-            stamps[4 * blockIdx.x] = __builtin_amdgcn_s_memtime() - t0;
-            stamps[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - r0;
-            stamps[4 * blockIdx.x + 2] = r0;
-            stamps[4 * blockIdx.x + 3] = r_staged - r0;
         }
     }
 }
@@ -882,14 +810,10 @@ __device__ __forceinline__ void hg_corners(const HashLevels& lv, uint32_t level,
 // corners x and x + 1 differ in bit 0 of the entry index only (dense: index + 1, hash: index ^ 1; level sizes and offsets are even) --
 // half of all (sample, level) pairs.  The test is made on the indices themselves (idx[c + 1] == idx[c] ^ 1), so nothing is assumed
 // about the level: a lane whose four x-pairs all pass does 4 gathers of 8 bytes, the others 4 + 4.  Same entries, same order of the
-// weighted sum -- bit-identical features, 25 % fewer lane-gathers.  (-DNRC_HG_NO_PAIR_GATHER is the A/B build.)
+// weighted sum -- bit-identical features, 25 % fewer lane-gathers.
 __device__ __forceinline__ void hg_gather(const uint32_t* __restrict__ table16, const uint32_t (&idx)[8], const float (&w8)[8], float& r0, float& r1)
 {
     uint32_t v[8];
-#ifdef NRC_HG_NO_PAIR_GATHER
-#pragma unroll
-    for (int c = 0; c < 8; c++) v[c] = table16[idx[c]];
-#else
     bool paired = true;
 #pragma unroll
     for (int c = 0; c < 8; c += 2) paired = paired && idx[c + 1] == (idx[c] ^ 1u);
@@ -905,7 +829,6 @@ __device__ __forceinline__ void hg_gather(const uint32_t* __restrict__ table16, 
         v[c] = hi ? a.y : a.x;
         v[c + 1] = paired ? (hi ? a.x : a.y) : u[c >> 1];
     }
-#endif
     r0 = 0.0f; r1 = 0.0f;
 #pragma unroll
     for (int c = 0; c < 8; c++) {
@@ -1354,19 +1277,13 @@ __device__ __forceinline__ half8 ld_frag_g(const uint4* __restrict__ img, int fr
 // barrier per layer, no staging registers, 0.5-1 KB of L2 traffic per sample.  Same accumulator-as-
 // operand chain and numerics as k_infer.  skip_in (renderer inference): tiles whose 32 queries are all zero are not computed,
 // a workgroup whose 256 queries are all zero does not even stream the weights.
-#ifndef NRC_GEN128_WPS
-#define NRC_GEN128_WPS 1
-#endif
-#ifndef NRC_GEN128_THREADS
-#define NRC_GEN128_THREADS 512
-#endif
 #ifndef NRC_GEN128_WG4_PER_CU
 #define NRC_GEN128_WG4_PER_CU 2      // persistent 4-wave workgroups per CU of the renderer-mode 128-wide inference launch
 #endif
 // ENC80: the input is the raw 5-float query and the Frequency(12) + OneBlob(4) encoding is computed here, k-step by k-step, as
 // k_infer does (no k_encode pass, no 160 B/sample feature buffer); feat is unused, raw_in required, the image is in fmap80 order.
 template <int WIDTH, int THREADS, bool FEAT_LM, int NT = 2, bool ENC80 = false>
-__global__ __launch_bounds__(THREADS, WIDTH == 128 && NRC_GEN128_WPS > 2 ? NRC_GEN128_WPS : 2) void k_infer_gen(const half_t* __restrict__ feat, float* __restrict__ out, uint32_t n,
+__global__ __launch_bounds__(THREADS, 2) void k_infer_gen(const half_t* __restrict__ feat, float* __restrict__ out, uint32_t n,
                                                       const uint4* __restrict__ img, int depth, int ks0,
                                                       const float* __restrict__ skip_in, const float* __restrict__ raw_in = nullptr,
                                                       const uint32_t* __restrict__ live_list = nullptr,
@@ -2805,20 +2722,13 @@ int Mlp::num_cus()
 
 template <int THREADS, int NT>
 static void launch_infer(uint32_t blocks, size_t lds, hipStream_t s, const float* d_in, float* d_out, uint32_t n, const uint4* img,
-                         int skip_zero, const CompositeArgs* composite = nullptr, const uint32_t* live_list = nullptr,
-                         const uint32_t* live_count = nullptr)
+                         int skip_zero, const uint32_t* live_list = nullptr, const uint32_t* live_count = nullptr)
 {
-    if (composite != nullptr) {
-        launch_last(k_infer<6, THREADS, NT, 0, true>, dim3(blocks), dim3(THREADS), (uint32_t)lds, s, d_in, d_out, n, img,
-                    (unsigned long long*)nullptr, skip_zero, *composite, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-        return;
-    }
     if (live_list != nullptr)
-        launch_last(k_infer<6, THREADS, NT, 0, false, true>, dim3(blocks), dim3(THREADS), (uint32_t)lds, s, d_in, d_out, n, img,
-                           (unsigned long long*)nullptr, skip_zero, CompositeArgs{}, live_list, live_count);
+        launch_last(k_infer<6, THREADS, NT, true>, dim3(blocks), dim3(THREADS), (uint32_t)lds, s, d_in, d_out, n, img, skip_zero, live_list, live_count);
     else
-        launch_last(k_infer<6, THREADS, NT>, dim3(blocks), dim3(THREADS), (uint32_t)lds, s, d_in, d_out, n, img,
-                           (unsigned long long*)nullptr, skip_zero, CompositeArgs{}, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
+        launch_last(k_infer<6, THREADS, NT>, dim3(blocks), dim3(THREADS), (uint32_t)lds, s, d_in, d_out, n, img, skip_zero,
+                    (const uint32_t*)nullptr, (const uint32_t*)nullptr);
 }
 
 // fp16 feature buffer of the generic path ([n][E16]); grows on demand (never inside a captured region: first use sizes it)
@@ -2830,12 +2740,11 @@ void Mlp::ensure_features(uint32_t n, int slot)
     feat_n_[slot] = n;
 }
 
-void Mlp::infer(const float* d_in, float* d_out, uint32_t n, bool use_ema, hipStream_t s, bool skip_zero_queries, const CompositeArgs* composite,
+void Mlp::infer(const float* d_in, float* d_out, uint32_t n, bool use_ema, hipStream_t s, bool skip_zero_queries,
                 const uint32_t* live_list, const uint32_t* live_count, int feat_slot)
 {
     if (n == 0) return;
     if (feat_slot != kInferSlot && feat_slot != kSideSlot) throw std::logic_error("SkyRenderer ERROR: bad inference feature slot");
-    if (composite != nullptr && !fused_) throw std::logic_error("SkyRenderer ERROR: compositing epilogue asked of a generic model");
     const uint4* img = (const uint4*)(use_ema ? d_pk_infer_[infer_set_] : d_pk_fwd_);
     if (!fused_) {
         // EMA inference of a Frequency(12) + OneBlob(4) model encodes inside the MLP kernel (image in the encoder's input order);
@@ -2888,128 +2797,34 @@ void Mlp::infer(const float* d_in, float* d_out, uint32_t n, bool use_ema, hipSt
                 else if (hash_) launch(k_infer_gen<128, T128, true, 1>, T128, lds, per_cu);
                 else launch(k_infer_gen<128, T128, false, 1>, T128, lds, per_cu);
             };
-#ifdef NRC_GEN128_THREADS_FORCED
-            launch128(std::integral_constant<int, NRC_GEN128_THREADS>{});
-#else
             if (skip_in != nullptr) launch128(std::integral_constant<int, 256>{});
             else launch128(std::integral_constant<int, 512>{});
-#endif
         }
         NRC_HIP(hipGetLastError());
         return;
     }
     // persistent workgroups sharing one 54 KB weight image in LDS: 8 waves x 2 tiles per iteration, two workgroups per CU.
-    // The shape sweeps and ablations that led here (256...1024 threads, 1...4 tiles, no-encode / no-ReLU variants, in-kernel
-    // clock stamps) exist only in the diagnostic build (make EXTRA=-DNRC_DIAG OUT=../lib_diag; tools/bench_mlp.py).
-    int threads = 512, nt = 2, bpc = 2;
-#ifdef NRC_DIAG
-    static const int e_threads = [] { const char* e = getenv("NRC_INFER_THREADS"); return e ? atoi(e) : 512; }();
-    static const int e_nt = [] { const char* e = getenv("NRC_INFER_NT"); return e ? atoi(e) : 2; }();
-    static const int e_bpc = [] { const char* e = getenv("NRC_INFER_BPC"); return e ? atoi(e) : 2; }();
-    threads = e_threads; nt = e_nt; bpc = e_bpc;
-#endif
+    // (The shape sweeps and ablations that led here -- 256...1024 threads, 1...4 tiles, no-encode / no-ReLU variants, in-kernel
+    // clock stamps -- are in docs/MEASUREMENT_LOG.md.)
     const uint32_t n_tiles = ceil_div(n, 32);
-    const uint32_t max_blocks = (uint32_t)num_cus() * (uint32_t)bpc;
-    uint32_t blocks = ceil_div(n_tiles, (uint32_t)(threads / 64) * (uint32_t)nt);
-    if (blocks > max_blocks) blocks = max_blocks;
+    const uint32_t cap = (uint32_t)num_cus() * 2u;
     const size_t lds = (size_t)n_frag_fwd_ * 1024;
     const int sz = skip_zero_queries ? 1 : 0;
-#ifdef NRC_DIAG
-    static const int abl = [] { const char* e = getenv("NRC_INFER_ABL"); return e ? atoi(e) : 0; }();
-    if (abl != 0) {       // ablations / in-kernel clock: tools/bench_mlp.py
-        infer_diagnostic(abl, blocks, lds, s, d_in, d_out, n, img);
-        return;
-    }
-    if (threads == 1024 && nt == 1) launch_infer<1024, 1>(blocks, lds, s, d_in, d_out, n, img, sz);
-    else if (threads == 256 && nt == 1) launch_infer<256, 1>(blocks, lds, s, d_in, d_out, n, img, sz);
-    else if (threads == 256 && nt == 2) launch_infer<256, 2>(blocks, lds, s, d_in, d_out, n, img, sz);
-    else if (threads == 512 && nt == 1) launch_infer<512, 1>(blocks, lds, s, d_in, d_out, n, img, sz);
-    else if (threads == 1024 && nt == 2) launch_infer<1024, 2>(blocks, lds, s, d_in, d_out, n, img, sz);
-    else if (threads == 512 && nt == 3) launch_infer<512, 3>(blocks, lds, s, d_in, d_out, n, img, sz);
-    else if (threads == 256 && nt == 3) launch_infer<256, 3>(blocks, lds, s, d_in, d_out, n, img, sz);
-    else if (threads == 256 && nt == 4) launch_infer<256, 4>(blocks, lds, s, d_in, d_out, n, img, sz);
-    else
-#endif
     // Renderer-mode launches (skip_zero_queries: the launch runs BESIDE gen_rays) of up to a 1080p frame's worth of queries use 4-wave
     // workgroups -- one 116-register wave per SIMD instead of two: a workgroup finds room once ONE of a SIMD's five camera waves has
     // retired (the same reason the 128-wide kernel does it, above).  Same box, default preset: 7 890-7 940 -> 7 990-8 020 Msamples/s;
     // 2-wave workgroups lose (7 500: twice the weight-image traffic), and the 8.3 M queries of a whole 4K frame on one GPU prefer the
-    // 8-wave form (7 970 against 7 820).  NRC_INFER_RENDER_THREADS=512 restores it everywhere.
-#ifndef NRC_INFER_RENDER_THREADS
-#define NRC_INFER_RENDER_THREADS 256
-#endif
-    if (NRC_INFER_RENDER_THREADS != 512 && skip_zero_queries && composite == nullptr && n <= (3u << 20)) {
-        constexpr int T = NRC_INFER_RENDER_THREADS;
-        uint32_t b2 = ceil_div(n_tiles, (uint32_t)(T / 64) * 2u);
-        const uint32_t cap = (uint32_t)num_cus() * 2u;
-        launch_infer<T, 2>(b2 > cap ? cap : b2, lds, s, d_in, d_out, n, img, sz, nullptr, live_list, live_count);
-        NRC_HIP(hipGetLastError());
-        return;
+    // 8-wave form (7 970 against 7 820).
+    if (skip_zero_queries && n <= (3u << 20)) {
+        constexpr int T = 256;
+        const uint32_t blocks = ceil_div(n_tiles, (uint32_t)(T / 64) * 2u);
+        launch_infer<T, 2>(blocks > cap ? cap : blocks, lds, s, d_in, d_out, n, img, sz, live_list, live_count);
+    } else {
+        const uint32_t blocks = ceil_div(n_tiles, (512u / 64u) * 2u);
+        launch_infer<512, 2>(blocks > cap ? cap : blocks, lds, s, d_in, d_out, n, img, sz, skip_zero_queries ? live_list : nullptr, live_count);
     }
-    launch_infer<512, 2>(blocks, lds, s, d_in, d_out, n, img, sz, composite, skip_zero_queries && composite == nullptr ? live_list : nullptr, live_count);
     NRC_HIP(hipGetLastError());
 }
-
-#ifdef NRC_DIAG
-// diagnostics of the fused inference kernel (never on the product path): ABL 1/2/3 drop the encoding / ReLU-convert work,
-// ABL 4 stamps s_memtime / s_memrealtime per workgroup and prints the in-kernel clock and inter-kernel gaps
-void Mlp::infer_diagnostic(int abl, uint32_t blocks, size_t lds, hipStream_t s, const float* d_in, float* d_out, uint32_t n,
-                           const void* image)
-{
-    const uint4* img = (const uint4*)image;
-    if (abl == 4) {
-        static unsigned long long* d_st = nullptr;
-        constexpr int SLOTS = 16;
-        if (!d_st) dev_alloc(&d_st, (size_t)SLOTS * 4 * 2048 * sizeof(unsigned long long), "d_st");
-        static int count = 0;
-        const int slot = count % SLOTS;
-        hipLaunchKernelGGL((k_infer<6, 512, 2, 4>), dim3(blocks), dim3(512), lds, s, d_in, d_out, n, img, d_st + (size_t)slot * 4 * 2048);
-        if (++count % 64 == 0) {
-            std::vector<unsigned long long> h((size_t)SLOTS * 4 * 2048);
-            NRC_HIP(hipStreamSynchronize(s));
-            NRC_HIP(hipMemcpy(h.data(), d_st, h.size() * 8, hipMemcpyDeviceToHost));
-            std::vector<std::pair<unsigned long long, unsigned long long>> span;
-            std::vector<double> clk;
-            for (int k = 0; k < SLOTS; k++) {
-                unsigned long long first = ~0ull, last = 0;
-                for (uint32_t b = 0; b < blocks; b++) {
-                    const unsigned long long* e = &h[((size_t)k * 2048 + b) * 4];
-                    first = std::min(first, e[2]);
-                    last = std::max(last, e[2] + e[1]);
-                    clk.push_back((double)e[0] / (double)e[1] * 100.0);
-                }
-                span.push_back({first, last});
-            }
-            std::sort(span.begin(), span.end());
-            std::sort(clk.begin(), clk.end());
-            fprintf(stderr, "[nrc diag] clock MHz med %.0f | per launch (wave-0 span us, gap to next us):", clk[clk.size() / 2]);
-            for (int k = 0; k + 1 < SLOTS; k++)
-                fprintf(stderr, " (%.1f, %.1f)", (double)(span[k].second - span[k].first) / 100.0,
-                        (double)(span[k + 1].first - span[k].second) / 100.0);
-            fprintf(stderr, "\n");
-            // one launch in detail: when workgroups start, how long the LDS staging takes, when they end (us from the first start)
-            {
-                std::vector<double> st, sg, en;
-                const unsigned long long* base = &h[0];
-                unsigned long long first = ~0ull;
-                for (uint32_t b = 0; b < blocks; b++) first = std::min(first, base[4 * b + 2]);
-                for (uint32_t b = 0; b < blocks; b++) {
-                    st.push_back((double)(base[4 * b + 2] - first) / 100.0);
-                    sg.push_back((double)base[4 * b + 3] / 100.0);
-                    en.push_back((double)(base[4 * b + 2] + base[4 * b + 1] - first) / 100.0);
-                }
-                std::sort(st.begin(), st.end()); std::sort(sg.begin(), sg.end()); std::sort(en.begin(), en.end());
-                auto q = [](const std::vector<double>& v, double f) { return v[(size_t)(f * (double)(v.size() - 1))]; };
-                fprintf(stderr, "[nrc diag] workgroup start us: med %.1f p90 %.1f max %.1f | staging us: min %.1f med %.1f max %.1f | end us: min %.1f p10 %.1f med %.1f p90 %.1f max %.1f\n",
-                        q(st, .5), q(st, .9), q(st, 1), q(sg, 0), q(sg, .5), q(sg, 1), q(en, 0), q(en, .1), q(en, .5), q(en, .9), q(en, 1));
-            }
-        }
-    } else if (abl == 1) hipLaunchKernelGGL((k_infer<6, 512, 1, 1>), dim3(blocks), dim3(512), lds, s, d_in, d_out, n, img);
-    else if (abl == 2) hipLaunchKernelGGL((k_infer<6, 512, 1, 2>), dim3(blocks), dim3(512), lds, s, d_in, d_out, n, img);
-    else hipLaunchKernelGGL((k_infer<6, 512, 1, 3>), dim3(blocks), dim3(512), lds, s, d_in, d_out, n, img);
-    NRC_HIP(hipGetLastError());
-}
-#endif
 
 // the row-block tasks of k_wgrad2: one per (layer, 32-row block of its delta, group of up to four 32-column blocks of its input)
 void Mlp::build_wgrad_tasks()

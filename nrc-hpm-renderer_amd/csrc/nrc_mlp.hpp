@@ -14,17 +14,6 @@ struct MlpLayer {
     uint32_t off;   // offset into the canonical fp32 parameter vector ([out][in] row-major)
 };
 
-// nrc/render.comp as the epilogue of the renderer's inference launch: the queries are in the renderer's tile-major order (query
-// q_base + i = pixel (x, y) of 8x8 tile (tx, ty), see query_index in nrc_integrator.hip), so the 32 queries of an inference tile are
-// four rows of eight pixels.  primary / info / framebuffer are [h][w] images.
-struct CompositeArgs {
-    const float* primary;      // float4: rgb, throughput
-    const float* info;         // didScatter
-    float* framebuffer;        // float4, blended in place
-    uint32_t w, h, show_nrc, q_base;
-    float blend_factor;
-};
-
 // The non-finite guard (include/nrc_hpm.h, nrc_cache_set_nonfinite_policy).  A pass that reads the final gradient stores `stamp` into
 // words[0] when a word of it, or the loss, is not finite; the optimizer kernels of the same step compare words[0] with `stamp` and turn
 // their update into the identity on a match.  Every scan gets a stamp of its own, so the word is never cleared: a verdict that is not
@@ -69,12 +58,9 @@ public:
     // the first on another stream (the renderer's self-training tails on the training stream beside its render inference)
     static constexpr int kInferSlot = 0, kSideSlot = 4;
     void infer(const float* d_in, float* d_out, uint32_t n, bool use_ema, hipStream_t s, bool skip_zero_queries = false,
-               const CompositeArgs* composite = nullptr, const uint32_t* live_list = nullptr, const uint32_t* live_count = nullptr,
-               int feat_slot = kInferSlot);
+               const uint32_t* live_list = nullptr, const uint32_t* live_count = nullptr, int feat_slot = kInferSlot);
     // sizes kSideSlot's feature buffer for n EMA queries now (a buffer that grows later synchronises the device)
     void reserve_side_slot(uint32_t n) { if (!encodes_in_kernel()) ensure_features(n, kSideSlot); }
-    // the fused 6x64 inference kernel can composite in its epilogue (nrc/render.comp); the generic kernels cannot
-    bool can_composite() const { return fused_; }
     // EMA inference encodes the raw queries inside the MLP kernel (no feature buffer sized by the launch)
     bool encodes_in_kernel() const { return fused_ || enc80_generic_; }
     // forward (training weights) + loss + backward -> gradient vector (x loss_scale) and loss cell
@@ -147,10 +133,6 @@ private:
     void ensure_features(uint32_t n, int slot);
     void launch_features(const float* d_in, uint32_t n, bool use_ema, int slot, hipStream_t s, bool skip_zero, const uint32_t* live_list = nullptr,
                          const uint32_t* live_count = nullptr);
-#ifdef NRC_DIAG
-    void infer_diagnostic(int abl, uint32_t blocks, size_t lds, hipStream_t s, const float* d_in, float* d_out, uint32_t n,
-                          const void* image);
-#endif
 
     nrc_config cfg_;
     uint32_t width_, depth_, enc_dims_, n_params_;

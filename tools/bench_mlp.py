@@ -36,5 +36,5 @@ for _ in range(5):
     torch.cuda.synchronize()
     times.append(e0.elapsed_time(e1) / reps)
 ms = float(np.median(times))
-print("%dx%d threads=%s n=%d  %.4f ms  %.1f TFLOP/s (%.1f%% of 2500)  %.2f Gsamples/s" %
-      (depth, width, os.environ.get("NRC_INFER_THREADS", "512"), n, ms, flop * n / ms / 1e9, flop * n / ms / 1e9 / 25.0, n / ms / 1e6))
+print("%dx%d n=%d  %.4f ms  %.1f TFLOP/s (%.1f%% of 2500)  %.2f Gsamples/s" %
+      (depth, width, n, ms, flop * n / ms / 1e9, flop * n / ms / 1e9 / 25.0, n / ms / 1e6))
