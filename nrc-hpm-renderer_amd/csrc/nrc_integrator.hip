@@ -1368,10 +1368,13 @@ __device__ __forceinline__ void tile_mask_box(const float* __restrict__ boxes, u
     float gx0 = floorf((xmin + 1.0f) * 0.5f * gw) - 1.0f, gx1 = ceilf((xmax + 1.0f) * 0.5f * gw) + 1.0f;
     float gy0 = floorf((ymin + 1.0f) * 0.5f * gh) - 1.0f, gy1 = ceilf((ymax + 1.0f) * 0.5f * gh) + 1.0f;
     // local columns: strip s = gx >> b of the global frame is the local strip (s - x_offset) / x_stride (global_x); every local
-    // column of the local strips the rectangle can touch is taken (conservative)
+    // column of the local strips the rectangle can touch is taken (conservative).  The rectangle touches the global strips s0 .. s1, so the
+    // local strips l with s0 <= x_offset + l * x_stride <= s1: from ceil((s0 - x_offset) / x_stride) to floor((s1 - x_offset) / x_stride)
+    // (near the frame these are small integers, whose fp32 quotient is an integer only when the true one is: ceil and floor are exact;
+    // far outside it the clamps below decide)
     const float blk = (float)(1u << fr.x_block_log2);
-    float lx0 = floorf((floorf(gx0 / blk) - (float)fr.x_offset) / (float)fr.x_stride) * blk;
-    float lx1 = (ceilf((floorf(gx1 / blk) - (float)fr.x_offset) / (float)fr.x_stride) + 1.0f) * blk - 1.0f;
+    float lx0 = ceilf((floorf(gx0 / blk) - (float)fr.x_offset) / (float)fr.x_stride) * blk;
+    float lx1 = (floorf((floorf(gx1 / blk) - (float)fr.x_offset) / (float)fr.x_stride) + 1.0f) * blk - 1.0f;
     lx0 = fmaxf(lx0, 0.0f); gy0 = fmaxf(gy0, 0.0f);
     lx1 = fminf(lx1, (float)(fr.w - 1u)); gy1 = fminf(gy1, (float)(fr.h - 1u));
     if (!(lx0 <= lx1) || !(gy0 <= gy1)) {                    // off screen

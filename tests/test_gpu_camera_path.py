@@ -25,10 +25,12 @@ def same_bits(a, b):
 
 
 def views_of(sc, aspect):
-    """the one view set of this file, chosen to hit every branch of the mask: the default view and two orbit views (rectangles that cover
-    part of the screen), an eye inside the volume (a box corner behind the eye plane: the off word), and a far eye that looks past the
-    cloud (every box in front of the eye plane, every rectangle off screen: all clear).  The all-clear view follows mixed ones and the
-    off view is followed by others, so a word the build failed to rewrite would show."""
+    """the one view set of this file, chosen to hit every outcome of a box's rectangle: the default view and two orbit views (rectangles
+    that cover part of the screen), an eye inside the volume (a box corner behind the eye plane: the off word), and a far eye that looks
+    past the cloud (every box in front of the eye plane, every rectangle off screen: all clear).  The all-clear view follows mixed ones and
+    the off view is followed by others, so a word the build failed to rewrite would show.  Not every branch of the build: cloud16 has 162
+    boxes and these frames are at most 16 tiles across, so the tile-parallel build stages one chunk of rectangles and no mask word lies
+    inside one tile row; test_gpu_empty_skip_geometry.py has more than two chunks and a frame 41 tiles across."""
     orbit = sc.orbit_cameras(5, radius=70.0, height=25.0, aspect=aspect)
     return [sc.make_camera(aspect=aspect), orbit[1], sc.make_camera(pos=(10.0, 0.0, 0.0), aspect=aspect),
             sc.make_camera(pos=(200.0, 0.0, 0.0), view_dir=(-1.0, 0.0, 2.5), aspect=aspect), orbit[3]]
