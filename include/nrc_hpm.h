@@ -412,6 +412,35 @@ uint32_t nrc_renderer_volume_key_count(nrc_renderer_t* r);
 int nrc_renderer_set_volume_time(nrc_renderer_t* r, float t);
 int nrc_renderer_render_path_timed(nrc_renderer_t* r, uint32_t n_cameras, const nrc_camera* cameras, const float* times,
                                    uint32_t frames_per_camera, const float* frame_randoms, int train, float* d_frames);
+/* Sparse volume keyframes: the same key sequence held as lists of 8^3 bricks instead of dense volumes (a cached simulation whose frames
+ * are mostly empty).  A renderer holds ONE key sequence, dense or bricks: setting either kind replaces whatever was there, and
+ * nrc_renderer_volume_key_count, nrc_renderer_set_volume_time and nrc_renderer_render_path_timed work on either kind with the contracts
+ * stated above.
+ *   Keys.  key_counts: n_keys words, ALWAYS host memory -- key k is a list of key_counts[k] bricks.  origins and bricks are the keys' lists
+ *     concatenated in key order, in the layouts of nrc_renderer_set_volume_bricks (origins int32[3 * total], bricks total * 512 elements of
+ *     `format`, total = the sum of key_counts); on_device applies to these two pointers, as there.  The volume keeps the dims of creation.
+ *     Per key the rules of nrc_renderer_set_volume_bricks hold: the highest index wins a cell named twice, a brick of zeros is legal, brick
+ *     voxels past the volume's edge are ignored, a key with count 0 is the empty medium (total = 0: both pointers may be NULL).  A host list
+ *     is checked: an invalid origin returns NRC_ERR_INVALID and the message names the key and the brick inside that key's list.  A device
+ *     list's invalid origins are ignored on the device.  n_keys = 0 drops the sequence (the other arguments are then ignored).
+ *   What is kept.  One R8 array of all bricks (a NRC_VOLUME_F32 source is quantised once, at upload, by the rule of
+ *     nrc_renderer_set_volume) and, per key, one 32-bit word per 8^3 cell of the volume that names the cell's brick.  The origins are not
+ *     kept.  nrc_renderer_volume_key_bytes returns the device bytes the current sequence holds:
+ *         dense keys:  n_keys * nx*ny*nz
+ *         brick keys:  512 * (sum of key_counts) + 4 * n_keys * cells,  cells = ceil(nx/8) * ceil(ny/8) * ceil(nz/8)
+ *         no keys:     0
+ *   Definition.  With brick keys, nrc_renderer_set_volume_time(t) leaves the three device buffers (nrc_renderer_volume_buffer) byte for
+ *     byte what nrc_renderer_set_volume_keys(the densified keys) followed by nrc_renderer_set_volume_time(t) leaves, where the densified
+ *     key is what nrc_renderer_set_volume_bricks makes of that key's list; the frames and the training that follow are therefore
+ *     bit-identical too.  A cell with a brick in only one key blends against 0: for 0 < W < 256 that is NOT a copy of the brick (a voxel
+ *     of 1 is 1 up to W = 128 and 0 from W = 129), and the occupancy follows q, not the keys.
+ *   As nrc_renderer_set_volume_keys, the call may wait for every stream of the renderer: this is NOT a per-frame call.  The renderer's
+ *     current medium is not touched.  A call that fails -- a NULL pointer, an unknown format, an invalid host origin, sizes that do not fit,
+ *     an allocation failure -- leaves the renderer and the previous sequence, of either kind, as they were: the new sequence is complete
+ *     before the old one goes.  In a sharded run every rank makes the same calls with the same lists. */
+int nrc_renderer_set_volume_key_bricks(nrc_renderer_t* r, const uint32_t* key_counts, const int32_t* origins, const void* bricks, uint32_t n_keys,
+                                       int format, int on_device);
+size_t nrc_renderer_volume_key_bytes(nrc_renderer_t* r);
 /* diagnostics: the current volume's device buffers after synchronising the renderer -- which 0: density [nz][ny][nx] u8, 1: occupancy
  * bits (uint32 words), 2: empty-space boxes float[6 * n] {lo.xyz, hi.xyz}; *bytes = their size (NULL, bytes 0: no boxes) */
 const void* nrc_renderer_volume_buffer(nrc_renderer_t* r, int which, size_t* bytes);
@@ -580,6 +609,10 @@ int nrc_mc_renderer_set_volume_bricks(nrc_mc_renderer_t* r, const int32_t* origi
 int nrc_mc_renderer_set_volume_keys(nrc_mc_renderer_t* r, const void* volumes, uint32_t n_keys, uint32_t nx, uint32_t ny, uint32_t nz, int format,
                                     int on_device);
 uint32_t nrc_mc_renderer_volume_key_count(nrc_mc_renderer_t* r);
+/* see nrc_renderer_set_volume_key_bricks */
+int nrc_mc_renderer_set_volume_key_bricks(nrc_mc_renderer_t* r, const uint32_t* key_counts, const int32_t* origins, const void* bricks, uint32_t n_keys,
+                                          int format, int on_device);
+size_t nrc_mc_renderer_volume_key_bytes(nrc_mc_renderer_t* r);
 int nrc_mc_renderer_set_volume_time(nrc_mc_renderer_t* r, float t);
 int nrc_mc_renderer_render_path_timed(nrc_mc_renderer_t* r, uint32_t n_cameras, const nrc_camera* cameras, const float* times,
                                       uint32_t frames_per_camera, const float* frame_randoms, float* d_frames);

@@ -490,6 +490,15 @@ public:
     {
         nrc_check(nrc_renderer_set_volume_keys(h_, volumes, nKeys, nx, ny, nz, format, onDevice ? 1 : 0));
     }
+    // the same sequence from 8^3 brick lists (nrc_renderer_set_volume_key_bricks): keyCounts nKeys host words, origins / bricks the keys' lists
+    // concatenated in key order, in SetVolumeBricks' layouts; it replaces a dense sequence and the other way round.  VolumeKeyBytes(): the
+    // device bytes the current sequence holds
+    void SetVolumeKeyBricks(const uint32_t* keyCounts, const int32_t* origins, const void* bricks, uint32_t nKeys, int format = NRC_VOLUME_U8,
+                            bool onDevice = true)
+    {
+        nrc_check(nrc_renderer_set_volume_key_bricks(h_, keyCounts, origins, bricks, nKeys, format, onDevice ? 1 : 0));
+    }
+    size_t VolumeKeyBytes() const { return nrc_renderer_volume_key_bytes(h_); }
     uint32_t VolumeKeyCount() const { return nrc_renderer_volume_key_count(h_); }
     void SetVolumeTime(float t) { nrc_check(nrc_renderer_set_volume_time(h_, t)); }
     nrc_renderer_t* Handle() const { return h_; }
@@ -563,6 +572,13 @@ public:
     {
         nrc_check(nrc_mc_renderer_set_volume_keys(h_, volumes, nKeys, nx, ny, nz, format, onDevice ? 1 : 0));
     }
+    // see NrcHpmRenderer::SetVolumeKeyBricks / VolumeKeyBytes
+    void SetVolumeKeyBricks(const uint32_t* keyCounts, const int32_t* origins, const void* bricks, uint32_t nKeys, int format = NRC_VOLUME_U8,
+                            bool onDevice = true)
+    {
+        nrc_check(nrc_mc_renderer_set_volume_key_bricks(h_, keyCounts, origins, bricks, nKeys, format, onDevice ? 1 : 0));
+    }
+    size_t VolumeKeyBytes() const { return nrc_mc_renderer_volume_key_bytes(h_); }
     uint32_t VolumeKeyCount() const { return nrc_mc_renderer_volume_key_count(h_); }
     void SetVolumeTime(float t) { nrc_check(nrc_mc_renderer_set_volume_time(h_, t)); }
     nrc_mc_renderer_t* Handle() const { return h_; }

@@ -88,6 +88,7 @@ ABI_SYMBOLS = [
     "nrc_renderer_set_volume", "nrc_mc_renderer_set_volume", "nrc_renderer_volume_buffer", "nrc_mc_renderer_volume_buffer",
     "nrc_renderer_set_volume_bricks", "nrc_mc_renderer_set_volume_bricks",
     "nrc_renderer_set_volume_keys", "nrc_mc_renderer_set_volume_keys", "nrc_renderer_volume_key_count", "nrc_mc_renderer_volume_key_count",
+    "nrc_renderer_set_volume_key_bricks", "nrc_mc_renderer_set_volume_key_bricks", "nrc_renderer_volume_key_bytes", "nrc_mc_renderer_volume_key_bytes",
     "nrc_renderer_set_volume_time", "nrc_mc_renderer_set_volume_time", "nrc_renderer_render_path_timed", "nrc_mc_renderer_render_path_timed",
     "nrc_renderer_render_path", "nrc_mc_renderer_render_path", "nrc_renderer_tile_mask", "nrc_mc_renderer_tile_mask",
     "nrc_renderer_set_show_nrc", "nrc_renderer_set_frame_random", "nrc_renderer_framebuffer", "nrc_renderer_framebuffer_on",
@@ -178,6 +179,12 @@ def load_library():
             getattr(L, name).argtypes = [C.c_void_p, C.c_float]
         L.nrc_renderer_render_path_timed.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]
         L.nrc_mc_renderer_render_path_timed.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    if hasattr(L, "nrc_renderer_set_volume_key_bricks"):      # (an older build loaded through NRC_HPM_LIB has no brick keys)
+        for name in ("nrc_renderer_set_volume_key_bricks", "nrc_mc_renderer_set_volume_key_bricks"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int]
+        for name in ("nrc_renderer_volume_key_bytes", "nrc_mc_renderer_volume_key_bytes"):
+            getattr(L, name).restype = C.c_size_t
+            getattr(L, name).argtypes = [C.c_void_p]
     L.nrc_mc_renderer_frame_time_ms.restype = C.c_float
     for name in ("nrc_cache_get_loss", "nrc_cache_get_loss_blocking", "nrc_renderer_is_blending", "nrc_mc_renderer_is_blending",
                  "nrc_cache_get_infer_batch_count", "nrc_cache_get_train_batch_count",
@@ -390,6 +397,41 @@ def _set_volume_keys(fn, h, keys):
         raise RuntimeError("SkyRenderer ERROR: SetVolumeKeys takes a contiguous CUDA tensor or a numpy array, uint8 or float32 [n_keys][nz][ny][nx]")
     n, nz, ny, nx = keys.shape
     _check(fn(h, _dev_ptr(keys) if n else None, n, nx, ny, nz, VOLUME_F32 if keys.dtype == torch.float32 else VOLUME_U8, 1))
+
+
+def _set_volume_key_bricks(fn, h, counts, origins, bricks):
+    """SetVolumeKeyBricks of both renderers: counts, the bricks of every key (a sequence of ints or an integer numpy array, always host
+    memory), and the keys' lists concatenated in key order -- origins int32 [sum(counts)][3] and bricks uint8 or float32 [sum(counts)][8][8][8],
+    validated like SetVolumeBricks' (two C-contiguous numpy arrays or two contiguous CUDA tensors).  counts None or empty drops the sequence."""
+    if counts is None or len(counts) == 0:
+        _check(fn(h, None, None, None, 0, VOLUME_U8, 0))
+        return
+    counts64 = np.asarray(counts)
+    if counts64.ndim != 1 or counts64.dtype.kind not in "iu" or (counts64 < 0).any() or (counts64 > 0xffffffff).any():
+        raise RuntimeError("SkyRenderer ERROR: SetVolumeKeyBricks takes counts as a sequence of non-negative integers, one per key (got %r)" % (counts,))
+    key_counts = np.ascontiguousarray(counts64, np.uint32)
+    total = int(counts64.astype(np.uint64).sum())
+    if isinstance(origins, np.ndarray) and isinstance(bricks, np.ndarray):
+        ok = origins.dtype == np.int32 and origins.ndim == 2 and origins.shape[1] == 3 and origins.flags.c_contiguous \
+            and bricks.dtype in (np.uint8, np.float32) and bricks.shape == (origins.shape[0], 8, 8, 8) and bricks.flags.c_contiguous
+        if not ok:
+            raise RuntimeError("SkyRenderer ERROR: SetVolumeKeyBricks takes C-contiguous numpy arrays, origins int32 [n][3] and bricks uint8 or "
+                               "float32 [n][8][8][8] (got %s %s and %s %s)" % (origins.dtype, origins.shape, bricks.dtype, bricks.shape))
+        on_device, fmt = 0, VOLUME_F32 if bricks.dtype == np.float32 else VOLUME_U8
+        p_origins, p_bricks = C.c_void_p(origins.ctypes.data), C.c_void_p(bricks.ctypes.data)
+    else:
+        import torch
+        ok = isinstance(origins, torch.Tensor) and isinstance(bricks, torch.Tensor) and origins.is_cuda and bricks.is_cuda \
+            and origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 3 and origins.is_contiguous() \
+            and bricks.dtype in (torch.uint8, torch.float32) and tuple(bricks.shape) == (origins.shape[0], 8, 8, 8) and bricks.is_contiguous()
+        if not ok:
+            raise RuntimeError("SkyRenderer ERROR: SetVolumeKeyBricks takes contiguous CUDA tensors, origins int32 [n][3] and bricks uint8 or "
+                               "float32 [n][8][8][8], or two numpy arrays of those types")
+        on_device, fmt = 1, VOLUME_F32 if bricks.dtype == torch.float32 else VOLUME_U8
+        p_origins, p_bricks = _dev_ptr(origins), _dev_ptr(bricks)
+    if origins.shape[0] != total:
+        raise RuntimeError("SkyRenderer ERROR: SetVolumeKeyBricks: counts sum to %d bricks, origins and bricks hold %d" % (total, origins.shape[0]))
+    _check(fn(h, C.c_void_p(key_counts.ctypes.data), p_origins if total else None, p_bricks if total else None, key_counts.size, fmt, on_device))
 
 
 def _render_path(call, width, height, cameras, framesPerCamera, frameRandoms, out, times=None):
@@ -849,6 +891,17 @@ class NrcHpmRenderer:
         sequence.  Not a per-frame call: it may wait for the frames in flight."""
         _set_volume_keys(self.L.nrc_renderer_set_volume_keys, self.h, keys)
 
+    def SetVolumeKeyBricks(self, counts, origins, bricks):
+        """the same sequence held as 8^3 brick lists (include/nrc_hpm.h, nrc_renderer_set_volume_key_bricks; scene.volumes_to_key_bricks makes
+        the three of dense keys): counts = bricks per key, origins int32 [sum][3] and bricks uint8 or float32 [sum][8][8][8] the keys' lists
+        in key order, numpy arrays or CUDA tensors.  It replaces a dense sequence and the other way round; counts None drops the sequence.
+        Not a per-frame call."""
+        _set_volume_key_bricks(self.L.nrc_renderer_set_volume_key_bricks, self.h, counts, origins, bricks)
+
+    def VolumeKeyBytes(self):
+        """the device bytes the current key sequence holds (dense: n_keys * nx*ny*nz; bricks: 512 * sum(counts) + 4 * n_keys * cells)"""
+        return int(self.L.nrc_renderer_volume_key_bytes(self.h))
+
     def VolumeKeyCount(self):
         return int(self.L.nrc_renderer_volume_key_count(self.h))
 
@@ -1097,6 +1150,14 @@ class McHpmRenderer:
     def SetVolumeKeys(self, keys):
         """see NrcHpmRenderer.SetVolumeKeys"""
         _set_volume_keys(self.L.nrc_mc_renderer_set_volume_keys, self.h, keys)
+
+    def SetVolumeKeyBricks(self, counts, origins, bricks):
+        """see NrcHpmRenderer.SetVolumeKeyBricks"""
+        _set_volume_key_bricks(self.L.nrc_mc_renderer_set_volume_key_bricks, self.h, counts, origins, bricks)
+
+    def VolumeKeyBytes(self):
+        """see NrcHpmRenderer.VolumeKeyBytes"""
+        return int(self.L.nrc_mc_renderer_volume_key_bytes(self.h))
 
     def VolumeKeyCount(self):
         return int(self.L.nrc_mc_renderer_volume_key_count(self.h))

@@ -26,6 +26,9 @@ through them with NrcHpmRenderer.SetVolumeBricks.  The run prints the device byt
 An animated fly-through (new): `--orbit N --vdb a b c --animate` uploads the files as volume keys (NrcHpmRenderer.SetVolumeKeys; key i
 at time i) and renders view v at time v * (n_keys - 1) / max(N - 1, 1) * `--time-scale` -- the medium in between two files is their
 linear in-between -- with one RenderPath(..., times=...) call.  A --time-scale below 1 is slow motion; times past the last key stay there.
+With `--sparse-keys` the keys are held as brick lists (NrcHpmRenderer.SetVolumeKeyBricks): every file's leaves are read over the aligned
+union bbox as for `--bricks`, no dense array is made per file (only the first list is densified, for creation), and the run prints the
+dense and brick byte counts held.  `--animate --bricks` stays refused: `--bricks` means stepping with SetVolumeBricks.
 """
 import argparse
 import math
@@ -67,11 +70,14 @@ def check_orbit_args(args):
 def check_animate_args(args):
     """what --animate needs (raises SystemExit); returns whether the run is an animated fly-through"""
     if not getattr(args, "animate", False):
+        if getattr(args, "sparse_keys", False):
+            raise SystemExit("SkyRenderer ERROR: --sparse-keys goes with --animate (the keys of an animated fly-through held as bricks)")
         return False
     if args.orbit is None or not (args.vdb and len(args.vdb) > 1):
         raise SystemExit("SkyRenderer ERROR: --animate goes with --orbit and a --vdb sequence (several files: the keys)")
     if getattr(args, "bricks", False):
-        raise SystemExit("SkyRenderer ERROR: --animate and --bricks exclude each other (volume keys are dense)")
+        raise SystemExit("SkyRenderer ERROR: --animate and --bricks exclude each other (--bricks steps a sequence with SetVolumeBricks; --sparse-keys holds "
+                         "the keys of --animate as bricks)")
     scale = getattr(args, "time_scale", 1.0)
     if not (math.isfinite(scale) and scale >= 0.0):
         raise SystemExit("SkyRenderer ERROR: --time-scale must be a finite number, at least 0")
@@ -112,6 +118,8 @@ def main(argv=None):
     ap.add_argument("--animate", action="store_true",
                     help="with --orbit and a --vdb sequence: the files are volume keys and the medium moves through them along the turntable "
                          "(include/nrc_hpm.h, nrc_renderer_render_path_timed)")
+    ap.add_argument("--sparse-keys", action="store_true",
+                    help="--animate: hold the keys on the device as lists of 8^3 bricks (include/nrc_hpm.h, nrc_renderer_set_volume_key_bricks)")
     ap.add_argument("--time-scale", type=float, default=1.0, help="--animate: the medium's speed (below 1: slow motion; times stop at the last key)")
     ap.add_argument("--orbit-radius", type=float, default=64.0)
     ap.add_argument("--orbit-height", type=float, default=0.0)
@@ -156,7 +164,8 @@ def main(argv=None):
     if args.self_train:
         cfg.c.self_train = 1
     sequence, brick_lists = [], []
-    if args.vdb and args.bricks:
+    sparse_keys = animate and args.sparse_keys
+    if args.vdb and (args.bricks or sparse_keys):
         # bricks: only the creation volume (the densified first file) exists as a dense array
         bbox = io_vdb.aligned_bbox(io_vdb.union_bbox(args.vdb))
         dims = tuple(int(hi - lo + 1) for lo, hi in zip(bbox[0], bbox[1]))[::-1]      # (nz, ny, nx)
@@ -199,7 +208,7 @@ def main(argv=None):
     # a sequence: every volume uploaded once, swapped in on the device (every rank swaps the whole volume before the same frame)
     seq_dev = [torch.from_numpy(np.ascontiguousarray(v)).cuda() for v in sequence] if len(sequence) > 1 and not animate else []
     # --bricks: every file's list uploaded once (float32 bricks, quantised by the rebuild as the dense path quantises on the host)
-    seq_bricks = [(torch.from_numpy(o).cuda(), torch.from_numpy(b).cuda()) for o, b in brick_lists]
+    seq_bricks = [(torch.from_numpy(o).cuda(), torch.from_numpy(b).cuda()) for o, b in brick_lists] if not sparse_keys else []
     if seq_bricks and rank == 0:
         for p, (o, b) in zip(args.vdb, seq_bricks):
             held = o.numel() * 4 + b.numel() * 4
@@ -239,8 +248,15 @@ def main(argv=None):
         per_view = args.export is not None and "%" in args.export
         times = None
         if animate:      # the files are the keys (uploaded once, from the host), the views' times run through them
-            nrc_renderer.SetVolumeKeys(np.ascontiguousarray(np.stack(sequence)))
-            times = animate_times(n_views, len(sequence), args.time_scale)
+            if sparse_keys:      # (from the host, float32 bricks: quantised once at upload, as the dense path quantises on the host)
+                nrc_renderer.SetVolumeKeyBricks([len(o) for o, _ in brick_lists], np.ascontiguousarray(np.concatenate([o for o, _ in brick_lists])),
+                                                np.ascontiguousarray(np.concatenate([b for _, b in brick_lists])))
+                if rank == 0:
+                    print("%d keys, %d bricks: %d bytes on the device as brick keys; dense keys %d bytes" %
+                          (len(brick_lists), sum(len(o) for o, _ in brick_lists), nrc_renderer.VolumeKeyBytes(), len(brick_lists) * density.size))
+            else:
+                nrc_renderer.SetVolumeKeys(np.ascontiguousarray(np.stack(sequence)))
+            times = animate_times(n_views, nrc_renderer.VolumeKeyCount(), args.time_scale)
         images = nrc_renderer.RenderPath(views, args.frames, train=True, out=None if per_view else False, times=times)
         loss = nrc.GetLoss(wait=True)
         failed = (math.isnan(loss) or math.isinf(loss)) and not args.skip_nonfinite      # (the all-reduced loss: the same on every rank)

@@ -2076,6 +2076,45 @@ struct VolBricks {
     }
 };
 
+// two keys held as bricks, blended (nrc_renderer_set_volume_key_bricks + set_volume_time, 0 < W < 256): `bricks` is the library's own R8
+// array of every key's bricks (4-byte aligned at every half row), cell_a / cell_b the two keys' resident cell_brick indices (1 + the brick
+// in that array, 0 = none).  A key without a brick in the lane's cell counts as 0 -- lerp_voxel(a, 0, W), not a copy of a -- and where
+// neither key has one nothing is loaded.  Every voxel of the volume is written.
+struct VolLerpBricks {
+    const uint8_t* bricks;
+    const uint32_t *cell_a, *cell_b;
+    uint32_t W;
+    struct Lane { uint32_t a, b; size_t base_a, base_b; };
+    // both keys' brick ids of the workgroup's 32 cells (a first, b behind it): one LDS array per kernel instantiation, as VolBricks::lbrick()
+    static __device__ __forceinline__ uint32_t* lbrick() { __shared__ uint32_t l[64]; return l; }
+    __device__ __forceinline__ void stage(uint32_t t, size_t cell, bool in) const
+    {
+        lbrick()[t] = in ? cell_a[cell] : 0u;
+        lbrick()[32u + t] = in ? cell_b[cell] : 0u;
+    }
+    __device__ __forceinline__ Lane lane(uint32_t t) const
+    {
+        const uint32_t c = (t & 63u) >> 1, a = lbrick()[c], b = lbrick()[32u + c];
+        return {a, b, a ? (size_t)(a - 1u) * 512u + 4u * (t & 1u) : 0u, b ? (size_t)(b - 1u) * 512u + 4u * (t & 1u) : 0u};
+    }
+    template <bool VEC>
+    __device__ __forceinline__ uint32_t fetch(const Lane& ln, size_t idx, uint32_t r, uint32_t x, uint32_t nx, uint32_t q[4], uint8_t* __restrict__ density) const
+    {
+        uint32_t wa = 0u, wb = 0u;      // one 4-byte load per present key and row (64 * dz + 8 * dy: r = 8 * dz + dy)
+        if (ln.a) wa = *(const uint32_t*)(bricks + ln.base_a + 8u * r);
+        if (ln.b) wb = *(const uint32_t*)(bricks + ln.base_b + 8u * r);
+        if (!VEC) {
+            uint32_t a[4], b[4];
+            vol_unpack4(wa, a);
+            vol_unpack4(wb, b);
+            return vol_scalar4([&](uint32_t k) { return lerp_voxel(a[k], b[k], W); }, x, nx, q, density + idx);
+        }
+        const uint32_t w = (ln.a | ln.b) ? lerp_voxels4(wa, wb, W) : 0u;
+        vol_unpack4(w, q);
+        return w;
+    }
+};
+
 // One workgroup per (32 cells along x) x (one 8x8 row of cells in y, z): 256 lanes, a lane owns four consecutive voxels of x (in one
 // cell) in 16 of the 64 voxel rows.  Writes the density and every cell's 27-bit touch mask (the workgroup owns its cells: no global atomics).
 // VEC: nx % 4 == 0 and what the source asks for (one 4-byte store per lane and row; otherwise the source stores, vol_scalar4).
@@ -2256,9 +2295,10 @@ __global__ __launch_bounds__(1024) void k_vol_rows(const uint8_t* __restrict__ c
 //
 // One lane per brick: cell_brick[cell] = 1 + the highest index of the bricks that name the cell (cleared to 0 = none by the caller).
 // atomicMax on integers: which brick wins does not depend on the order the lanes run in.  An origin that is not a multiple of 8 or
-// lies outside the volume is ignored (a device list cannot be checked by the host without a wait).
+// lies outside the volume is ignored (a device list cannot be checked by the host without a wait).  first: the number of brick 0 of
+// this list (0, or where a key's slice starts in the concatenated array of nrc_renderer_set_volume_key_bricks).
 __global__ __launch_bounds__(256) void k_vol_brick_index(const int32_t* __restrict__ origins, uint32_t n_bricks, uint32_t* __restrict__ cell_brick,
-                                                        uint32_t nx, uint32_t ny, uint32_t nz, uint32_t gx, uint32_t gy)
+                                                        uint32_t nx, uint32_t ny, uint32_t nz, uint32_t gx, uint32_t gy, uint32_t first)
 {
     NRC_RAISE_WAVE_PRIORITY(16);
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -2266,7 +2306,7 @@ __global__ __launch_bounds__(256) void k_vol_brick_index(const int32_t* __restri
     const int32_t x0 = origins[3u * (size_t)i], y0 = origins[3u * (size_t)i + 1u], z0 = origins[3u * (size_t)i + 2u];
     if ((x0 | y0 | z0) < 0 || ((x0 | y0 | z0) & 7) != 0) return;
     if ((uint32_t)x0 >= nx || (uint32_t)y0 >= ny || (uint32_t)z0 >= nz) return;
-    atomicMax(&cell_brick[((size_t)((uint32_t)z0 >> 3) * gy + ((uint32_t)y0 >> 3)) * gx + ((uint32_t)x0 >> 3)], i + 1u);
+    atomicMax(&cell_brick[((size_t)((uint32_t)z0 >> 3) * gy + ((uint32_t)y0 >> 3)) * gx + ((uint32_t)x0 >> 3)], first + i + 1u);
 }
 
 }  // namespace
@@ -2389,15 +2429,35 @@ size_t volume_brick_index_bytes(uint32_t nx, uint32_t ny, uint32_t nz)
     return (size_t)ceil_div(nx, 8) * ceil_div(ny, 8) * ceil_div(nz, 8) * 4;
 }
 
+void launch_volume_brick_index(const int32_t* origins, uint32_t n_bricks, uint32_t first, uint32_t* cell_brick, uint32_t nx, uint32_t ny, uint32_t nz,
+                               hipStream_t s)
+{
+    NRC_HIP(hipMemsetAsync(cell_brick, 0, volume_brick_index_bytes(nx, ny, nz), s));
+    if (n_bricks == 0) return;
+    hipLaunchKernelGGL(k_vol_brick_index, dim3(ceil_div(n_bricks, 256)), dim3(256), 0, s, origins, n_bricks, cell_brick, nx, ny, nz, ceil_div(nx, 8),
+                       ceil_div(ny, 8), first);
+    NRC_HIP(hipGetLastError());
+}
+
+void launch_volume_rebuild_indexed(const uint8_t* bricks, const uint32_t* cell_brick, const VolumeRebuild& v, void* scratch, hipStream_t s)
+{
+    launch_volume_ingest(VolBricks<false>{bricks, cell_brick, 1u}, v.nx % 4 == 0, v, scratch, s);
+}
+
+void launch_volume_rebuild_lerp_bricks(const uint8_t* bricks, const uint32_t* cell_a, const uint32_t* cell_b, uint32_t W, const VolumeRebuild& v,
+                                       void* scratch, hipStream_t s)
+{
+    if (W == 0u || W >= 256u) {      // one key as it is, through its resident index (cell_b may be null at W == 0: the last key has no successor)
+        launch_volume_rebuild_indexed(bricks, W == 0u ? cell_a : cell_b, v, scratch, s);
+        return;
+    }
+    launch_volume_ingest(VolLerpBricks{bricks, cell_a, cell_b, W}, v.nx % 4 == 0, v, scratch, s);
+}
+
 void launch_volume_rebuild_bricks(const int32_t* origins, const void* bricks, uint32_t n_bricks, int format, const VolumeRebuild& v, void* scratch,
                                   uint32_t* brick_index, hipStream_t s)
 {
-    NRC_HIP(hipMemsetAsync(brick_index, 0, volume_brick_index_bytes(v.nx, v.ny, v.nz), s));
-    if (n_bricks) {
-        hipLaunchKernelGGL(k_vol_brick_index, dim3(ceil_div(n_bricks, 256)), dim3(256), 0, s, origins, n_bricks, brick_index, v.nx, v.ny, v.nz,
-                           ceil_div(v.nx, 8), ceil_div(v.ny, 8));
-        NRC_HIP(hipGetLastError());
-    }
+    launch_volume_brick_index(origins, n_bricks, 0u, brick_index, v.nx, v.ny, v.nz, s);
     const bool f32 = format == NRC_VOLUME_F32, vec = v.nx % 4 == 0;
     const uint32_t aligned = (uintptr_t)bricks % (f32 ? 16 : 4) == 0 ? 1u : 0u;
     if (f32) launch_volume_ingest(VolBricks<true>{bricks, brick_index, aligned}, vec, v, scratch, s);

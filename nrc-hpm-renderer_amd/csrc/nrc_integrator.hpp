@@ -143,6 +143,19 @@ void launch_volume_rebuild(const void* src, int format, const VolumeRebuild& v, 
 size_t volume_brick_index_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
 void launch_volume_rebuild_bricks(const int32_t* origins, const void* bricks, uint32_t n_bricks, int format, const VolumeRebuild& v, void* scratch,
                                   uint32_t* brick_index, hipStream_t s);
+// the first half of that call alone: cell_brick (volume_brick_index_bytes) cleared, then cell_brick[cell] = 1 + first + the highest index of the
+// n_bricks bricks at `origins` that name the cell (nrc_renderer_set_volume_key_bricks: a key's slice of the concatenated list, first = where it
+// starts).  A clear and one launch (none when n_bricks == 0).
+void launch_volume_brick_index(const int32_t* origins, uint32_t n_bricks, uint32_t first, uint32_t* cell_brick, uint32_t nx, uint32_t ny, uint32_t nz,
+                               hipStream_t s);
+// the second half from a ready index: R8 bricks aligned to 4 bytes, cell_brick as launch_volume_brick_index leaves it (neither is written).
+// Three launches.
+void launch_volume_rebuild_indexed(const uint8_t* bricks, const uint32_t* cell_brick, const VolumeRebuild& v, void* scratch, hipStream_t s);
+// two keys of one such array blended (nrc_renderer_set_volume_time on brick keys): voxel = lerp_voxel(a, b, W) with 0 where a key has no brick
+// in the cell, 0 <= W <= 256 -- what launch_volume_rebuild_lerp makes of the two densified keys, bit for bit.  W == 0 reads cell_a's key alone
+// through launch_volume_rebuild_indexed (cell_b may be null), W == 256 cell_b's.  Three launches.
+void launch_volume_rebuild_lerp_bricks(const uint8_t* bricks, const uint32_t* cell_a, const uint32_t* cell_b, uint32_t W, const VolumeRebuild& v,
+                                       void* scratch, hipStream_t s);
 // n NRC_VOLUME_F32 voxels -> R8, the quantisation of launch_volume_rebuild (key volumes are kept as R8: nrc_renderer_set_volume_keys)
 void launch_volume_quantize(const float* src, uint8_t* dst, size_t n, hipStream_t s);
 // the same from two R8 key volumes in device memory (nrc_renderer_set_volume_time): every voxel lerp_voxel(a, b, W) of nrc_volume_keys.hpp,

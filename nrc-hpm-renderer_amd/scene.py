@@ -171,6 +171,39 @@ def volume_at(keys, t):
     return np.ascontiguousarray(keys[i]) if W == 0 else lerp_volume(keys[i], keys[i + 1], W)
 
 
+def volumes_to_key_bricks(keys):
+    """Dense keys [n_keys][nz][ny][nx] (uint8 or float32, or a sequence of such volumes of one shape) as the arguments of SetVolumeKeyBricks
+    (include/nrc_hpm.h, nrc_renderer_set_volume_key_bricks): (counts uint32 [n_keys], origins int32 [sum][3], bricks [sum][8][8][8]) --
+    every key's volume_to_bricks list, concatenated in key order."""
+    lists = [volume_to_bricks(k) for k in keys]
+    if not lists:
+        raise ValueError("volumes_to_key_bricks: at least one key")
+    if len({np.asarray(k).shape for k in keys}) != 1 or len({b.dtype for _, b in lists}) != 1:
+        raise ValueError("volumes_to_key_bricks: keys of one shape and one type")
+    counts = np.array([o.shape[0] for o, _ in lists], np.uint32)
+    return counts, np.ascontiguousarray(np.concatenate([o for o, _ in lists])), np.ascontiguousarray(np.concatenate([b for _, b in lists]))
+
+
+def key_bricks_to_volumes(counts, origins, bricks, dims, ignore_invalid=False):
+    """The dense keys [n_keys][nz][ny][nx] a brick key sequence stands for, dims = (nz, ny, nx): bricks_to_volume of every key's slice (the
+    inverse of volumes_to_key_bricks and the CPU statement of SetVolumeKeyBricks)."""
+    counts = [int(c) for c in counts]
+    origins, bricks = np.asarray(origins), np.asarray(bricks)
+    if sum(counts) != origins.shape[0] or origins.shape[0] != bricks.shape[0]:
+        raise ValueError("key_bricks_to_volumes: counts sum to %d, origins hold %d and bricks %d" % (sum(counts), origins.shape[0], bricks.shape[0]))
+    first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    vols = [bricks_to_volume(origins[a:b], bricks[a:b], dims, ignore_invalid) for a, b in zip(first[:-1], first[1:])]
+    return np.ascontiguousarray(np.stack(vols)) if vols else np.zeros((0,) + tuple(int(v) for v in dims), bricks.dtype)
+
+
+def key_brick_bytes(counts, dims):
+    """The device bytes a brick key sequence holds (nrc_renderer_volume_key_bytes): 512 * sum(counts) + 4 * n_keys * cells, dims = (nz, ny, nx)"""
+    cells = 1
+    for n in dims:
+        cells *= (int(n) + 7) // 8
+    return 512 * sum(int(c) for c in counts) + 4 * len(counts) * cells
+
+
 def white_env(value=1.0):
     """Quirk Q9 (src/read_file.cpp:129-130): every loaded env texel is overwritten with 1.0."""
     return np.full((1, 1, 4), value, np.float32)

@@ -1,10 +1,12 @@
 """What volume keyframes cost and buy (nrc_renderer_set_volume_keys / _set_volume_time / _render_path_timed), on an MI355X.
 
-  (a) rocprofv3 --kernel-trace --stats -d <dir> -- python tools/volume_keys_rate.py --rebuild-only lerp|dense --dims 256|512 [--calls 200]
+  (a) rocprofv3 --kernel-trace --stats -d <dir> -- python tools/volume_keys_rate.py --rebuild-only lerp|dense|bricks --dims 256|512 [--calls 200]
       only the rebuild runs, on a small MC renderer: `lerp` is SetVolumeTime at weights strictly between two keys (k_vol_ingest<VolLerp, ...> +
       k_vol_cells + k_vol_rows), `dense` is SetVolume of a device u8 volume (k_vol_ingest<VolDense<false>, ...> + the same two) -- the
       baseline: one kernel template, two voxel sources.  Each in a trace of its own: the two share k_vol_cells and k_vol_rows.  512 is the 256^3 cloud
-      doubled along every axis.  The in-between reads twice the source bytes; the ratio is reported, not bounded.
+      doubled along every axis.  The in-between reads twice the source bytes; the ratio is reported, not bounded.  `bricks` is `lerp` on the
+      same two keys held as 8^3 brick lists (SetVolumeKeyBricks: k_vol_ingest<VolLerpBricks, ...> + the same two); its line also carries
+      the bricks per key, the share of the cells they fill and the device bytes held against the dense keys'.
   (b) python tools/volume_keys_rate.py [--renderer nrc|mc|both] [--views 64] [--frames-per-view 4] [--keys 8] [--reps 7]
       a 64-view orbit, 4 frames per view, of the default preset (1920 x 1080, 6x64 cache, training on) and of the MC renderer at 32
       vertices, over 8 keys of the 256^3 fBm cloud (key k is the cloud rolled by 6 k voxels along x), view v at time v * 7 / 63:
@@ -47,19 +49,26 @@ def rebuild_only(how, dims, calls):
     other = np.ascontiguousarray(np.roll(vol, 7, axis=2))
     mc = api.McHpmRenderer(64, 64, 4, False, sc.make_camera(aspect=1.0), sc.make_scene(vol, scene_id=4))
     dv = [torch.from_numpy(vol).cuda(), torch.from_numpy(other).cuda()]
-    dkeys = torch.stack(dv)
-    mc.SetVolumeKeys(dkeys)
+    extra = {}
+    if how == "bricks":
+        counts, origins, bricks = sc.volumes_to_key_bricks([vol, other])
+        mc.SetVolumeKeyBricks(counts, torch.from_numpy(origins).cuda(), torch.from_numpy(bricks).cuda())
+        cells = (dims // 8) ** 3
+        extra = dict(bricks_per_key=[int(c) for c in counts], cell_share=float(counts.sum()) / (2 * cells), key_bytes_held=mc.VolumeKeyBytes(),
+                     dense_key_bytes=2 * int(vol.size))
+    else:
+        mc.SetVolumeKeys(torch.stack(dv))
     weights = [(1 + 37 * i) % 255 + 1 for i in range(calls)]      # 1 .. 255: never an end of the interval
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(calls):
-        if how == "lerp":
+        if how != "dense":
             mc.SetVolumeTime(weights[i] / 256.0)
         else:
             mc.SetVolume(dv[i % 2])
     torch.cuda.synchronize()
     emit(what="rebuild_only", how=how, dims=dims, calls=calls, wall_us_per_call=(time.perf_counter() - t0) / calls * 1e6,
-         source_bytes_per_call=int(vol.size) * (2 if how == "lerp" else 1))
+         source_bytes_per_call=512 * int(counts.sum()) + 8 * cells if how == "bricks" else int(vol.size) * (2 if how == "lerp" else 1), **extra)
     mc.Destroy()
 
 
@@ -160,7 +169,7 @@ def main():
     ap.add_argument("--frames-per-view", type=int, default=4)
     ap.add_argument("--keys", type=int, default=8)
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--rebuild-only", choices=["lerp", "dense"], default=None)
+    ap.add_argument("--rebuild-only", choices=["lerp", "dense", "bricks"], default=None)
     ap.add_argument("--dims", type=int, choices=[256, 512], default=256)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--record", default=None, metavar="FILE")
