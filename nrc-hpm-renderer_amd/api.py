@@ -335,68 +335,28 @@ VOLUME_U8, VOLUME_F32 = 0, 1      # NRC_VOLUME_U8 / NRC_VOLUME_F32
 VOLUME_BUF = dict(density=0, occ_bits=1, boxes=2)
 
 
-def _set_volume(fn, h, vol):
-    """SetVolume of both renderers: a C-contiguous numpy uint8 [nz][ny][nx] array (host memory: the call copies it and waits for the copy)
-    or a contiguous CUDA torch tensor, uint8 or float32 [nz][ny][nx] (read on the renderer's stream; the call does not wait)"""
-    if isinstance(vol, np.ndarray):
-        if vol.dtype != np.uint8 or vol.ndim != 3 or not vol.flags.c_contiguous:
-            raise RuntimeError("SkyRenderer ERROR: SetVolume takes a C-contiguous uint8 numpy array [nz][ny][nx] (got %s %s)" % (vol.dtype, vol.shape))
-        nz, ny, nx = vol.shape
-        _check(fn(h, C.c_void_p(vol.ctypes.data), nx, ny, nz, VOLUME_U8, 0))
-        return
-    import torch
-    if not isinstance(vol, torch.Tensor) or not vol.is_cuda or vol.dim() != 3 or not vol.is_contiguous() \
-            or vol.dtype not in (torch.uint8, torch.float32):
-        raise RuntimeError("SkyRenderer ERROR: SetVolume takes a contiguous CUDA tensor, uint8 or float32 [nz][ny][nx], or a uint8 numpy array")
-    nz, ny, nx = vol.shape
-    _check(fn(h, _dev_ptr(vol), nx, ny, nz, VOLUME_F32 if vol.dtype == torch.float32 else VOLUME_U8, 1))
-
-
-def _set_volume_bricks(fn, h, origins, bricks):
-    """SetVolumeBricks of both renderers: origins int32 [n][3] and bricks uint8 or float32 [n][8][8][8] ([dz][dy][dx]), both C-contiguous
-    numpy arrays (host memory: the call copies them and waits for the copy) or both contiguous CUDA torch tensors (read on the renderer's
-    stream; the call does not wait).  n = 0 is the empty medium."""
+def _brick_list(who, origins, bricks):
+    """a brick list of SetVolumeBricks / SetVolumeKeyBricks (`who`, for the error text): origins int32 [n][3] and bricks uint8 or float32
+    [n][8][8][8] ([dz][dy][dx]), both C-contiguous numpy arrays (host memory: the call copies them and waits for the copy) or both
+    contiguous CUDA torch tensors (read on the renderer's stream; the call does not wait).  Returns what the library call takes: the two
+    pointers (None for an empty list), n, the format and on_device."""
     if isinstance(origins, np.ndarray) and isinstance(bricks, np.ndarray):
         if origins.dtype != np.int32 or origins.ndim != 2 or origins.shape[1] != 3 or not origins.flags.c_contiguous \
                 or bricks.dtype not in (np.uint8, np.float32) or bricks.shape != (origins.shape[0], 8, 8, 8) or not bricks.flags.c_contiguous:
-            raise RuntimeError("SkyRenderer ERROR: SetVolumeBricks takes C-contiguous numpy arrays, origins int32 [n][3] and bricks uint8 or "
-                               "float32 [n][8][8][8] (got %s %s and %s %s)" % (origins.dtype, origins.shape, bricks.dtype, bricks.shape))
-        n = origins.shape[0]
-        fmt = VOLUME_F32 if bricks.dtype == np.float32 else VOLUME_U8
-        _check(fn(h, C.c_void_p(origins.ctypes.data) if n else None, C.c_void_p(bricks.ctypes.data) if n else None, n, fmt, 0))
-        return
-    import torch
-    ok = isinstance(origins, torch.Tensor) and isinstance(bricks, torch.Tensor) and origins.is_cuda and bricks.is_cuda \
-        and origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 3 and origins.is_contiguous() \
-        and bricks.dtype in (torch.uint8, torch.float32) and tuple(bricks.shape) == (origins.shape[0], 8, 8, 8) and bricks.is_contiguous()
-    if not ok:
-        raise RuntimeError("SkyRenderer ERROR: SetVolumeBricks takes contiguous CUDA tensors, origins int32 [n][3] and bricks uint8 or float32 "
-                           "[n][8][8][8], or two numpy arrays of those types")
+            raise RuntimeError("SkyRenderer ERROR: %s takes C-contiguous numpy arrays, origins int32 [n][3] and bricks uint8 or "
+                               "float32 [n][8][8][8] (got %s %s and %s %s)" % (who, origins.dtype, origins.shape, bricks.dtype, bricks.shape))
+        on_device, f32, ptr = 0, bricks.dtype == np.float32, lambda a: C.c_void_p(a.ctypes.data)
+    else:
+        import torch
+        ok = isinstance(origins, torch.Tensor) and isinstance(bricks, torch.Tensor) and origins.is_cuda and bricks.is_cuda \
+            and origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 3 and origins.is_contiguous() \
+            and bricks.dtype in (torch.uint8, torch.float32) and tuple(bricks.shape) == (origins.shape[0], 8, 8, 8) and bricks.is_contiguous()
+        if not ok:
+            raise RuntimeError("SkyRenderer ERROR: %s takes contiguous CUDA tensors, origins int32 [n][3] and bricks uint8 or float32 "
+                               "[n][8][8][8], or two numpy arrays of those types" % who)
+        on_device, f32, ptr = 1, bricks.dtype == torch.float32, _dev_ptr
     n = origins.shape[0]
-    fmt = VOLUME_F32 if bricks.dtype == torch.float32 else VOLUME_U8
-    _check(fn(h, _dev_ptr(origins) if n else None, _dev_ptr(bricks) if n else None, n, fmt, 1))
-
-
-def _set_volume_keys(fn, h, keys):
-    """SetVolumeKeys of both renderers: keys [n_keys][nz][ny][nx], a C-contiguous numpy array (host memory: the call copies it and waits for
-    the copy) or a contiguous CUDA torch tensor (read on the renderer's stream; the call does not wait for that), uint8 or float32; None
-    or an array of no keys drops the sequence"""
-    if keys is None:
-        _check(fn(h, None, 0, 0, 0, 0, VOLUME_U8, 0))
-        return
-    if isinstance(keys, np.ndarray):
-        if keys.dtype not in (np.uint8, np.float32) or keys.ndim != 4 or not keys.flags.c_contiguous:
-            raise RuntimeError("SkyRenderer ERROR: SetVolumeKeys takes a C-contiguous uint8 or float32 numpy array [n_keys][nz][ny][nx] (got %s %s)"
-                               % (keys.dtype, keys.shape))
-        n, nz, ny, nx = keys.shape
-        _check(fn(h, C.c_void_p(keys.ctypes.data) if n else None, n, nx, ny, nz, VOLUME_F32 if keys.dtype == np.float32 else VOLUME_U8, 0))
-        return
-    import torch
-    if not isinstance(keys, torch.Tensor) or not keys.is_cuda or keys.dim() != 4 or not keys.is_contiguous() \
-            or keys.dtype not in (torch.uint8, torch.float32):
-        raise RuntimeError("SkyRenderer ERROR: SetVolumeKeys takes a contiguous CUDA tensor or a numpy array, uint8 or float32 [n_keys][nz][ny][nx]")
-    n, nz, ny, nx = keys.shape
-    _check(fn(h, _dev_ptr(keys) if n else None, n, nx, ny, nz, VOLUME_F32 if keys.dtype == torch.float32 else VOLUME_U8, 1))
+    return ptr(origins) if n else None, ptr(bricks) if n else None, n, VOLUME_F32 if f32 else VOLUME_U8, on_device
 
 
 def _set_volume_key_bricks(fn, h, counts, origins, bricks):
@@ -411,27 +371,10 @@ def _set_volume_key_bricks(fn, h, counts, origins, bricks):
         raise RuntimeError("SkyRenderer ERROR: SetVolumeKeyBricks takes counts as a sequence of non-negative integers, one per key (got %r)" % (counts,))
     key_counts = np.ascontiguousarray(counts64, np.uint32)
     total = int(counts64.astype(np.uint64).sum())
-    if isinstance(origins, np.ndarray) and isinstance(bricks, np.ndarray):
-        ok = origins.dtype == np.int32 and origins.ndim == 2 and origins.shape[1] == 3 and origins.flags.c_contiguous \
-            and bricks.dtype in (np.uint8, np.float32) and bricks.shape == (origins.shape[0], 8, 8, 8) and bricks.flags.c_contiguous
-        if not ok:
-            raise RuntimeError("SkyRenderer ERROR: SetVolumeKeyBricks takes C-contiguous numpy arrays, origins int32 [n][3] and bricks uint8 or "
-                               "float32 [n][8][8][8] (got %s %s and %s %s)" % (origins.dtype, origins.shape, bricks.dtype, bricks.shape))
-        on_device, fmt = 0, VOLUME_F32 if bricks.dtype == np.float32 else VOLUME_U8
-        p_origins, p_bricks = C.c_void_p(origins.ctypes.data), C.c_void_p(bricks.ctypes.data)
-    else:
-        import torch
-        ok = isinstance(origins, torch.Tensor) and isinstance(bricks, torch.Tensor) and origins.is_cuda and bricks.is_cuda \
-            and origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 3 and origins.is_contiguous() \
-            and bricks.dtype in (torch.uint8, torch.float32) and tuple(bricks.shape) == (origins.shape[0], 8, 8, 8) and bricks.is_contiguous()
-        if not ok:
-            raise RuntimeError("SkyRenderer ERROR: SetVolumeKeyBricks takes contiguous CUDA tensors, origins int32 [n][3] and bricks uint8 or "
-                               "float32 [n][8][8][8], or two numpy arrays of those types")
-        on_device, fmt = 1, VOLUME_F32 if bricks.dtype == torch.float32 else VOLUME_U8
-        p_origins, p_bricks = _dev_ptr(origins), _dev_ptr(bricks)
-    if origins.shape[0] != total:
-        raise RuntimeError("SkyRenderer ERROR: SetVolumeKeyBricks: counts sum to %d bricks, origins and bricks hold %d" % (total, origins.shape[0]))
-    _check(fn(h, C.c_void_p(key_counts.ctypes.data), p_origins if total else None, p_bricks if total else None, key_counts.size, fmt, on_device))
+    p_origins, p_bricks, n, fmt, on_device = _brick_list("SetVolumeKeyBricks", origins, bricks)
+    if n != total:
+        raise RuntimeError("SkyRenderer ERROR: SetVolumeKeyBricks: counts sum to %d bricks, origins and bricks hold %d" % (total, n))
+    _check(fn(h, C.c_void_p(key_counts.ctypes.data), p_origins, p_bricks, key_counts.size, fmt, on_device))
 
 
 def _render_path(call, width, height, cameras, framesPerCamera, frameRandoms, out, times=None):
@@ -481,31 +424,113 @@ def _times_keyword(plain):
     return RenderPath
 
 
-def _tile_mask(fn, h):
-    n = fn(h, None, C.c_size_t(0))
-    out = np.zeros(n, np.uint32)
-    if n and fn(h, out.ctypes.data_as(C.c_void_p), C.c_size_t(n)) != n:
-        raise RuntimeError(load_library().nrc_last_error().decode() or "tile_mask failed")
-    return out
+class _LiveMedium:
+    """The medium of a live renderer: what NrcHpmRenderer and McHpmRenderer share (include/nrc_hpm.h declares every call once per renderer,
+    nrc_renderer_* and nrc_mc_renderer_*: _PREFIX is the class's).  Uses the renderer's self.L, self.h and self._scene."""
+    _PREFIX = None
 
+    def _medium(self, name):
+        return getattr(self.L, self._PREFIX + name)
 
-def _volume_buffer(fn, h, name, dims):
-    """the current volume's device buffers (synchronises the renderer): density uint8 [nz][ny][nx], occ_bits int32 words, boxes float32 [n][6]"""
-    import torch
-    if name not in VOLUME_BUF:
-        raise RuntimeError("SkyRenderer ERROR: VolumeBuffer name must be one of %s" % sorted(VOLUME_BUF))
-    nbytes = C.c_size_t(0)
-    p = fn(h, C.c_int(VOLUME_BUF[name]), C.byref(nbytes))
-    if not p:
-        if name == "boxes" and not load_library().nrc_last_error():
-            return torch.zeros((0, 6), dtype=torch.float32, device="cuda")
-        _check(-1)
-    if name == "density":
-        nx, ny, nz = dims
-        return _wrap_device(p, nbytes.value, torch.uint8, (nz, ny, nx))
-    if name == "occ_bits":
-        return _wrap_device(p, nbytes.value, torch.int32, (nbytes.value // 4,))
-    return _wrap_device(p, nbytes.value, torch.float32, (nbytes.value // 24, 6))
+    def TileMask(self):
+        """the empty-space tile mask in use (numpy uint32: the bit words + the trailing "off for this camera" word; empty: no mask in use);
+        synchronises the renderer"""
+        fn = self._medium("tile_mask")
+        n = fn(self.h, None, C.c_size_t(0))
+        out = np.zeros(n, np.uint32)
+        if n and fn(self.h, out.ctypes.data_as(C.c_void_p), C.c_size_t(n)) != n:
+            raise RuntimeError(self.L.nrc_last_error().decode() or "tile_mask failed")
+        return out
+
+    def SetSceneParams(self, scene):
+        """lights / medium constants of `scene` (dict of scene.make_scene or scene.HpmScene); textures are not re-uploaded"""
+        sc_ = make_c_scene(scene.scene if hasattr(scene, "scene") else scene)
+        _check(self._medium("set_scene_params")(self.h, C.byref(sc_)))
+
+    def SetVolume(self, vol):
+        """a new density volume with the creation dims (include/nrc_hpm.h, nrc_renderer_set_volume): frames rendered from now on see it,
+        blending restarts, the cache keeps its weights.  vol: a C-contiguous numpy uint8 [nz][ny][nx] array (host memory: the call copies
+        it and waits for the copy) or a contiguous CUDA torch tensor, uint8 or float32 [nz][ny][nx] (read on the renderer's stream; the call
+        does not wait)"""
+        fn = self._medium("set_volume")
+        if isinstance(vol, np.ndarray):
+            if vol.dtype != np.uint8 or vol.ndim != 3 or not vol.flags.c_contiguous:
+                raise RuntimeError("SkyRenderer ERROR: SetVolume takes a C-contiguous uint8 numpy array [nz][ny][nx] (got %s %s)" % (vol.dtype, vol.shape))
+            nz, ny, nx = vol.shape
+            _check(fn(self.h, C.c_void_p(vol.ctypes.data), nx, ny, nz, VOLUME_U8, 0))
+            return
+        import torch
+        if not isinstance(vol, torch.Tensor) or not vol.is_cuda or vol.dim() != 3 or not vol.is_contiguous() \
+                or vol.dtype not in (torch.uint8, torch.float32):
+            raise RuntimeError("SkyRenderer ERROR: SetVolume takes a contiguous CUDA tensor, uint8 or float32 [nz][ny][nx], or a uint8 numpy array")
+        nz, ny, nx = vol.shape
+        _check(fn(self.h, _dev_ptr(vol), nx, ny, nz, VOLUME_F32 if vol.dtype == torch.float32 else VOLUME_U8, 1))
+
+    def SetVolumeBricks(self, origins, bricks):
+        """the same from 8^3 bricks (include/nrc_hpm.h, nrc_renderer_set_volume_bricks; scene.volume_to_bricks makes them of a dense volume):
+        origins int32 [n][3] (x, y, z: multiples of 8), bricks uint8 or float32 [n][8][8][8], two numpy arrays or two CUDA tensors (_brick_list);
+        voxels no brick covers become 0, n = 0 is the empty medium"""
+        _check(self._medium("set_volume_bricks")(self.h, *_brick_list("SetVolumeBricks", origins, bricks)))
+
+    def SetVolumeKeys(self, keys):
+        """volume keyframes (include/nrc_hpm.h, nrc_renderer_set_volume_keys): keys [n_keys][nz][ny][nx] of the creation dims, uint8 or
+        float32, a C-contiguous numpy array (host memory: the call copies it and waits for the copy) or a contiguous CUDA torch tensor
+        (read on the renderer's stream; the call does not wait for that); key i sits at time i.  The renderer keeps its own R8 copy on the
+        device.  None or an array of no keys drops the sequence.  Not a per-frame call: it may wait for the frames in flight."""
+        fn = self._medium("set_volume_keys")
+        if keys is None:
+            _check(fn(self.h, None, 0, 0, 0, 0, VOLUME_U8, 0))
+            return
+        if isinstance(keys, np.ndarray):
+            if keys.dtype not in (np.uint8, np.float32) or keys.ndim != 4 or not keys.flags.c_contiguous:
+                raise RuntimeError("SkyRenderer ERROR: SetVolumeKeys takes a C-contiguous uint8 or float32 numpy array [n_keys][nz][ny][nx] (got %s %s)"
+                                   % (keys.dtype, keys.shape))
+            n, nz, ny, nx = keys.shape
+            _check(fn(self.h, C.c_void_p(keys.ctypes.data) if n else None, n, nx, ny, nz, VOLUME_F32 if keys.dtype == np.float32 else VOLUME_U8, 0))
+            return
+        import torch
+        if not isinstance(keys, torch.Tensor) or not keys.is_cuda or keys.dim() != 4 or not keys.is_contiguous() \
+                or keys.dtype not in (torch.uint8, torch.float32):
+            raise RuntimeError("SkyRenderer ERROR: SetVolumeKeys takes a contiguous CUDA tensor or a numpy array, uint8 or float32 [n_keys][nz][ny][nx]")
+        n, nz, ny, nx = keys.shape
+        _check(fn(self.h, _dev_ptr(keys) if n else None, n, nx, ny, nz, VOLUME_F32 if keys.dtype == torch.float32 else VOLUME_U8, 1))
+
+    def SetVolumeKeyBricks(self, counts, origins, bricks):
+        """the same sequence held as 8^3 brick lists (include/nrc_hpm.h, nrc_renderer_set_volume_key_bricks; scene.volumes_to_key_bricks makes
+        the three of dense keys): counts = bricks per key, origins int32 [sum][3] and bricks uint8 or float32 [sum][8][8][8] the keys' lists
+        in key order, numpy arrays or CUDA tensors.  It replaces a dense sequence and the other way round; counts None drops the sequence.
+        Not a per-frame call."""
+        _set_volume_key_bricks(self._medium("set_volume_key_bricks"), self.h, counts, origins, bricks)
+
+    def VolumeKeyBytes(self):
+        """the device bytes the current key sequence holds (dense: n_keys * nx*ny*nz; bricks: 512 * sum(counts) + 4 * n_keys * cells)"""
+        return int(self._medium("volume_key_bytes")(self.h))
+
+    def VolumeKeyCount(self):
+        return int(self._medium("volume_key_count")(self.h))
+
+    def SetVolumeTime(self, t):
+        """the medium becomes the in-between of the two keys around time t, 0 <= t <= VolumeKeyCount() - 1 (scene.volume_at is the CPU
+        statement): what SetVolume of that volume does, without a host wait"""
+        _check(self._medium("set_volume_time")(self.h, C.c_float(float(t))))
+
+    def VolumeBuffer(self, name):
+        """device view of the current volume's buffers (after synchronising the renderer): 'density' uint8 [nz][ny][nx], 'occ_bits' int32
+        words, 'boxes' float32 [n][6]"""
+        import torch
+        if name not in VOLUME_BUF:
+            raise RuntimeError("SkyRenderer ERROR: VolumeBuffer name must be one of %s" % sorted(VOLUME_BUF))
+        nbytes = C.c_size_t(0)
+        p = self._medium("volume_buffer")(self.h, C.c_int(VOLUME_BUF[name]), C.byref(nbytes))
+        if not p:
+            if name == "boxes" and not self.L.nrc_last_error():
+                return torch.zeros((0, 6), dtype=torch.float32, device="cuda")
+            _check(-1)
+        if name == "density":
+            return _wrap_device(p, nbytes.value, torch.uint8, (self._scene.nz, self._scene.ny, self._scene.nx))
+        if name == "occ_bits":
+            return _wrap_device(p, nbytes.value, torch.int32, (nbytes.value // 4,))
+        return _wrap_device(p, nbytes.value, torch.float32, (nbytes.value // 24, 6))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -805,8 +830,9 @@ class NeuralRadianceCache:
 
 
 # ------------------------------------------------------------------------------------------------------------------
-class NrcHpmRenderer:
+class NrcHpmRenderer(_LiveMedium):
     """en::NrcHpmRenderer (src/NrcHpmRenderer.cu).  `queue` arguments of the reference become the HIP stream."""
+    _PREFIX = "nrc_renderer_"
     BUF = dict(primary=0, info=1, origin=2, dir=3, infer_input=4, infer_output=5, train_input=6, train_target=7, ring=8,
                tail_query=9, tail_record=10, tail_output=11)
 
@@ -862,57 +888,8 @@ class NrcHpmRenderer:
             return self.L.nrc_renderer_render_path_timed(self.h, n, cams, t, fpc, rnd, tr, img)
         return _render_path(call, self.width, self.height, cameras, framesPerCamera, frameRandoms, out, times)
 
-    def TileMask(self):
-        """the empty-space tile mask in use (numpy uint32: the bit words + the trailing "off for this camera" word; empty: no mask in use);
-        synchronises the renderer"""
-        return _tile_mask(self.L.nrc_renderer_tile_mask, self.h)
-
     def SetBlend(self, blend):
         _check(self.L.nrc_renderer_set_blend(self.h, C.c_int(int(blend))))
-
-    def SetSceneParams(self, scene):
-        """lights / medium constants of `scene` (dict of scene.make_scene or scene.HpmScene); textures are not re-uploaded"""
-        sc_ = make_c_scene(scene.scene if hasattr(scene, "scene") else scene)
-        _check(self.L.nrc_renderer_set_scene_params(self.h, C.byref(sc_)))
-
-    def SetVolume(self, vol):
-        """a new density volume with the creation dims (include/nrc_hpm.h, nrc_renderer_set_volume): frames rendered from now on see it,
-        blending restarts, the cache keeps its weights"""
-        _set_volume(self.L.nrc_renderer_set_volume, self.h, vol)
-
-    def SetVolumeBricks(self, origins, bricks):
-        """the same from 8^3 bricks (include/nrc_hpm.h, nrc_renderer_set_volume_bricks; scene.volume_to_bricks makes them of a dense volume):
-        origins int32 [n][3] (x, y, z: multiples of 8), bricks uint8 or float32 [n][8][8][8]; voxels no brick covers become 0"""
-        _set_volume_bricks(self.L.nrc_renderer_set_volume_bricks, self.h, origins, bricks)
-
-    def SetVolumeKeys(self, keys):
-        """volume keyframes (include/nrc_hpm.h, nrc_renderer_set_volume_keys): keys [n_keys][nz][ny][nx] of the creation dims, uint8 or
-        float32, a numpy array or a CUDA tensor; key i sits at time i.  The renderer keeps its own R8 copy on the device.  None drops the
-        sequence.  Not a per-frame call: it may wait for the frames in flight."""
-        _set_volume_keys(self.L.nrc_renderer_set_volume_keys, self.h, keys)
-
-    def SetVolumeKeyBricks(self, counts, origins, bricks):
-        """the same sequence held as 8^3 brick lists (include/nrc_hpm.h, nrc_renderer_set_volume_key_bricks; scene.volumes_to_key_bricks makes
-        the three of dense keys): counts = bricks per key, origins int32 [sum][3] and bricks uint8 or float32 [sum][8][8][8] the keys' lists
-        in key order, numpy arrays or CUDA tensors.  It replaces a dense sequence and the other way round; counts None drops the sequence.
-        Not a per-frame call."""
-        _set_volume_key_bricks(self.L.nrc_renderer_set_volume_key_bricks, self.h, counts, origins, bricks)
-
-    def VolumeKeyBytes(self):
-        """the device bytes the current key sequence holds (dense: n_keys * nx*ny*nz; bricks: 512 * sum(counts) + 4 * n_keys * cells)"""
-        return int(self.L.nrc_renderer_volume_key_bytes(self.h))
-
-    def VolumeKeyCount(self):
-        return int(self.L.nrc_renderer_volume_key_count(self.h))
-
-    def SetVolumeTime(self, t):
-        """the medium becomes the in-between of the two keys around time t, 0 <= t <= VolumeKeyCount() - 1 (scene.volume_at is the CPU
-        statement): what SetVolume of that volume does, without a host wait"""
-        _check(self.L.nrc_renderer_set_volume_time(self.h, C.c_float(float(t))))
-
-    def VolumeBuffer(self, name):
-        """device view of the current volume's 'density', 'occ_bits' or 'boxes' (after synchronising the renderer)"""
-        return _volume_buffer(self.L.nrc_renderer_volume_buffer, self.h, name, (self._scene.nx, self._scene.ny, self._scene.nz))
 
     def SetShowNrc(self, show):
         _check(self.L.nrc_renderer_set_show_nrc(self.h, C.c_int(int(show))))
@@ -1082,8 +1059,9 @@ class NrcHpmRenderer:
             pass
 
 
-class McHpmRenderer:
+class McHpmRenderer(_LiveMedium):
     """en::McHpmRenderer (src/McHpmRenderer.cpp)."""
+    _PREFIX = "nrc_mc_renderer_"
 
     def __init__(self, width, height, pathLength, blend, camera, scene, tile=None, stream=None):
         self.L = load_library()
@@ -1119,10 +1097,6 @@ class McHpmRenderer:
             return self.L.nrc_mc_renderer_render_path_timed(self.h, n, cams, t, fpc, rnd, img)
         return _render_path(call, self.width, self.height, cameras, framesPerCamera, frameRandoms, out, times)
 
-    def TileMask(self):
-        """see NrcHpmRenderer.TileMask"""
-        return _tile_mask(self.L.nrc_mc_renderer_tile_mask, self.h)
-
     def SetBlend(self, blend):
         _check(self.L.nrc_mc_renderer_set_blend(self.h, C.c_int(int(blend))))
 
@@ -1134,41 +1108,6 @@ class McHpmRenderer:
 
     def SetCostOrder(self, on=True):
         _check(self.L.nrc_mc_renderer_set_cost_order(self.h, C.c_int(int(on))))
-
-    def SetSceneParams(self, scene):
-        sc_ = make_c_scene(scene.scene if hasattr(scene, "scene") else scene)
-        _check(self.L.nrc_mc_renderer_set_scene_params(self.h, C.byref(sc_)))
-
-    def SetVolume(self, vol):
-        """see NrcHpmRenderer.SetVolume"""
-        _set_volume(self.L.nrc_mc_renderer_set_volume, self.h, vol)
-
-    def SetVolumeBricks(self, origins, bricks):
-        """see NrcHpmRenderer.SetVolumeBricks"""
-        _set_volume_bricks(self.L.nrc_mc_renderer_set_volume_bricks, self.h, origins, bricks)
-
-    def SetVolumeKeys(self, keys):
-        """see NrcHpmRenderer.SetVolumeKeys"""
-        _set_volume_keys(self.L.nrc_mc_renderer_set_volume_keys, self.h, keys)
-
-    def SetVolumeKeyBricks(self, counts, origins, bricks):
-        """see NrcHpmRenderer.SetVolumeKeyBricks"""
-        _set_volume_key_bricks(self.L.nrc_mc_renderer_set_volume_key_bricks, self.h, counts, origins, bricks)
-
-    def VolumeKeyBytes(self):
-        """see NrcHpmRenderer.VolumeKeyBytes"""
-        return int(self.L.nrc_mc_renderer_volume_key_bytes(self.h))
-
-    def VolumeKeyCount(self):
-        return int(self.L.nrc_mc_renderer_volume_key_count(self.h))
-
-    def SetVolumeTime(self, t):
-        """see NrcHpmRenderer.SetVolumeTime"""
-        _check(self.L.nrc_mc_renderer_set_volume_time(self.h, C.c_float(float(t))))
-
-    def VolumeBuffer(self, name):
-        """see NrcHpmRenderer.VolumeBuffer"""
-        return _volume_buffer(self.L.nrc_mc_renderer_volume_buffer, self.h, name, (self._scene.nx, self._scene.ny, self._scene.nz))
 
     def SetFrameRandom(self, r4):
         r = (C.c_float * 4)(*[float(x) for x in r4])

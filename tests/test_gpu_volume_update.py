@@ -41,6 +41,11 @@ def _as_source(vol, source):
     return torch.from_numpy((vol.astype(np.float32) + np.float32(0.5)) / np.float32(255.0)).cuda()
 
 
+# device allocations a renderer's first SetVolume makes: four buffers per slot (density, occupancy bits, boxes, box count) and the rebuild
+# scratch, two slots for NRC and one for MC.  Counted with live_allocations() at commit f36b916, before the slot choice moved.
+FIRST_SWAP_ALLOCATIONS = {"nrc": 9, "mc": 5}
+
+
 @pytest.mark.parametrize("kind", ["nrc", "mc"])
 @pytest.mark.parametrize("source", ["u8_host", "u8_device", "f32_device"])
 def test_device_rebuild_equals_creation_build(api, sc, cloud16, torch_gpu, kind, source):
@@ -53,11 +58,18 @@ def test_device_rebuild_equals_creation_build(api, sc, cloud16, torch_gpu, kind,
     for shape, vols in groups.items():
         other = np.ascontiguousarray(np.flip(vols[0][1], axis=0) // 2 + 1)      # created with another volume of the same dims
         ren, nrc = _make(api, sc, kind, other)
-        for name, v in vols:
+        for i, (name, v) in enumerate(vols):
             fresh, fnrc = _make(api, sc, "mc", v)
             want = volume_buffers(fresh)
             fresh.Destroy()
-            ren.SetVolume(_as_source(v, source))
+            src = _as_source(v, source)
+            held = api.live_allocations()
+            ren.SetVolume(src)
+            if source == "u8_device":      # (a device source: no staging buffer comes and goes)
+                # DESIGN.md's memory table: nothing before the first swap, which allocates the slots -- NRC two, MC one -- and nothing after
+                grown = api.live_allocations() - held
+                print("%s %s SetVolume %d: %+d device allocations" % (kind, name, i, grown))
+                assert grown == (FIRST_SWAP_ALLOCATIONS[kind] if i == 0 else 0), (kind, name, i, grown)
             got = volume_buffers(ren)
             assert_same_volume(got, want, name)
         ren.Destroy()
