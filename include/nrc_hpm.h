@@ -642,6 +642,53 @@ int nrc_compare_images_sharded(nrc_cache_t* comm, const float* d_ref_local_rgba,
 int nrc_image_create(uint32_t w, uint32_t h, const float* host_rgba, float** d_out);
 int nrc_image_destroy(float* d_image);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * View AOV: opacity and depth per pixel, exact for the medium (both renderers; every call has an nrc_mc_renderer_ twin).
+ * A view AOV is an [h][w][4] fp32 image of {alpha, tau, z_front, z_half} per pixel; a sharded renderer holds its local columns, as its
+ * framebuffer does.  It depends on the camera and the medium alone -- no random numbers, no frames -- and neither renderer's framebuffer
+ * alpha changes (the NRC renderer's stays 1, the Monte-Carlo renderer's the blended scatter fraction, of which alpha is the expectation).
+ *   Ray.     The pixel's camera ray is the one the frames trace: inv_proj_view applied to the frames' own fp32 u = global x / global_w,
+ *            v = y / global_h (no half-pixel offset, no y flip), from camera.pos, normalised.  Distances t are along that ray from
+ *            camera.pos.  The frames form the direction as (w.xyz / w.w) - pos in plain fp32, which at |pos| = 70 is 2e-5 rad from the
+ *            ray of the fp32 matrix -- 1.5e-3 where it meets the medium, more than a depth should be off by.  The AOV evaluates the same
+ *            expression with the large terms cancelled before anything is rounded (csrc/nrc_view_aov.hpp, view_aov_camera_ray): within
+ *            5e-7 rad of that ray evaluated in fp64, and so within 3e-5 rad of the direction a frame's pixel traces.
+ *   Density. sigma(p) = density_factor * u8 / 255 of the voxel that holds p (the frames' NEAREST look-up) inside the box, 0 outside:
+ *            piecewise constant.  With t0 = max(0, box entry) and t1 = box exit,  tau = integral of sigma dt over [t0, t1].
+ *   alpha    = 1 - exp(-tau).
+ *   z_front  = the smallest t with sigma > 0.
+ *   z_half   = the t at which the optical depth reaches ln 2, linear inside the voxel where it does; defined only when tau >= ln 2.
+ *   An undefined depth is +inf.  A ray that misses the box or meets no non-empty voxel gives {0, 0, +inf, +inf}; so does every pixel
+ *   of an 8x8 tile that the empty-space tile mask rejects (no ray of such a tile comes within a voxel of a non-empty one).
+ *   No NaN for any finite camera; 0 <= alpha <= 1; 0 <= z_front <= z_half where both are finite.
+ * The fp32 arithmetic is defined once, in csrc/nrc_view_aov.hpp, which the kernel and the host (nrc_test_view_aov_host) both run:
+ *   voxel plane i of axis a lies at t_a(i) = fma(i, k_a, c_a), k_a = (size_a / n_a) / rd_a, c_a = (-size_a / 2 - ro_a) / rd_a -- from the
+ *   plane's index, never a running sum; an axis with rd_a == 0 is never crossed, and the ray misses if |ro_a| >= size_a / 2; tau is
+ *   accumulated front to back as fma(sigma_i, t_next - t_cur, tau); alpha = nrc_expm1_negf(tau) (csrc/nrc_math.h).  The result does not
+ *   depend on how a traversal skips empty space (a skipped segment adds an exact 0), with or without the tile mask
+ *   (nrc_renderer_set_empty_skip), and is bit-identical between the kernel and the host.
+ * nrc_renderer_view_aov: the AOV of the current camera and medium (device memory, owned by the renderer, valid until the renderer is
+ *   destroyed).  It is computed at most once per change of camera (set_camera, a path's views), volume (set_volume, set_volume_bricks,
+ *   set_volume_time) or scene parameters, by one launch on the render stream behind the volume rebuilds and frames enqueued so far; no
+ *   host wait.  The creation stream is ordered behind it, as for nrc_renderer_framebuffer.  A renderer on which none of these calls
+ *   is made allocates and launches nothing for them.  NULL on failure.
+ * nrc_renderer_set_path_aov_target: the next nrc_renderer_render_path / _render_path_timed call writes view i's AOV -- of that view's
+ *   camera and, in a timed path, its in-between medium -- to d_aovs + i * h * w * 4 (device memory, n_views * h * w * 4 floats).  That
+ *   call consumes the target.  A path call whose n_cameras is not n_views fails with NRC_ERR_INVALID, enqueues nothing and drops the
+ *   target.  d_aovs == NULL cancels.  When the path call returns, the creation stream is ordered behind the last AOV, as it is for
+ *   d_frames.  Frames, d_frames and training state are bit for bit what they are without a target.
+ * nrc_renderer_export_exr_aov: nrc_renderer_export_exr with FLOAT channels A, B, G, R, Z, Zhalf, tau -- A = alpha (not the
+ *   framebuffer's), Z = z_front; B, G, R the framebuffer's.  Readers of the RGBA file still find R, G, B, A.
+ * nrc_test_view_aov_host (test hook): the same image computed on the CPU inside the library, by the header's plain voxel walk, for the
+ *   scene as a renderer of w x h pixels would hold it (tile: as for nrc_renderer_create_tiled, or NULL); host memory, no device. */
+const float* nrc_renderer_view_aov(nrc_renderer_t* r);
+int nrc_renderer_set_path_aov_target(nrc_renderer_t* r, float* d_aovs, uint32_t n_views);
+int nrc_renderer_export_exr_aov(nrc_renderer_t* r, const char* path);
+const float* nrc_mc_renderer_view_aov(nrc_mc_renderer_t* r);
+int nrc_mc_renderer_set_path_aov_target(nrc_mc_renderer_t* r, float* d_aovs, uint32_t n_views);
+int nrc_mc_renderer_export_exr_aov(nrc_mc_renderer_t* r, const char* path);
+int nrc_test_view_aov_host(const nrc_scene* scene, const nrc_camera* camera, uint32_t w, uint32_t h, const nrc_tile* tile, float* host_out);
+
 /* THE environment switch of the library: NRC_DEBUG="name[=value],..." -- diagnostic and test switches only, none changes a result
  * (the list and what each does: csrc/nrc_common.hpp, debug_switch).
  * diagnostics (read when the library first allocates): NRC_DEBUG=poison_alloc fills every device allocation with 0xFF

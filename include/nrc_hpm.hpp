@@ -463,6 +463,18 @@ public:
     {
         nrc_check(nrc_renderer_render_path_timed(h_, nCameras, cameras, times, framesPerCamera, frameRandoms, train ? 1 : 0, dFrames));
     }
+    // The view AOV (include/nrc_hpm.h, "View AOV"): device [height][width][4] {alpha, tau, z_front, z_half} of the current camera and medium,
+    // computed at most once per change, the creation stream ordered behind it; throws on failure (nrc_renderer_view_aov)
+    const float* GetViewAov() const
+    {
+        const float* p = nrc_renderer_view_aov(h_);
+        if (p == nullptr) nrc_check(NRC_ERR_STATE);
+        return p;
+    }
+    // the next RenderPath with nViews cameras writes view i's AOV to dAovs + i * height * width * 4 (device; nullptr cancels)
+    void SetPathAovTarget(float* dAovs, uint32_t nViews) { nrc_check(nrc_renderer_set_path_aov_target(h_, dAovs, nViews)); }
+    // ExportOutputImageToFile with the AOV beside the colours: FLOAT channels A (= alpha), B, G, R, Z (= z_front), Zhalf, tau; this renderer's pixels
+    void ExportOutputImageWithAovToFile(void* /*queue*/, const std::string& filePath) const { nrc_check(nrc_renderer_export_exr_aov(h_, filePath.c_str())); }
     // diagnostics: the empty-space tile mask in use (synchronises; empty: the frame uses none) -- nrc_renderer_tile_mask
     std::vector<uint32_t> TileMask() const
     {
@@ -549,6 +561,15 @@ public:
     {
         nrc_check(nrc_mc_renderer_render_path_timed(h_, nCameras, cameras, times, framesPerCamera, frameRandoms, dFrames));
     }
+    // see NrcHpmRenderer::GetViewAov / SetPathAovTarget / ExportOutputImageWithAovToFile
+    const float* GetViewAov() const
+    {
+        const float* p = nrc_mc_renderer_view_aov(h_);
+        if (p == nullptr) nrc_check(NRC_ERR_STATE);
+        return p;
+    }
+    void SetPathAovTarget(float* dAovs, uint32_t nViews) { nrc_check(nrc_mc_renderer_set_path_aov_target(h_, dAovs, nViews)); }
+    void ExportOutputImageWithAovToFile(void* /*queue*/, const std::string& filePath) const { nrc_check(nrc_mc_renderer_export_exr_aov(h_, filePath.c_str())); }
     std::vector<uint32_t> TileMask() const
     {
         std::vector<uint32_t> m(nrc_mc_renderer_tile_mask(h_, nullptr, 0));

@@ -91,6 +91,8 @@ ABI_SYMBOLS = [
     "nrc_renderer_set_volume_key_bricks", "nrc_mc_renderer_set_volume_key_bricks", "nrc_renderer_volume_key_bytes", "nrc_mc_renderer_volume_key_bytes",
     "nrc_renderer_set_volume_time", "nrc_mc_renderer_set_volume_time", "nrc_renderer_render_path_timed", "nrc_mc_renderer_render_path_timed",
     "nrc_renderer_render_path", "nrc_mc_renderer_render_path", "nrc_renderer_tile_mask", "nrc_mc_renderer_tile_mask",
+    "nrc_renderer_view_aov", "nrc_mc_renderer_view_aov", "nrc_renderer_set_path_aov_target", "nrc_mc_renderer_set_path_aov_target",
+    "nrc_renderer_export_exr_aov", "nrc_mc_renderer_export_exr_aov", "nrc_test_view_aov_host",
     "nrc_renderer_set_show_nrc", "nrc_renderer_set_frame_random", "nrc_renderer_framebuffer", "nrc_renderer_framebuffer_on",
     "nrc_renderer_export_exr",
     "nrc_renderer_frame_time_ms", "nrc_renderer_stage_stats", "nrc_renderer_frame_timeline", "nrc_set_wave_priority_raise", "nrc_renderer_destroy", "nrc_renderer_buffer", "nrc_renderer_count_fetches",
@@ -185,6 +187,15 @@ def load_library():
         for name in ("nrc_renderer_volume_key_bytes", "nrc_mc_renderer_volume_key_bytes"):
             getattr(L, name).restype = C.c_size_t
             getattr(L, name).argtypes = [C.c_void_p]
+    if hasattr(L, "nrc_renderer_view_aov"):      # (an older build loaded through NRC_HPM_LIB has no view AOV)
+        for name in ("nrc_renderer_view_aov", "nrc_mc_renderer_view_aov"):
+            getattr(L, name).restype = C.c_void_p
+            getattr(L, name).argtypes = [C.c_void_p]
+        for name in ("nrc_renderer_set_path_aov_target", "nrc_mc_renderer_set_path_aov_target"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        for name in ("nrc_renderer_export_exr_aov", "nrc_mc_renderer_export_exr_aov"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_char_p]
+        L.nrc_test_view_aov_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     L.nrc_mc_renderer_frame_time_ms.restype = C.c_float
     for name in ("nrc_cache_get_loss", "nrc_cache_get_loss_blocking", "nrc_renderer_is_blending", "nrc_mc_renderer_is_blending",
                  "nrc_cache_get_infer_batch_count", "nrc_cache_get_train_batch_count",
@@ -411,16 +422,29 @@ def _render_path(call, width, height, cameras, framesPerCamera, frameRandoms, ou
 
 
 def _times_keyword(plain):
-    """RenderPath(..., times=None) of both renderers.  The keyword rides on the untimed method: its positional signature is a published
-    one (callers and tests/test_camera_path_host.py name its parameters in order) and stays what inspect.signature reports; a call
-    without times is `plain`'s own, a call with times goes to the renderer's _path with the same arguments."""
+    """RenderPath(..., times=None, aov_out=None) of both renderers.  The keywords ride on the untimed method: its positional signature is
+    a published one (callers and tests/test_camera_path_host.py name its parameters in order) and stays what inspect.signature reports; a
+    call without times is `plain`'s own, a call with times goes to the renderer's _path with the same arguments.
+    aov_out: a contiguous float32 CUDA tensor [len(cameras)][height][width][4] that receives every view's AOV ({alpha, tau, z_front,
+    z_half} of that view's camera and medium: ViewAov, nrc_renderer_set_path_aov_target); frames, `out` and training are unchanged by it."""
     @functools.wraps(plain)
-    def RenderPath(self, *args, times=None, **kw):
-        if times is None:
-            return plain(self, *args, **kw)
+    def RenderPath(self, *args, times=None, aov_out=None, **kw):
         bound = inspect.signature(plain).bind(self, *args, **kw)
         bound.apply_defaults()
-        return self._path(*list(bound.arguments.values())[1:], times)
+        if aov_out is not None:
+            import torch
+            shape = (len(list(bound.arguments["cameras"])), self.height, self.width, 4)
+            if not isinstance(aov_out, torch.Tensor) or not aov_out.is_cuda or aov_out.dtype != torch.float32 \
+                    or tuple(aov_out.shape) != shape or not aov_out.is_contiguous():
+                raise ValueError("RenderPath: aov_out must be a contiguous float32 CUDA tensor of shape %s" % (shape,))
+            self.SetPathAovTarget(aov_out)
+        try:
+            if times is None:
+                return plain(self, *args, **kw)
+            return self._path(*list(bound.arguments.values())[1:], times)
+        finally:
+            if aov_out is not None:      # (consumed by the path call; a call that failed before it reached the library leaves none behind)
+                self.SetPathAovTarget(None)
     return RenderPath
 
 
@@ -441,6 +465,31 @@ class _LiveMedium:
         if n and fn(self.h, out.ctypes.data_as(C.c_void_p), C.c_size_t(n)) != n:
             raise RuntimeError(self.L.nrc_last_error().decode() or "tile_mask failed")
         return out
+
+    def ViewAov(self):
+        """the view AOV of the current camera and medium (include/nrc_hpm.h, "View AOV"): a torch CUDA tensor view [height, width, 4] of
+        {alpha, tau, z_front, z_half} per pixel -- exact opacity 1 - exp(-tau), optical depth, distance to the first non-empty voxel and
+        to optical depth ln 2 along the pixel's camera ray (+inf where undefined).  Computed at most once per change of camera, volume
+        or scene parameters, on the renderer's stream; the stream given at construction is ordered behind it.  The tensor is the
+        renderer's buffer: the next ViewAov() after a change rewrites it."""
+        import torch
+        p = self._medium("view_aov")(self.h)
+        if not p:
+            raise RuntimeError(self.L.nrc_last_error().decode() or "view_aov failed")
+        return _wrap_device(p, self.width * self.height * 16, torch.float32, (self.height, self.width, 4))
+
+    def SetPathAovTarget(self, aovs, views=None):
+        """nrc_renderer_set_path_aov_target: the next RenderPath writes view i's AOV to aovs[i] (a contiguous float32 CUDA tensor
+        [views][height][width][4]; None cancels).  RenderPath(..., aov_out=) makes this call itself."""
+        if aovs is None:
+            _check(self._medium("set_path_aov_target")(self.h, None, C.c_uint32(0)))
+        else:
+            _check(self._medium("set_path_aov_target")(self.h, _dev_ptr(aovs), C.c_uint32(int(aovs.shape[0]) if views is None else int(views))))
+
+    def ExportImageWithAovToFile(self, filePath):
+        """ExportOutputImageToFile with the view AOV beside the colours: a scan-line EXR with FLOAT channels A (alpha of the AOV), B, G, R,
+        Z (z_front), Zhalf, tau (io_exr.read_exr_channels; io_exr.read_exr still finds RGBA).  This renderer's pixels only."""
+        _check(self._medium("export_exr_aov")(self.h, filePath.encode()))
 
     def SetSceneParams(self, scene):
         """lights / medium constants of `scene` (dict of scene.make_scene or scene.HpmScene); textures are not re-uploaded"""
@@ -1185,6 +1234,18 @@ def test_math(fn, a, b=None):
     _check(load_library().nrc_test_math(C.c_int(fn), _dev_ptr(a), _dev_ptr(b) if b is not None else None,
                                         C.c_uint32(a.numel()), _dev_ptr(out), _dev_ptr(out2), _stream_ptr(None)))
     return out, out2
+
+
+def test_view_aov_host(scene, camera, width, height, tile=None):
+    """nrc_test_view_aov_host: the view AOV [height][width][4] (numpy) of `scene` (scene.make_scene) seen from `camera`, computed on the
+    CPU inside the library by csrc/nrc_view_aov.hpp's plain voxel walk; tile: the strip of a sharded frame, as for the renderers"""
+    sc_ = make_c_scene(scene.scene if hasattr(scene, "scene") else scene)
+    cam = make_c_camera(camera)
+    t = NrcTile(*[int(x) for x in tile]) if tile is not None else None
+    out = np.empty((height, width, 4), np.float32)
+    _check(load_library().nrc_test_view_aov_host(C.byref(sc_), C.byref(cam), C.c_uint32(width), C.c_uint32(height),
+                                                 C.byref(t) if t is not None else None, out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def test_rng(u, v, frame_random, n):

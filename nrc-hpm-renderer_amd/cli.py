@@ -67,6 +67,21 @@ def check_orbit_args(args):
     return args.orbit
 
 
+def check_aov_args(args):
+    """what --aov can be combined with (raises SystemExit)"""
+    if not getattr(args, "aov", False):
+        return
+    if not args.export:
+        raise SystemExit("SkyRenderer ERROR: --aov adds channels to the files --export writes: give --export")
+    if args.gpus > 1:
+        raise SystemExit("SkyRenderer ERROR: --aov is not available with --gpus (a sharded renderer holds its own columns' AOV only)")
+
+
+def aov_planes(rgba, aov):
+    """the channels of an --aov file from a view's [h][w][4] framebuffer and AOV: what ExportImageWithAovToFile writes"""
+    return {"R": rgba[..., 0], "G": rgba[..., 1], "B": rgba[..., 2], "A": aov[..., 0], "tau": aov[..., 1], "Z": aov[..., 2], "Zhalf": aov[..., 3]}
+
+
 def check_animate_args(args):
     """what --animate needs (raises SystemExit); returns whether the run is an animated fly-through"""
     if not getattr(args, "animate", False):
@@ -112,6 +127,10 @@ def main(argv=None):
     ap.add_argument("--ref-frames", type=int, default=256)
     ap.add_argument("--output", default="output")
     ap.add_argument("--export", default=None, help="write the final NRC image to this EXR; with --orbit a pattern such as out_%%04d.exr writes one file per view")
+    ap.add_argument("--aov", action="store_true",
+                    help="with --export: the files also carry the view AOV (exact opacity and depth per pixel) as FLOAT channels -- A = alpha "
+                         "instead of the framebuffer's constant 1, Z = distance to the first non-empty voxel, Zhalf = distance to optical depth "
+                         "ln 2, tau = optical depth -- for compositing; one GPU")
     ap.add_argument("--orbit", type=int, default=None, metavar="N",
                     help="render an N-view turntable around the volume with one RenderPath call (include/nrc_hpm.h, nrc_renderer_render_path): "
                          "--frames frames per view")
@@ -138,6 +157,7 @@ def main(argv=None):
         raise SystemExit("SkyRenderer ERROR: --frames-per-volume must be at least 1")
     animate = check_animate_args(args)
     n_views = check_orbit_args(args)
+    check_aov_args(args)
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # start the ranks before anything touches the GPU in this process (a process that has initialised HIP must not spawn them)
@@ -257,7 +277,9 @@ def main(argv=None):
             else:
                 nrc_renderer.SetVolumeKeys(np.ascontiguousarray(np.stack(sequence)))
             times = animate_times(n_views, nrc_renderer.VolumeKeyCount(), args.time_scale)
-        images = nrc_renderer.RenderPath(views, args.frames, train=True, out=None if per_view else False, times=times)
+        # (--aov: every view's AOV, of its camera and its in-between medium, lands beside its image; the frames are the same frames)
+        aovs = torch.empty((n_views, H, lw, 4), device="cuda", dtype=torch.float32) if per_view and args.aov else None
+        images = nrc_renderer.RenderPath(views, args.frames, train=True, out=None if per_view else False, times=times, aov_out=aovs)
         loss = nrc.GetLoss(wait=True)
         failed = (math.isnan(loss) or math.isinf(loss)) and not args.skip_nonfinite      # (the all-reduced loss: the same on every rank)
         if failed:
@@ -266,8 +288,12 @@ def main(argv=None):
             print("orbit: %d views x %d frames, loss %.5f" % (n_views, args.frames, loss))
         if per_view and not failed:
             host = images.cpu().numpy()
-            for path, img in zip(export_paths(args.export, n_views), host):
-                io_exr.write_exr(path, img)
+            host_aov = aovs.cpu().numpy() if aovs is not None else None
+            for i, (path, img) in enumerate(zip(export_paths(args.export, n_views), host)):
+                if host_aov is not None:
+                    io_exr.write_exr_channels(path, aov_planes(img, host_aov[i]))
+                else:
+                    io_exr.write_exr(path, img)
     for frame in range(0 if n_views else args.frames):
         if seq_dev and frame > 0 and frame % args.frames_per_volume == 0:
             nrc_renderer.SetVolume(seq_dev[(frame // args.frames_per_volume) % len(seq_dev)])
@@ -303,7 +329,10 @@ def main(argv=None):
     if args.skip_nonfinite and rank == 0:
         print("skipped %d of %d steps" % (nrc.GetSkippedSteps()[0], nrc.GetStep()))
     if args.export and not failed and not (n_views and "%" in args.export):
-        nrc_renderer.ExportOutputImageToFile(None, args.export)      # sharded: collective, rank 0 writes the whole frame
+        if args.aov:
+            nrc_renderer.ExportImageWithAovToFile(args.export)
+        else:
+            nrc_renderer.ExportOutputImageToFile(None, args.export)      # sharded: collective, rank 0 writes the whole frame
     nrc_renderer.Destroy()
     if ref is not None:
         eval_renderer.Destroy()

@@ -19,6 +19,7 @@
 #include <string>
 
 #include "nrc_math.h"
+#include "nrc_view_aov.hpp"
 #include "nrc_volume_keys.hpp"
 
 // waves per SIMD the camera kernels are register-allocated for
@@ -1031,6 +1032,45 @@ __device__ __forceinline__ void out_store(float4* p, float4 v)
 __device__ __forceinline__ void out_store(float* p, float v)
 {
     *p = v;
+}
+
+// ------------------------------------------------------------------------------------------------ the view AOV (nrc_view_aov.hpp)
+// {alpha, tau, z_front, z_half} of every pixel's camera ray: exact for the piecewise-constant medium, no random numbers.  One wave per
+// 8x8 tile and one lane per pixel, as in k_gen_rays, in the default tile order.  A tile the view's mask rejects stores the empty result
+// and is gone before the occupancy table is copied (no ray of such a tile comes within a voxel of a non-empty one: what a walk would
+// return).  The other lanes run the header's two-level walk: empty coarse cells are left in one jump against the occupancy bits in LDS,
+// voxels of occupied cells are fetched through the raw buffer (an offset beyond the volume reads 0 without a memory access) -- the
+// byte's load is issued before the step's plane parameters are formed and used behind them.  Lanes of a tile cross nearly the same
+// cells, so the jump / step branches diverge at the silhouette only.
+struct AovDensity {
+    __amdgpu_buffer_rsrc_t vol;
+    uint32_t nx, ny;
+    __device__ __forceinline__ uint32_t operator()(uint32_t ix, uint32_t iy, uint32_t iz) const
+    {
+        return __builtin_amdgcn_raw_buffer_load_b8(vol, (int)((iz * ny + iy) * nx + ix), 0, 0);
+    }
+};
+__global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK) void k_view_aov(DevScene sc, DevCamera cam, DevFrame fr, float4* __restrict__ out)
+{
+    camera_wave_priority(fr);
+    __shared__ uint32_t s_occ[kOccMaxWords];
+    uint32_t lx = 0, y = 0;
+    const bool inside = pixel_of_wave_tile(fr, &lx, &y);
+    if (__ballot(inside) == 0ull) return;      // a padding workgroup's wave
+    const size_t pix = (size_t)y * fr.w + lx;
+    if (tile_mask_clear(fr, lx, y)) {
+        if (inside) out[pix] = make_float4(0.0f, 0.0f, NRC_AOV_INF, NRC_AOV_INF);
+        return;
+    }
+    const uint32_t* occ = load_occupancy_per_wave(sc, s_occ);
+    if (!inside) return;
+    const uint32_t gx = global_x(fr, lx);
+    const float u = (float)gx * fr.inv_gw, v = (float)y * fr.inv_gh;      // k_gen_rays' u, v
+    const AovRay ray = view_aov_camera_ray(cam.m, cam.pos, u, v);
+    const AovGrid g{sc.nx, sc.ny, sc.nz, {sc.size[0], sc.size[1], sc.size[2]}, sc.density_factor, sc.occ_shift, sc.occ_gx, sc.occ_gy};
+    const AovDensity den{__builtin_amdgcn_make_buffer_rsrc((void*)sc.density, 0, (int)(sc.nx * sc.ny * sc.nz), 0x00020000), sc.nx, sc.ny};
+    const ViewAov r = occ != nullptr ? view_aov_walk(g, ray, den, AovOccupancyBits{occ}) : view_aov_walk(g, ray, den, NoOccupancy{});
+    out[pix] = make_float4(r.alpha, r.tau, r.z_front, r.z_half);
 }
 
 // ------------------------------------------------------------------------------------------------ nrc/gen_rays.comp + prep_infer_rays.comp
@@ -2334,6 +2374,17 @@ void launch_gen_rays(const DevScene& sc, const DevCamera& cam, const DevFrame& f
     launch_last(kernel, grid, dim3(64 * CAMERA_WAVES_PER_BLOCK), 0u, s, sc, cam, fa,
                 primary_ray_length, primary_ray_prob, (float4*)primary, info, (float4*)origin, (float4*)dir, infer_in,
                 fetch_counter, tg, full_vertex_images ? 1 : 0);
+    NRC_HIP(hipGetLastError());
+}
+
+void launch_view_aov(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, float* out, hipStream_t s)
+{
+    DevFrame fa = fr;      // the view's geometry and mask; the default tile order, no hot tiles, no cost samples
+    fa.tile_order = nullptr;
+    fa.tile_cost = nullptr;
+    fa.hot_front = fa.hot_n = 0u;
+    fa.raise_priority = (g_host_raise_wave_priority != 0 && fr.camera_priority_low == 0u) ? 1u : 0u;
+    hipLaunchKernelGGL(k_view_aov, wave_tile_grid(fr.w, fr.h), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc, cam, fa, (float4*)out);
     NRC_HIP(hipGetLastError());
 }
 

@@ -175,6 +175,10 @@ void launch_tile_order(const uint32_t* cost, uint32_t n_slots, uint32_t* order, 
 void launch_mc_render(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, uint32_t path_length,
                       float blend_factor, float* out_rgba, float* info, unsigned long long* fetch_counter, hipStream_t s);
 
+// the view AOV (nrc_view_aov.hpp): out [h][w][4] = {alpha, tau, z_front, z_half} of every pixel's camera ray through the scene's active
+// volume; fr carries the view's geometry and, when it has one, the empty-space tile mask of the SAME camera and medium.  One launch.
+void launch_view_aov(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, float* out, hipStream_t s);
+
 // ring: {uint head, uint tail, RayInfo[ring_size]}; scratch: uint32[2*T + 4]
 // start == nullptr: the whole of prep_train_rays.comp (scan, pop / trace / write, ring push).  start != nullptr (long train paths, the split
 // frame graph): scan, the rays' start vertices -> start ([T][6] floats) + the training inputs, ring push; launch_train_trace does the rest

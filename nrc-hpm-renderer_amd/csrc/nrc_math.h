@@ -157,6 +157,41 @@ NRC_HD static inline float nrc_atan2f(float y, float x)
     return a;
 }
 
+/* 1 - exp(-x) = -expm1(-x) for x >= 0 (the opacity of optical depth x, nrc_view_aov.hpp); 0 for x <= 0 or NaN.
+ * Spec: n = trunc(fma(x, 1/ln2, 0.5)); r = fma(-n, LN2_LO, fma(-n, LN2_HI, x)) (Cody-Waite: n * LN2_HI is exact for n < 2^12), so
+ * |r| <= ln2/2 (+ an ulp) and exp(-x) = 2^-n exp(-r).  With s = -r: p = expm1(s) = s + s^2 q(s), q the degree-6 Taylor polynomial of
+ * (expm1(s) - s) / s^2 (1/2 ... 1/8!; the next term is s^9/9! <= 6e-10 s), and
+ *   n == 0:  1 - exp(-x) = -p                        (x < ln2/2: no cancellation, the result keeps p's relative error)
+ *   n >= 1:  1 - exp(-x) = fma(-2^-n, p, 1 - 2^-n)   (1 - 2^-n is exact for n <= 24; the result is >= 0.29)
+ *   x >= NRC_EXPM1_ONE: 1 (exp(-x) < 2^-25).
+ * Branch points: 0, (n + 1/2) ln2 for n = 0 .. 24, NRC_EXPM1_ONE.  0.88 ulp from the fp64 value at worst over the sweep of
+ * tests/test_view_aov_cpu.py (2^22 arguments and both sides of every branch point; its bound is 4 ulp). */
+#define NRC_EXPM1_ONE 17.5f
+#define NRC_INV_LN2 0x1.715476p+0f
+#define NRC_LN2_HI 0x1.630000p-1f /* 0.693359375 */
+#define NRC_LN2_LO -2.12194440e-4f /* ln2 - NRC_LN2_HI */
+NRC_HD static inline float nrc_expm1_negf(float x)
+{
+    if (!(x > 0.0f)) return 0.0f;
+    if (x >= NRC_EXPM1_ONE) return 1.0f;
+    const int n = (int)nrc_fmaf_(x, NRC_INV_LN2, 0.5f);
+    const float fn = (float)n;
+    float r = nrc_fmaf_(-fn, NRC_LN2_HI, x);
+    r = nrc_fmaf_(-fn, NRC_LN2_LO, r);
+    const float s = -r;
+    float q = 2.4801587e-5f;              /* 1/40320 */
+    q = nrc_fmaf_(q, s, 1.9841270e-4f);   /* 1/5040 */
+    q = nrc_fmaf_(q, s, 1.3888889e-3f);   /* 1/720 */
+    q = nrc_fmaf_(q, s, 8.3333333e-3f);   /* 1/120 */
+    q = nrc_fmaf_(q, s, 4.1666667e-2f);   /* 1/24 */
+    q = nrc_fmaf_(q, s, 1.6666667e-1f);   /* 1/6 */
+    q = nrc_fmaf_(q, s, 0.5f);
+    const float p = nrc_fmaf_(s * q, s, s);
+    if (n == 0) return -p;
+    const float scale = nrc_u2f((uint32_t)(127 - n) << 23);      /* 2^-n, 1 <= n <= 25 */
+    return nrc_fmaf_(-scale, p, 1.0f - scale);
+}
+
 /* IEEE binary16 <-> binary32, round-to-nearest-even (what a plain float->half cast does) */
 NRC_HD static inline uint16_t nrc_f32_to_f16(float f)
 {

@@ -20,6 +20,17 @@
 namespace nrc {
 
 // ---------------------------------------------------------------------------------------------------- scene upload
+// the world size of a scene's box: the caller's, or for an all-zero size the reference's default
+inline void scene_world_size(const nrc_scene& s, float size[3])
+{
+    for (int k = 0; k < 3; k++) size[k] = s.size[k];
+    if (size[0] == 0.0f && size[1] == 0.0f && size[2] == 0.0f) {
+        // volumeSizeF = normalize(extent) * 107.5 (src/NrcHpmRenderer.cu:910-912)
+        const float fnx = (float)s.nx, fny = (float)s.ny, fnz = (float)s.nz;
+        const float l = sqrtf((fnx * fnx + fny * fny) + fnz * fnz);
+        size[0] = fnx / l * 107.5f; size[1] = fny / l * 107.5f; size[2] = fnz / l * 107.5f;
+    }
+}
 struct SceneDev {
     DevScene d{};
     DevBuf<uint8_t> d_density;
@@ -63,12 +74,8 @@ struct SceneDev {
         d.density = d_density;
         d.nx = s.nx; d.ny = s.ny; d.nz = s.nz;
         d.fnx = (float)s.nx; d.fny = (float)s.ny; d.fnz = (float)s.nz;
-        float size[3] = {s.size[0], s.size[1], s.size[2]};
-        if (size[0] == 0.0f && size[1] == 0.0f && size[2] == 0.0f) {
-            // volumeSizeF = normalize(extent) * 107.5 (src/NrcHpmRenderer.cu:910-912)
-            const float l = sqrtf((d.fnx * d.fnx + d.fny * d.fny) + d.fnz * d.fnz);
-            size[0] = d.fnx / l * 107.5f; size[1] = d.fny / l * 107.5f; size[2] = d.fnz / l * 107.5f;
-        }
+        float size[3];
+        scene_world_size(s, size);
         for (int k = 0; k < 3; k++) {
             d.size[k] = size[k];
             d.half_size[k] = size[k] * 0.5f;

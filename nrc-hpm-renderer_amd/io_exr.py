@@ -131,3 +131,97 @@ def write_exr(path, img, compression="zip"):
         off += len(ck)
     with open(path, "wb") as f:
         f.write(hdr + table + b"".join(chunks))
+
+
+def read_exr_channels(path):
+    """Every FLOAT channel of a scan-line EXR as {name: float32 [H][W]} (ExportImageWithAovToFile: A, B, G, R, Z, Zhalf, tau)."""
+    with open(path, "rb") as f:
+        d = f.read()
+    assert struct.unpack("<I", d[:4])[0] == 20000630, "not an EXR file"
+    p = 8
+    attrs = {}
+    while d[p] != 0:
+        e = d.index(b"\0", p)
+        name = d[p:e].decode()
+        p = e + 1
+        e = d.index(b"\0", p)
+        p = e + 1
+        size = struct.unpack("<i", d[p:p + 4])[0]
+        p += 4
+        attrs[name] = d[p:p + size]
+        p += size
+    p += 1
+    chans = []
+    cb = attrs["channels"]
+    q = 0
+    while cb[q] != 0:
+        e = cb.index(b"\0", q)
+        chans.append(cb[q:e].decode())
+        q = e + 1
+        assert struct.unpack("<i", cb[q:q + 4])[0] == 2, "only FLOAT channels supported"
+        q += 16
+    comp = attrs["compression"][0]
+    xmin, ymin, xmax, ymax = struct.unpack("<4i", attrs["dataWindow"])
+    W, H = xmax - xmin + 1, ymax - ymin + 1
+    lines = {0: 1, 2: 1, 3: 16}[comp]
+    n_chunks = (H + lines - 1) // lines
+    offs = struct.unpack("<%dQ" % n_chunks, d[p:p + 8 * n_chunks])
+    planes = {cn: np.zeros((H, W), np.float32) for cn in chans}
+    for o in offs:
+        y, size = struct.unpack("<ii", d[o:o + 8])
+        payload = d[o + 8:o + 8 + size]
+        nl = min(lines, ymax + 1 - y)
+        raw_size = nl * W * 4 * len(chans)
+        raw = payload if (comp == 0 or size == raw_size) else _unpredict(zlib.decompress(payload))
+        a = np.frombuffer(raw, "<f4").reshape(nl, len(chans), W)
+        for ci, cn in enumerate(chans):
+            planes[cn][y - ymin:y - ymin + nl] = a[:, ci, :]
+    return planes
+
+
+def write_exr_channels(path, planes, compression="zip"):
+    """Write {name: float32 [H][W]} as a scan-line EXR with one FLOAT channel per name (stored in the format's alphabetical order)."""
+    names = sorted(planes)
+    assert names, "no channels"
+    arr = [np.ascontiguousarray(planes[n], np.float32) for n in names]
+    H, W = arr[0].shape
+    assert all(a.shape == (H, W) for a in arr), "channels differ in shape"
+    comp = {"none": 0, "zip": 3}[compression]
+    lines = 16 if comp == 3 else 1
+
+    def attr(name, typ, payload):
+        return name.encode() + b"\0" + typ.encode() + b"\0" + struct.pack("<i", len(payload)) + payload
+
+    ch = b""
+    for cn in names:
+        ch += cn.encode() + b"\0" + struct.pack("<iBBBBii", 2, 0, 0, 0, 0, 1, 1)
+    ch += b"\0"
+    box = struct.pack("<4i", 0, 0, W - 1, H - 1)
+    hdr = struct.pack("<II", 20000630, 2)
+    hdr += attr("channels", "chlist", ch)
+    hdr += attr("compression", "compression", bytes([comp]))
+    hdr += attr("dataWindow", "box2i", box)
+    hdr += attr("displayWindow", "box2i", box)
+    hdr += attr("lineOrder", "lineOrder", b"\0")
+    hdr += attr("pixelAspectRatio", "float", struct.pack("<f", 1.0))
+    hdr += attr("screenWindowCenter", "v2f", struct.pack("<2f", 0.0, 0.0))
+    hdr += attr("screenWindowWidth", "float", struct.pack("<f", 1.0))
+    hdr += b"\0"
+    stack = np.stack(arr, axis=1)      # [line][chan][x]
+    n_chunks = (H + lines - 1) // lines
+    chunks = []
+    for c in range(n_chunks):
+        y0 = c * lines
+        raw = np.ascontiguousarray(stack[y0:y0 + lines], "<f4").tobytes()
+        payload = raw
+        if comp == 3:
+            z = zlib.compress(_predict(raw))
+            payload = z if len(z) < len(raw) else raw
+        chunks.append(struct.pack("<ii", y0, len(payload)) + payload)
+    off = len(hdr) + 8 * n_chunks
+    table = b""
+    for ck in chunks:
+        table += struct.pack("<Q", off)
+        off += len(ck)
+    with open(path, "wb") as f:
+        f.write(hdr + table + b"".join(chunks))
