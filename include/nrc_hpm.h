@@ -689,6 +689,61 @@ int nrc_mc_renderer_set_path_aov_target(nrc_mc_renderer_t* r, float* d_aovs, uin
 int nrc_mc_renderer_export_exr_aov(nrc_mc_renderer_t* r, const char* path);
 int nrc_test_view_aov_host(const nrc_scene* scene, const nrc_camera* camera, uint32_t w, uint32_t h, const nrc_tile* tile, float* host_out);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Ray AOV: the view AOV's four numbers {alpha, tau, z_front, z_half} along ray segments the caller supplies -- a holdout (the medium in
+ * front of an object: the camera ray up to the object's depth), the medium's shadow (the directional light's rays: a shadow map), or any
+ * list of segments.  Same medium, same exact walk, same arithmetic (csrc/nrc_view_aov.hpp, view_aov_walk_range); both renderers.
+ *   Record.  A ray is 8 floats {ox, oy, oz, t_min, dx, dy, dz, t_max}; its result is 4 floats.
+ *   Range.   The result covers the part of the ray o + t d with t in [max(t_min, 0), t_max].  d is used as given: t is the ray parameter and
+ *            the optical depth is integrated against it.  With |d| = 1, t is distance, tau the optical depth the renderers mean and
+ *            z_front, z_half distances from o; the Python helpers (scene.light_view, api.camera_rays) hand out unit directions.
+ *   Start.   The walk begins at t0 = max(box entry, t_min, 0) + 0, in the state of the view AOV's rule: every voxel plane with t <= t0 is
+ *            behind the ray.  When t0 falls inside a non-empty voxel, z_front is exactly t0.
+ *   End.     The walk ends at min(box exit, t_max).  A voxel's segment [ta, tb] counts as [ta, fminf(tb, t_max)]; the walk is done after
+ *            the first trip whose far plane is at or beyond t_max, and the jump out of an empty occupancy cell is such a trip.  A segment
+ *            of length 0 adds nothing.
+ *   Bits.    With t_min <= 0 and t_max = +inf the result is bit for bit the whole ray's (nrc_renderer_view_aov's for a camera ray).  A
+ *            ray cut at t_max = T keeps the whole ray's z_front and, wherever the cut result has a finite z_half, the whole ray's z_half
+ *            (formed against the voxel's own far plane, so it may lie beyond T by the rounding of one quotient); tau accumulates
+ *            identically up to the cut segment.  The plain voxel walk and the walk that jumps out of empty cells agree in every bit for
+ *            every range, and so do the kernel and the host.
+ *   Empty.   {0, 0, +inf, +inf} for t_max <= max(t_min, 0), a NaN in any of the eight numbers, a zero or non-finite direction, a
+ *            non-finite origin, and a range that holds no medium.  The result never contains a NaN.
+ * Every call below enqueues ONE launch on the stream given at creation, behind the volume rebuilds enqueued so far (set_volume,
+ * set_volume_bricks, set_volume_time) and, for the view's depths, behind the view's tile mask when one is due -- where
+ * nrc_renderer_view_aov puts its own.  No host wait; results are not kept (the caller's buffers may change between two calls); a renderer
+ * on which none of them is made allocates and launches nothing for them.  d_rays and d_out are device memory, 16-byte aligned.
+ * nrc_renderer_ray_aov: ray i of d_rays [n][8] -> d_out [n][4].  Rays are independent: a permuted list gives the permuted results.
+ *   n == 0 is a no-op; a NULL pointer with n > 0 returns NRC_ERR_INVALID.
+ * nrc_renderer_view_aov_to_depth: every pixel's camera ray (the view AOV's) with t_min = 0 and t_max = d_depth[pixel]; d_depth [h][w]
+ *   fp32, distance along the pixel's ray -- the unit of z_front --, d_out [h][w][4]; a sharded renderer's local columns.  A depth of +inf
+ *   gives nrc_renderer_view_aov's bits, a depth <= 0 or NaN the empty result.  A tile the view's mask rejects is empty whatever its depths.
+ * nrc_renderer_ortho_aov: an orthographic image of w x h pixels, its size independent of the renderer's: pixel (i, j) is the whole ray
+ *   from origin + su du + sv dv, su = (i + 1/2) / w, sv = (j + 1/2) / h, along dir; d_out [h][w][4].
+ * nrc_renderer_set_path_aov_depths: with an AOV target set (nrc_renderer_set_path_aov_target), the next render_path call holds view i's
+ *   AOV out to d_depths + i * h * w (device memory, n_views * h * w floats).  Consumed by that call like the target, and dropped with it;
+ *   NULL cancels; depths without a target, or for another number of views, fail the path call with NRC_ERR_INVALID.  Frames, d_frames and
+ *   training state are bit for bit what they are without it.
+ * nrc_camera_rays / nrc_ortho_rays (host memory, no renderer, no device): the records {o, 0, d, +inf} of the rays the two image-shaped
+ *   calls walk, [h][w][8] -- the camera's for a renderer of w x h pixels (tile: as for nrc_renderer_create_tiled, or NULL).  The
+ *   image-shaped calls ARE nrc_renderer_ray_aov on these records, with t_max replaced by the depth; callers who build their own segment
+ *   lists (several depth layers per pixel) start from them.
+ * nrc_test_ray_aov_host (test hook): the list call on the CPU inside the library, by the header's plain voxel walk; host memory. */
+typedef struct nrc_ortho_view {
+    float origin[3], du[3], dv[3], dir[3];
+} nrc_ortho_view;
+int nrc_renderer_ray_aov(nrc_renderer_t* r, size_t n, const float* d_rays, float* d_out);
+int nrc_renderer_view_aov_to_depth(nrc_renderer_t* r, const float* d_depth, float* d_out);
+int nrc_renderer_ortho_aov(nrc_renderer_t* r, const nrc_ortho_view* view, uint32_t w, uint32_t h, float* d_out);
+int nrc_renderer_set_path_aov_depths(nrc_renderer_t* r, const float* d_depths, uint32_t n_views);
+int nrc_mc_renderer_ray_aov(nrc_mc_renderer_t* r, size_t n, const float* d_rays, float* d_out);
+int nrc_mc_renderer_view_aov_to_depth(nrc_mc_renderer_t* r, const float* d_depth, float* d_out);
+int nrc_mc_renderer_ortho_aov(nrc_mc_renderer_t* r, const nrc_ortho_view* view, uint32_t w, uint32_t h, float* d_out);
+int nrc_mc_renderer_set_path_aov_depths(nrc_mc_renderer_t* r, const float* d_depths, uint32_t n_views);
+int nrc_camera_rays(const nrc_camera* camera, uint32_t w, uint32_t h, const nrc_tile* tile, float* host_rays);
+int nrc_ortho_rays(const nrc_ortho_view* view, uint32_t w, uint32_t h, float* host_rays);
+int nrc_test_ray_aov_host(const nrc_scene* scene, size_t n, const float* host_rays, float* host_out);
+
 /* THE environment switch of the library: NRC_DEBUG="name[=value],..." -- diagnostic and test switches only, none changes a result
  * (the list and what each does: csrc/nrc_common.hpp, debug_switch).
  * diagnostics (read when the library first allocates): NRC_DEBUG=poison_alloc fills every device allocation with 0xFF

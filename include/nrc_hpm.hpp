@@ -286,6 +286,19 @@ private:
 inline int LoadScheduleCache(const std::string& path) { int n = 0; nrc_check(nrc_schedule_cache_load(path.c_str(), &n)); return n; }
 inline int SaveScheduleCache(const std::string& path) { int n = 0; nrc_check(nrc_schedule_cache_save(path.c_str(), &n)); return n; }
 inline void ClearScheduleCache() { nrc_check(nrc_schedule_cache_clear()); }
+// the ray records {o, 0, d, +inf} [h][w][8] the image-shaped ray AOV calls walk (include/nrc_hpm.h, "Ray AOV"): host only, no renderer
+inline std::vector<float> CameraRays(const nrc_camera& camera, uint32_t w, uint32_t h, const nrc_tile* tile = nullptr)
+{
+    std::vector<float> rays((size_t)w * h * 8);
+    nrc_check(nrc_camera_rays(&camera, w, h, tile, rays.data()));
+    return rays;
+}
+inline std::vector<float> OrthoRays(const nrc_ortho_view& view, uint32_t w, uint32_t h)
+{
+    std::vector<float> rays((size_t)w * h * 8);
+    nrc_check(nrc_ortho_rays(&view, w, h, rays.data()));
+    return rays;
+}
 
 class NeuralRadianceCache {
 public:
@@ -473,6 +486,14 @@ public:
     }
     // the next RenderPath with nViews cameras writes view i's AOV to dAovs + i * height * width * 4 (device; nullptr cancels)
     void SetPathAovTarget(float* dAovs, uint32_t nViews) { nrc_check(nrc_renderer_set_path_aov_target(h_, dAovs, nViews)); }
+    // The ray AOV (include/nrc_hpm.h, "Ray AOV"): the same four numbers along caller-supplied ray segments through the current medium; one
+    // launch each on the renderer's stream, no host wait, device memory.  RayAov: n records {o, t_min, d, t_max} -> n results.
+    // ViewAovToDepth: every pixel's camera ray up to dDepth [height][width] (a holdout).  OrthoAov: an orthographic view of w x h pixels (the
+    // medium's shadow map).  SetPathAovDepths: with SetPathAovTarget, the next RenderPath holds view i's AOV out to dDepths + i * height * width.
+    void RayAov(size_t n, const float* dRays, float* dOut) const { nrc_check(nrc_renderer_ray_aov(h_, n, dRays, dOut)); }
+    void ViewAovToDepth(const float* dDepth, float* dOut) const { nrc_check(nrc_renderer_view_aov_to_depth(h_, dDepth, dOut)); }
+    void OrthoAov(const nrc_ortho_view& view, uint32_t w, uint32_t h, float* dOut) const { nrc_check(nrc_renderer_ortho_aov(h_, &view, w, h, dOut)); }
+    void SetPathAovDepths(const float* dDepths, uint32_t nViews) { nrc_check(nrc_renderer_set_path_aov_depths(h_, dDepths, nViews)); }
     // ExportOutputImageToFile with the AOV beside the colours: FLOAT channels A (= alpha), B, G, R, Z (= z_front), Zhalf, tau; this renderer's pixels
     void ExportOutputImageWithAovToFile(void* /*queue*/, const std::string& filePath) const { nrc_check(nrc_renderer_export_exr_aov(h_, filePath.c_str())); }
     // diagnostics: the empty-space tile mask in use (synchronises; empty: the frame uses none) -- nrc_renderer_tile_mask
@@ -569,6 +590,11 @@ public:
         return p;
     }
     void SetPathAovTarget(float* dAovs, uint32_t nViews) { nrc_check(nrc_mc_renderer_set_path_aov_target(h_, dAovs, nViews)); }
+    // see NrcHpmRenderer::RayAov / ViewAovToDepth / OrthoAov / SetPathAovDepths
+    void RayAov(size_t n, const float* dRays, float* dOut) const { nrc_check(nrc_mc_renderer_ray_aov(h_, n, dRays, dOut)); }
+    void ViewAovToDepth(const float* dDepth, float* dOut) const { nrc_check(nrc_mc_renderer_view_aov_to_depth(h_, dDepth, dOut)); }
+    void OrthoAov(const nrc_ortho_view& view, uint32_t w, uint32_t h, float* dOut) const { nrc_check(nrc_mc_renderer_ortho_aov(h_, &view, w, h, dOut)); }
+    void SetPathAovDepths(const float* dDepths, uint32_t nViews) { nrc_check(nrc_mc_renderer_set_path_aov_depths(h_, dDepths, nViews)); }
     void ExportOutputImageWithAovToFile(void* /*queue*/, const std::string& filePath) const { nrc_check(nrc_mc_renderer_export_exr_aov(h_, filePath.c_str())); }
     std::vector<uint32_t> TileMask() const
     {

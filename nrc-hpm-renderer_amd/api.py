@@ -93,6 +93,9 @@ ABI_SYMBOLS = [
     "nrc_renderer_render_path", "nrc_mc_renderer_render_path", "nrc_renderer_tile_mask", "nrc_mc_renderer_tile_mask",
     "nrc_renderer_view_aov", "nrc_mc_renderer_view_aov", "nrc_renderer_set_path_aov_target", "nrc_mc_renderer_set_path_aov_target",
     "nrc_renderer_export_exr_aov", "nrc_mc_renderer_export_exr_aov", "nrc_test_view_aov_host",
+    "nrc_renderer_ray_aov", "nrc_mc_renderer_ray_aov", "nrc_renderer_view_aov_to_depth", "nrc_mc_renderer_view_aov_to_depth",
+    "nrc_renderer_ortho_aov", "nrc_mc_renderer_ortho_aov", "nrc_renderer_set_path_aov_depths", "nrc_mc_renderer_set_path_aov_depths",
+    "nrc_camera_rays", "nrc_ortho_rays", "nrc_test_ray_aov_host",
     "nrc_renderer_set_show_nrc", "nrc_renderer_set_frame_random", "nrc_renderer_framebuffer", "nrc_renderer_framebuffer_on",
     "nrc_renderer_export_exr",
     "nrc_renderer_frame_time_ms", "nrc_renderer_stage_stats", "nrc_renderer_frame_timeline", "nrc_set_wave_priority_raise", "nrc_renderer_destroy", "nrc_renderer_buffer", "nrc_renderer_count_fetches",
@@ -196,6 +199,18 @@ def load_library():
         for name in ("nrc_renderer_export_exr_aov", "nrc_mc_renderer_export_exr_aov"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_char_p]
         L.nrc_test_view_aov_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    if hasattr(L, "nrc_renderer_ray_aov"):      # (an older build loaded through NRC_HPM_LIB has no ray AOV)
+        for name in ("nrc_renderer_ray_aov", "nrc_mc_renderer_ray_aov"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        for name in ("nrc_renderer_view_aov_to_depth", "nrc_mc_renderer_view_aov_to_depth"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ("nrc_renderer_ortho_aov", "nrc_mc_renderer_ortho_aov"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        for name in ("nrc_renderer_set_path_aov_depths", "nrc_mc_renderer_set_path_aov_depths"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.nrc_camera_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.nrc_ortho_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.nrc_test_ray_aov_host.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.nrc_mc_renderer_frame_time_ms.restype = C.c_float
     for name in ("nrc_cache_get_loss", "nrc_cache_get_loss_blocking", "nrc_renderer_is_blending", "nrc_mc_renderer_is_blending",
                  "nrc_cache_get_infer_batch_count", "nrc_cache_get_train_batch_count",
@@ -421,14 +436,47 @@ def _render_path(call, width, height, cameras, framesPerCamera, frameRandoms, ou
     return None if out is False else out
 
 
+def _check_device_floats(what, t, shape):
+    """a contiguous float32 CUDA tensor of `shape`, as RenderPath checks aov_out"""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (what, tuple(shape)))
+    return t
+
+
+def _aov_out(what, out, shape):
+    """`out` checked, or a new tensor of `shape`"""
+    import torch
+    if out is None:
+        return torch.empty(tuple(shape), device="cuda", dtype=torch.float32)
+    return _check_device_floats(what + ": out", out, shape)
+
+
+class NrcOrthoView(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3), ("dir", C.c_float * 3)]
+
+
+def make_c_ortho_view(view):
+    """nrc_ortho_view of a dict {origin, du, dv, dir} (scene.light_view)"""
+    v = NrcOrthoView()
+    for k in ("origin", "du", "dv", "dir"):
+        a = np.asarray(view[k], np.float32).reshape(-1)
+        if a.size != 3:
+            raise ValueError("ortho view: %s must hold 3 numbers" % k)
+        getattr(v, k)[:] = [float(x) for x in a]
+    return v
+
+
 def _times_keyword(plain):
-    """RenderPath(..., times=None, aov_out=None) of both renderers.  The keywords ride on the untimed method: its positional signature is
+    """RenderPath(..., times=None, aov_out=None, aov_depths=None) of both renderers.  The keywords ride on the untimed method: its positional signature is
     a published one (callers and tests/test_camera_path_host.py name its parameters in order) and stays what inspect.signature reports; a
     call without times is `plain`'s own, a call with times goes to the renderer's _path with the same arguments.
     aov_out: a contiguous float32 CUDA tensor [len(cameras)][height][width][4] that receives every view's AOV ({alpha, tau, z_front,
-    z_half} of that view's camera and medium: ViewAov, nrc_renderer_set_path_aov_target); frames, `out` and training are unchanged by it."""
+    z_half} of that view's camera and medium: ViewAov, nrc_renderer_set_path_aov_target); frames, `out` and training are unchanged by it.
+    aov_depths (with aov_out): a contiguous float32 CUDA tensor [len(cameras)][height][width]; view i's AOV is held out to aov_depths[i]
+    (ViewAovToDepth, nrc_renderer_set_path_aov_depths)."""
     @functools.wraps(plain)
-    def RenderPath(self, *args, times=None, aov_out=None, **kw):
+    def RenderPath(self, *args, times=None, aov_out=None, aov_depths=None, **kw):
         bound = inspect.signature(plain).bind(self, *args, **kw)
         bound.apply_defaults()
         if aov_out is not None:
@@ -438,6 +486,15 @@ def _times_keyword(plain):
                     or tuple(aov_out.shape) != shape or not aov_out.is_contiguous():
                 raise ValueError("RenderPath: aov_out must be a contiguous float32 CUDA tensor of shape %s" % (shape,))
             self.SetPathAovTarget(aov_out)
+        if aov_depths is not None:
+            if aov_out is None:
+                raise ValueError("RenderPath: aov_depths needs aov_out")
+            try:
+                _check_device_floats("RenderPath: aov_depths", aov_depths, shape[:3])
+            except ValueError:
+                self.SetPathAovTarget(None)
+                raise
+            self.SetPathAovDepths(aov_depths)
         try:
             if times is None:
                 return plain(self, *args, **kw)
@@ -445,6 +502,8 @@ def _times_keyword(plain):
         finally:
             if aov_out is not None:      # (consumed by the path call; a call that failed before it reached the library leaves none behind)
                 self.SetPathAovTarget(None)
+            if aov_depths is not None:
+                self.SetPathAovDepths(None)
     return RenderPath
 
 
@@ -485,6 +544,46 @@ class _LiveMedium:
             _check(self._medium("set_path_aov_target")(self.h, None, C.c_uint32(0)))
         else:
             _check(self._medium("set_path_aov_target")(self.h, _dev_ptr(aovs), C.c_uint32(int(aovs.shape[0]) if views is None else int(views))))
+
+    def SetPathAovDepths(self, depths, views=None):
+        """nrc_renderer_set_path_aov_depths: with an AOV target set, the next RenderPath holds view i's AOV out to depths[i] (a contiguous
+        float32 CUDA tensor [views][height][width]; None cancels).  RenderPath(..., aov_out=, aov_depths=) makes this call itself."""
+        if depths is None:
+            _check(self._medium("set_path_aov_depths")(self.h, None, C.c_uint32(0)))
+        else:
+            _check(self._medium("set_path_aov_depths")(self.h, _dev_ptr(depths), C.c_uint32(int(depths.shape[0]) if views is None else int(views))))
+
+    def RayAov(self, rays, out=None):
+        """the ray AOV of a list of segments through the current medium (include/nrc_hpm.h, "Ray AOV"; nrc_renderer_ray_aov): rays is a
+        contiguous float32 CUDA tensor [n][8] of {ox, oy, oz, t_min, dx, dy, dz, t_max}, the result [n][4] of {alpha, tau, z_front, z_half}
+        (`out`, or a new tensor).  One launch on the renderer's stream, no host wait."""
+        import torch
+        if not isinstance(rays, torch.Tensor) or rays.dim() != 2:
+            raise ValueError("RayAov: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
+        _check_device_floats("RayAov: rays", rays, (rays.shape[0], 8))
+        out = _aov_out("RayAov", out, (rays.shape[0], 4))
+        _check(self._medium("ray_aov")(self.h, C.c_size_t(int(rays.shape[0])), _dev_ptr(rays), _dev_ptr(out)))
+        return out
+
+    def ViewAovToDepth(self, depth, out=None):
+        """the view AOV held out to a depth image (nrc_renderer_view_aov_to_depth): depth is a contiguous float32 CUDA tensor
+        [height][width], the distance along each pixel's camera ray (the unit of z_front) at which the ray ends; +inf gives ViewAov()'s
+        bits, a depth <= 0 or NaN the empty result.  Returns [height][width][4] (`out`, or a new tensor)."""
+        _check_device_floats("ViewAovToDepth: depth", depth, (self.height, self.width))
+        out = _aov_out("ViewAovToDepth", out, (self.height, self.width, 4))
+        _check(self._medium("view_aov_to_depth")(self.h, _dev_ptr(depth), _dev_ptr(out)))
+        return out
+
+    def OrthoAov(self, view, w, h, out=None):
+        """the ray AOV of an orthographic view {origin, du, dv, dir} (scene.light_view: the medium's shadow map) of w x h pixels, whatever
+        the renderer's size (nrc_renderer_ortho_aov).  Returns [h][w][4] (`out`, or a new tensor)."""
+        w, h = int(w), int(h)
+        if w <= 0 or h <= 0:
+            raise ValueError("OrthoAov: the image size must be positive")
+        v = make_c_ortho_view(view)
+        out = _aov_out("OrthoAov", out, (h, w, 4))
+        _check(self._medium("ortho_aov")(self.h, C.byref(v), C.c_uint32(w), C.c_uint32(h), _dev_ptr(out)))
+        return out
 
     def ExportImageWithAovToFile(self, filePath):
         """ExportOutputImageToFile with the view AOV beside the colours: a scan-line EXR with FLOAT channels A (alpha of the AOV), B, G, R,
@@ -1245,6 +1344,38 @@ def test_view_aov_host(scene, camera, width, height, tile=None):
     out = np.empty((height, width, 4), np.float32)
     _check(load_library().nrc_test_view_aov_host(C.byref(sc_), C.byref(cam), C.c_uint32(width), C.c_uint32(height),
                                                  C.byref(t) if t is not None else None, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def camera_rays(camera, width, height, tile=None):
+    """nrc_camera_rays: the records {pos, 0, dir, +inf} [height][width][8] (numpy) of the camera rays a renderer of width x height pixels
+    walks for its view AOV (unit directions); tile: the strip of a sharded frame.  Host only: no renderer, no GPU."""
+    cam = make_c_camera(camera)
+    t = NrcTile(*[int(x) for x in tile]) if tile is not None else None
+    out = np.empty((height, width, 8), np.float32)
+    _check(load_library().nrc_camera_rays(C.byref(cam), C.c_uint32(width), C.c_uint32(height), C.byref(t) if t is not None else None,
+                                          out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def ortho_rays(view, width, height):
+    """nrc_ortho_rays: the same records [height][width][8] of an orthographic view {origin, du, dv, dir} (scene.light_view)"""
+    v = make_c_ortho_view(view)
+    out = np.empty((height, width, 8), np.float32)
+    _check(load_library().nrc_ortho_rays(C.byref(v), C.c_uint32(width), C.c_uint32(height), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def test_ray_aov_host(scene, rays):
+    """nrc_test_ray_aov_host: the ray AOV [...][4] (numpy) of the records rays [...][8] through `scene` (scene.make_scene), computed on the
+    CPU inside the library by csrc/nrc_view_aov.hpp's plain range walk"""
+    sc_ = make_c_scene(scene.scene if hasattr(scene, "scene") else scene)
+    r = np.ascontiguousarray(rays, np.float32)
+    if r.ndim < 1 or r.shape[-1] != 8:
+        raise ValueError("test_ray_aov_host: rays must have 8 numbers per record")
+    out = np.empty(r.shape[:-1] + (4,), np.float32)
+    n = r.size // 8
+    _check(load_library().nrc_test_ray_aov_host(C.byref(sc_), C.c_size_t(n), r.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
     return out
 
 

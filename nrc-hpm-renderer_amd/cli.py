@@ -82,6 +82,40 @@ def aov_planes(rgba, aov):
     return {"R": rgba[..., 0], "G": rgba[..., 1], "B": rgba[..., 2], "A": aov[..., 0], "tau": aov[..., 1], "Z": aov[..., 2], "Zhalf": aov[..., 3]}
 
 
+def check_ray_aov_args(args):
+    """what --shadow-map and --holdout-sphere can be combined with (raises SystemExit)"""
+    radius = getattr(args, "holdout_sphere", None)
+    if radius is not None:
+        if not getattr(args, "aov", False):
+            raise SystemExit("SkyRenderer ERROR: --holdout-sphere holds the --aov export out: give --aov (and --export)")
+        if not (math.isfinite(radius) and radius > 0.0):
+            raise SystemExit("SkyRenderer ERROR: --holdout-sphere must be a finite radius above 0")
+    path = getattr(args, "shadow_map", None)
+    if path is not None:
+        if not path:
+            raise SystemExit("SkyRenderer ERROR: --shadow-map needs a file name")
+        if getattr(args, "shadow_size", 1) < 1:
+            raise SystemExit("SkyRenderer ERROR: --shadow-size must be at least 1")
+
+
+def shadow_planes(aov):
+    """the channels of a --shadow-map file from the light view's [h][w][4] ray AOV"""
+    return {"A": aov[..., 0], "tau": aov[..., 1], "Z": aov[..., 2], "Zhalf": aov[..., 3]}
+
+
+def sphere_depth(rays, radius):
+    """--holdout-sphere: the analytic depth image of a sphere of `radius` at the origin along the records rays [...][8] (api.camera_rays:
+    unit directions, so the ray parameter is distance) -- float32 [...], the near root, +inf where the ray passes the sphere or starts inside
+    or behind it"""
+    r = np.asarray(rays, np.float64)
+    o, d = r[..., 0:3], r[..., 4:7]
+    a, b, c = (d * d).sum(-1), (o * d).sum(-1), (o * o).sum(-1) - float(radius) ** 2
+    disc = b * b - a * c
+    with np.errstate(invalid="ignore"):
+        t = (-b - np.sqrt(np.where(disc >= 0.0, disc, np.nan))) / a
+    return np.where(np.isfinite(t) & (t > 0.0), t, np.inf).astype(np.float32)
+
+
 def check_animate_args(args):
     """what --animate needs (raises SystemExit); returns whether the run is an animated fly-through"""
     if not getattr(args, "animate", False):
@@ -131,6 +165,14 @@ def main(argv=None):
                     help="with --export: the files also carry the view AOV (exact opacity and depth per pixel) as FLOAT channels -- A = alpha "
                          "instead of the framebuffer's constant 1, Z = distance to the first non-empty voxel, Zhalf = distance to optical depth "
                          "ln 2, tau = optical depth -- for compositing; one GPU")
+    ap.add_argument("--holdout-sphere", type=float, default=None, metavar="R",
+                    help="with --aov: the AOV is held out to a sphere of radius R at the origin -- the medium in FRONT of the sphere, along each "
+                         "camera ray up to the sphere's depth (include/nrc_hpm.h, nrc_renderer_view_aov_to_depth); pixels beside the sphere keep "
+                         "the whole ray")
+    ap.add_argument("--shadow-map", default=None, metavar="PATH",
+                    help="write the medium's shadow map to this EXR: FLOAT channels A, Z, Zhalf, tau along the directional light's rays "
+                         "(scene.light_view; include/nrc_hpm.h, nrc_renderer_ortho_aov), of the medium the run ends with")
+    ap.add_argument("--shadow-size", type=int, default=1024, metavar="N", help="--shadow-map: the map is N x N pixels")
     ap.add_argument("--orbit", type=int, default=None, metavar="N",
                     help="render an N-view turntable around the volume with one RenderPath call (include/nrc_hpm.h, nrc_renderer_render_path): "
                          "--frames frames per view")
@@ -158,6 +200,7 @@ def main(argv=None):
     animate = check_animate_args(args)
     n_views = check_orbit_args(args)
     check_aov_args(args)
+    check_ray_aov_args(args)
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # start the ranks before anything touches the GPU in this process (a process that has initialised HIP must not spawn them)
@@ -279,7 +322,11 @@ def main(argv=None):
             times = animate_times(n_views, nrc_renderer.VolumeKeyCount(), args.time_scale)
         # (--aov: every view's AOV, of its camera and its in-between medium, lands beside its image; the frames are the same frames)
         aovs = torch.empty((n_views, H, lw, 4), device="cuda", dtype=torch.float32) if per_view and args.aov else None
-        images = nrc_renderer.RenderPath(views, args.frames, train=True, out=None if per_view else False, times=times, aov_out=aovs)
+        depths = None
+        if aovs is not None and args.holdout_sphere is not None:
+            depths = torch.from_numpy(np.stack([sphere_depth(api.camera_rays(v, lw, H), args.holdout_sphere) for v in views])).cuda()
+        images = nrc_renderer.RenderPath(views, args.frames, train=True, out=None if per_view else False, times=times, aov_out=aovs,
+                                         aov_depths=depths)
         loss = nrc.GetLoss(wait=True)
         failed = (math.isnan(loss) or math.isinf(loss)) and not args.skip_nonfinite      # (the all-reduced loss: the same on every rank)
         if failed:
@@ -329,10 +376,18 @@ def main(argv=None):
     if args.skip_nonfinite and rank == 0:
         print("skipped %d of %d steps" % (nrc.GetSkippedSteps()[0], nrc.GetStep()))
     if args.export and not failed and not (n_views and "%" in args.export):
-        if args.aov:
+        if args.aov and args.holdout_sphere is not None:
+            cam = views[-1] if n_views else camera
+            held = nrc_renderer.ViewAovToDepth(torch.from_numpy(sphere_depth(api.camera_rays(cam, lw, H), args.holdout_sphere)).cuda())
+            io_exr.write_exr_channels(args.export, aov_planes(nrc_renderer.GetImage().cpu().numpy(), held.cpu().numpy()))
+        elif args.aov:
             nrc_renderer.ExportImageWithAovToFile(args.export)
         else:
             nrc_renderer.ExportOutputImageToFile(None, args.export)      # sharded: collective, rank 0 writes the whole frame
+    if args.shadow_map and not failed and rank == 0:      # (every rank holds the whole medium: rank 0's map is the map)
+        n = args.shadow_size
+        shadow = nrc_renderer.OrthoAov(sc.light_view(scene, n, n), n, n)
+        io_exr.write_exr_channels(args.shadow_map, shadow_planes(shadow.cpu().numpy()))
     nrc_renderer.Destroy()
     if ref is not None:
         eval_renderer.Destroy()

@@ -1073,6 +1073,115 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK) void k_view_aov(DevSce
     out[pix] = make_float4(r.alpha, r.tau, r.z_front, r.z_half);
 }
 
+// ------------------------------------------------------------------------------------------------ the ray AOV (nrc_view_aov.hpp, view_aov_walk_range)
+// The same of caller-supplied ray segments: one kernel over a ray SOURCE, which says which ray a lane has, its range and where the result
+// goes -- nothing else.  The kernel owns the rest once: the wave priority of the camera kernels, the occupancy copy into LDS (<= 8 KB per
+// workgroup of four waves, as in k_view_aov), the raw-buffer density functor, the choice of the walk for a medium without a table, and
+// the one 16-byte store per ray.  A source has
+//   raise      the launcher's wave-priority switch (DevFrame::raise_priority)
+//   Lane       a lane's own state; lane(&ln): does the lane have a ray (ln.at: its index in out)
+//   rejected   wave-uniform: no ray of the wave can meet the medium, whatever its range -- the wave stores empty results and is gone
+//              before the table is copied
+//   ray        the lane's ray and range
+struct RayListLane { size_t at; };
+// ray i of a list: d_rays[i] = {ox, oy, oz, t_min, dx, dy, dz, t_max}, read as two 16-byte loads; lane i of the grid takes ray i
+struct RayList {
+    const float4* __restrict__ rays;
+    float4* __restrict__ out;
+    size_t n;
+    uint32_t raise;
+    using Lane = RayListLane;
+    __device__ __forceinline__ bool lane(Lane* ln) const
+    {
+        ln->at = (size_t)blockIdx.x * (64u * CAMERA_WAVES_PER_BLOCK) + threadIdx.x;
+        return ln->at < n;
+    }
+    __device__ __forceinline__ bool rejected(const Lane&) const { return false; }
+    __device__ __forceinline__ void ray(const Lane& ln, AovRay* r, float* t_min, float* t_max) const
+    {
+        const float4 a = rays[2u * ln.at], b = rays[2u * ln.at + 1u];
+        *r = AovRay{{a.x, a.y, a.z}, {b.x, b.y, b.z}};
+        *t_min = a.w;
+        *t_max = b.w;
+    }
+};
+// the renderer's frame, every pixel's camera ray up to the pixel's depth (a holdout): k_view_aov's tiles, columns and mask -- the mask's
+// guarantee (no ray of the tile comes within a voxel of a non-empty one) does not depend on the depth
+struct ViewDepthLane { size_t at; uint32_t lx, y; };
+struct ViewDepth {
+    DevCamera cam;
+    DevFrame fr;
+    const float* __restrict__ depth;
+    float4* __restrict__ out;
+    uint32_t raise;
+    using Lane = ViewDepthLane;
+    __device__ __forceinline__ bool lane(Lane* ln) const
+    {
+        ln->lx = ln->y = 0u;
+        const bool inside = pixel_of_wave_tile(fr, &ln->lx, &ln->y);
+        ln->at = (size_t)ln->y * fr.w + ln->lx;
+        return inside;
+    }
+    __device__ __forceinline__ bool rejected(const Lane& ln) const { return tile_mask_clear(fr, ln.lx, ln.y); }
+    __device__ __forceinline__ void ray(const Lane& ln, AovRay* r, float* t_min, float* t_max) const
+    {
+        const uint32_t gx = global_x(fr, ln.lx);
+        *r = view_aov_camera_ray(cam.m, cam.pos, (float)gx * fr.inv_gw, (float)ln.y * fr.inv_gh);      // k_view_aov's ray
+        *t_min = 0.0f;
+        *t_max = depth[ln.at];
+    }
+};
+// an orthographic image of w x h pixels, its size the caller's: one 8x8 pixel tile per wave in row-major tile order, so that a wave's
+// rays cross neighbouring voxels; every ray walked whole
+struct OrthoViewLane { size_t at; uint32_t i, j; };
+struct OrthoView {
+    AovOrthoView view;
+    uint32_t w, h;
+    float4* __restrict__ out;
+    uint32_t raise;
+    using Lane = OrthoViewLane;
+    __device__ __forceinline__ bool lane(Lane* ln) const
+    {
+        const uint32_t tiles_x = (w + 7u) >> 3, lane = threadIdx.x & 63u;
+        const uint32_t tile = __builtin_amdgcn_readfirstlane(blockIdx.x * CAMERA_WAVES_PER_BLOCK + (threadIdx.x >> 6));
+        const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+        ln->i = tx * 8u + (lane & 7u);
+        ln->j = ty * 8u + (lane >> 3);
+        ln->at = (size_t)ln->j * w + ln->i;
+        return ln->i < w && ln->j < h;      // (a tile row beyond the image: j >= h)
+    }
+    __device__ __forceinline__ bool rejected(const Lane&) const { return false; }
+    __device__ __forceinline__ void ray(const Lane& ln, AovRay* r, float* t_min, float* t_max) const
+    {
+        *r = ray_aov_ortho_ray(view, ln.i, ln.j, w, h);
+        *t_min = 0.0f;
+        *t_max = NRC_AOV_INF;
+    }
+};
+template <typename Src>
+__global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK) void k_ray_aov(DevScene sc, Src src)
+{
+    if (!((NRC_DIAG_LOWPRIO) & 8) && src.raise != 0u) __builtin_amdgcn_s_setprio(NRC_WAVE_PRIORITY);      // camera_wave_priority
+    __shared__ uint32_t s_occ[kOccMaxWords];
+    typename Src::Lane ln;
+    const bool inside = src.lane(&ln);
+    if (__ballot(inside) == 0ull) return;      // a wave beyond the rays
+    if (src.rejected(ln)) {
+        if (inside) src.out[ln.at] = make_float4(0.0f, 0.0f, NRC_AOV_INF, NRC_AOV_INF);
+        return;
+    }
+    const uint32_t* occ = load_occupancy_per_wave(sc, s_occ);
+    if (!inside) return;
+    AovRay ray;
+    float t_min, t_max;
+    src.ray(ln, &ray, &t_min, &t_max);
+    const AovGrid g{sc.nx, sc.ny, sc.nz, {sc.size[0], sc.size[1], sc.size[2]}, sc.density_factor, sc.occ_shift, sc.occ_gx, sc.occ_gy};
+    const AovDensity den{__builtin_amdgcn_make_buffer_rsrc((void*)sc.density, 0, (int)(sc.nx * sc.ny * sc.nz), 0x00020000), sc.nx, sc.ny};
+    const ViewAov r = occ != nullptr ? view_aov_walk_range(g, ray, t_min, t_max, den, AovOccupancyBits{occ})
+                                     : view_aov_walk_range(g, ray, t_min, t_max, den, NoOccupancy{});
+    src.out[ln.at] = make_float4(r.alpha, r.tau, r.z_front, r.z_half);
+}
+
 // ------------------------------------------------------------------------------------------------ nrc/gen_rays.comp + prep_infer_rays.comp
 #ifndef NRC_GEN_WAVES_PER_SIMD
 #define NRC_GEN_WAVES_PER_SIMD NRC_CAMERA_WAVES_PER_SIMD
@@ -2385,6 +2494,41 @@ void launch_view_aov(const DevScene& sc, const DevCamera& cam, const DevFrame& f
     fa.hot_front = fa.hot_n = 0u;
     fa.raise_priority = (g_host_raise_wave_priority != 0 && fr.camera_priority_low == 0u) ? 1u : 0u;
     hipLaunchKernelGGL(k_view_aov, wave_tile_grid(fr.w, fr.h), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc, cam, fa, (float4*)out);
+    NRC_HIP(hipGetLastError());
+}
+
+// the ray AOV's three sources; fr: the renderer's frame -- the view's geometry and mask for the depth source, the priority switch for all
+static uint32_t ray_aov_raise(const DevFrame& fr) { return (g_host_raise_wave_priority != 0 && fr.camera_priority_low == 0u) ? 1u : 0u; }
+void launch_ray_aov_list(const DevScene& sc, const DevFrame& fr, size_t n, const float* rays, float* out, hipStream_t s)
+{
+    const size_t blocks = (n + 64u * CAMERA_WAVES_PER_BLOCK - 1u) / (64u * CAMERA_WAVES_PER_BLOCK);
+    if (blocks == 0u) return;
+    if (blocks > 0x7fffffffull) fail("ray AOV: too many rays for one launch");
+    if ((((uintptr_t)rays) | ((uintptr_t)out)) & 15u) fail("ray AOV: rays and out must be 16-byte aligned");
+    hipLaunchKernelGGL(k_ray_aov<RayList>, dim3((uint32_t)blocks), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,
+                       RayList{(const float4*)rays, (float4*)out, n, ray_aov_raise(fr)});
+    NRC_HIP(hipGetLastError());
+}
+void launch_ray_aov_view_depth(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const float* depth, float* out, hipStream_t s)
+{
+    DevFrame fa = fr;      // as for launch_view_aov: the default tile order, no hot tiles, no cost samples
+    fa.tile_order = nullptr;
+    fa.tile_cost = nullptr;
+    fa.hot_front = fa.hot_n = 0u;
+    if (((uintptr_t)out) & 15u) fail("ray AOV: out must be 16-byte aligned");
+    hipLaunchKernelGGL(k_ray_aov<ViewDepth>, wave_tile_grid(fr.w, fr.h), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,
+                       ViewDepth{cam, fa, depth, (float4*)out, ray_aov_raise(fr)});
+    NRC_HIP(hipGetLastError());
+}
+void launch_ray_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrthoView& view, uint32_t w, uint32_t h, float* out, hipStream_t s)
+{
+    if (w == 0u || h == 0u) return;
+    const uint64_t tiles = (uint64_t)ceil_div(w, 8) * ceil_div(h, 8);
+    const uint64_t blocks = (tiles + CAMERA_WAVES_PER_BLOCK - 1u) / CAMERA_WAVES_PER_BLOCK;
+    if (tiles > 0x7fffffffull) fail("ray AOV: the orthographic view is too large for one launch");      // (the kernel numbers its tiles in 32 bits)
+    if (((uintptr_t)out) & 15u) fail("ray AOV: out must be 16-byte aligned");
+    hipLaunchKernelGGL(k_ray_aov<OrthoView>, dim3((uint32_t)blocks), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,
+                       OrthoView{view, w, h, (float4*)out, ray_aov_raise(fr)});
     NRC_HIP(hipGetLastError());
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 #include "nrc_common.hpp"
 #include "nrc_hot_tiles.hpp"
+#include "nrc_view_aov.hpp"
 
 namespace nrc {
 
@@ -178,6 +179,13 @@ void launch_mc_render(const DevScene& sc, const DevCamera& cam, const DevFrame& 
 // the view AOV (nrc_view_aov.hpp): out [h][w][4] = {alpha, tau, z_front, z_half} of every pixel's camera ray through the scene's active
 // volume; fr carries the view's geometry and, when it has one, the empty-space tile mask of the SAME camera and medium.  One launch.
 void launch_view_aov(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, float* out, hipStream_t s);
+// the ray AOV (nrc_view_aov.hpp, view_aov_walk_range): the same four numbers of caller-supplied ray segments, one launch of k_ray_aov each.
+// fr is the renderer's frame.  rays [n][8] = {ox, oy, oz, t_min, dx, dy, dz, t_max} -> out [n][4]; the frame's camera rays up to depth [h][w]
+// (fr's geometry and tile mask, as for launch_view_aov) -> out [h][w][4]; an orthographic view of w x h pixels -> out [h][w][4].  rays and
+// out 16-byte aligned.
+void launch_ray_aov_list(const DevScene& sc, const DevFrame& fr, size_t n, const float* rays, float* out, hipStream_t s);
+void launch_ray_aov_view_depth(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const float* depth, float* out, hipStream_t s);
+void launch_ray_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrthoView& view, uint32_t w, uint32_t h, float* out, hipStream_t s);
 
 // ring: {uint head, uint tail, RayInfo[ring_size]}; scratch: uint32[2*T + 4]
 // start == nullptr: the whole of prep_train_rays.comp (scan, pop / trace / write, ring push).  start != nullptr (long train paths, the split

@@ -1,6 +1,7 @@
-// nrc_view_aov.hpp -- the view AOV of a camera ray: {alpha, tau, z_front, z_half} (include/nrc_hpm.h, "View AOV").  Device-free: plain
-// C++17 over nrc_math.h, every function host + device (NRC_HD).  k_view_aov (nrc_integrator.hip) and the host restatement
-// (nrc_test_view_aov_host, tests/cpp/view_aov_main.cpp under the sanitizers) run THIS code, so the fp32 arithmetic is stated once.
+// nrc_view_aov.hpp -- the view AOV of a camera ray: {alpha, tau, z_front, z_half} (include/nrc_hpm.h, "View AOV"), and the same of any
+// ray segment ("Ray AOV": view_aov_walk_range).  Device-free: plain C++17 over nrc_math.h, every function host + device (NRC_HD).
+// k_view_aov and k_ray_aov (nrc_integrator.hip) and the host restatements (nrc_test_view_aov_host, nrc_test_ray_aov_host,
+// tests/cpp/view_aov_main.cpp and ray_aov_main.cpp under the sanitizers) run THIS code, so the fp32 arithmetic is stated once.
 //
 // The medium is piecewise constant (get_density samples an R8 grid NEAREST), so the optical depth of a ray is the sum over the voxels
 // it crosses of sigma_i * (length inside voxel i).  The arithmetic is arranged so that the result does not depend on HOW a traversal
@@ -169,12 +170,37 @@ struct AovSum {
         if (tau < NRC_AOV_LN2 && tau_new >= NRC_AOV_LN2) z_half = fminf(ta + (NRC_AOV_LN2 - tau) / sigma, tb);
         tau = tau_new;
     }
+    // the same for a voxel whose segment [ta, tb] a range cuts at te <= tb: the optical depth is that of [ta, te]; z_half, where the cut
+    // segment reaches ln 2, is formed as on the whole ray -- clamped to the voxel's own far plane, not to te --, so a cut ray's z_half has
+    // the whole ray's bits (it may lie beyond te by the rounding of its quotient, never by more).  (add() stays its own statement of the
+    // whole segment: a version that wrote it as add_cut(.., tb, tb), and the whole walk as a wrapper, cost k_view_aov a register.)
+    NRC_HD void add_cut(float density_factor, uint32_t byte, float ta, float tb, float te)
+    {
+        if (byte == 0u) return;
+        const float sigma = density_factor * ((float)byte * (1.0f / 255.0f));      // get_density's value
+        const float tau_new = nrc_fmaf_(sigma, te - ta, tau);
+        z_front = fminf(z_front, ta);
+        if (tau < NRC_AOV_LN2 && tau_new >= NRC_AOV_LN2) z_half = fminf(ta + (NRC_AOV_LN2 - tau) / sigma, tb);
+        tau = tau_new;
+    }
 };
 constexpr uint32_t kAovRound = 4;
 
-template <class Density, class Occ>
-NRC_HD inline ViewAov view_aov_walk(const AovGrid& g, const AovRay& r, const Density& density, const Occ& occupied)
+// Ranged (view_aov_walk_range below, which states the rules): the part of the ray with max(t_min, 0) <= t <= t_max; otherwise the whole
+// ray, t in [max(box entry, 0), box exit], and t_min, t_max are not looked at -- every line the range adds is behind `if constexpr
+// (Ranged)`, so the whole-ray walk is the code it was.
+template <class Density, class Occ, bool Ranged = false>
+NRC_HD inline ViewAov view_aov_walk(const AovGrid& g, const AovRay& r, const Density& density, const Occ& occupied, float t_min = 0.0f,
+                                    float t_max = NRC_AOV_INF)
 {
+    float t_from = 0.0f;
+    if constexpr (Ranged) {
+        // (every comparison is false for a NaN: one in any of the eight numbers ends here, and so does an infinite origin or direction)
+        const bool finite = fabsf(r.ro[0]) < NRC_AOV_INF && fabsf(r.ro[1]) < NRC_AOV_INF && fabsf(r.ro[2]) < NRC_AOV_INF &&
+                            fabsf(r.rd[0]) < NRC_AOV_INF && fabsf(r.rd[1]) < NRC_AOV_INF && fabsf(r.rd[2]) < NRC_AOV_INF;
+        t_from = fmaxf(t_min, 0.0f);
+        if (!finite || !(t_min == t_min) || !(t_from < t_max)) return view_aov_empty();
+    }
     AovAxis X, Y, Z;
     const bool hx = view_aov_axis(r.ro[0], r.rd[0], g.size[0], g.nx, &X);
     const bool hy = view_aov_axis(r.ro[1], r.rd[1], g.size[1], g.ny, &Y);
@@ -182,9 +208,12 @@ NRC_HD inline ViewAov view_aov_walk(const AovGrid& g, const AovRay& r, const Den
     if (!(hx && hy && hz)) return view_aov_empty();
     // slab test: plane_t is +inf on an axis that is never crossed, which leaves t1 alone; its entry is "always inside"
     const float ex = X.dir ? X.plane_t(0) : 0.0f, ey = Y.dir ? Y.plane_t(0) : 0.0f, ez = Z.dir ? Z.plane_t(0) : 0.0f;
-    const float t0 = fmaxf(fmaxf(ex, ey), fmaxf(ez, 0.0f)) + 0.0f;      // (+ 0: never -0, whichever zero a maximum of two returns)
+    const float t0 = fmaxf(fmaxf(ex, ey), fmaxf(ez, Ranged ? t_from : 0.0f)) + 0.0f;      // (+ 0: never -0, whichever zero a maximum of two returns)
     const float t1 = fminf(fminf(X.plane_t(X.n), Y.plane_t(Y.n)), Z.plane_t(Z.n));
     if (!(t0 < t1) || !(t1 < NRC_AOV_INF)) return view_aov_empty();      // (t1 = +inf: no axis is crossed -- not a ray)
+    if constexpr (Ranged) {
+        if (!(t0 < t_max)) return view_aov_empty();      // the range ends in front of the box
+    }
     // the state at t0: every plane with t <= t0 is behind the ray.  (At least plane 0 of every crossed axis is, and plane n is not:
     // t(n) >= t1 > t0 -- the clamps never act, they are what keeps a voxel index inside the grid whatever the arithmetic does.)
     uint32_t vx = X.dir ? X.planes_before(t0, true) : view_aov_layer(r.ro[0], g.size[0], g.nx) + 1u;
@@ -240,6 +269,7 @@ NRC_HD inline ViewAov view_aov_walk(const AovGrid& g, const AovRay& r, const Den
             tb[0] = t_next;
             t_cur = t_next;
             done = vx >= X.n || vy >= Y.n || vz >= Z.n || --trips == 0u;      // through the box's exit plane
+            if constexpr (Ranged) done = done || !(t_next < t_max);             // ... or the range's end: the trip's far plane is at or beyond it
         }
 #if defined(__clang__)
 #pragma unroll
@@ -257,16 +287,55 @@ NRC_HD inline ViewAov view_aov_walk(const AovGrid& g, const AovRay& r, const Den
                 byte[k] = density(ix, iy, iz);
                 t_cur = tb[k] = view_aov_step(X, Y, Z, &vx, &vy, &vz);
                 done = vx >= X.n || vy >= Y.n || vz >= Z.n || --trips == 0u;
+                if constexpr (Ranged) done = done || !(t_cur < t_max);
             }
         }
 #if defined(__clang__)
 #pragma unroll
 #endif
-        for (uint32_t k = 0; k < kAovRound; k++) sum.add(g.density_factor, byte[k], ta[k], tb[k]);
+        for (uint32_t k = 0; k < kAovRound; k++) {
+            if constexpr (Ranged) sum.add_cut(g.density_factor, byte[k], ta[k], tb[k], fminf(tb[k], t_max));
+            else sum.add(g.density_factor, byte[k], ta[k], tb[k]);
+        }
     }
     const float tau = sum.tau, z_front = sum.z_front, z_half = sum.z_half;
     if (!(tau > 0.0f)) return view_aov_empty();      // (a ray that only grazes non-empty voxels along zero-length segments saw nothing)
     return ViewAov{nrc_expm1_negf(tau), tau, z_front, z_half};
+}
+
+// ---- a ray segment (include/nrc_hpm.h, "Ray AOV"): {alpha, tau, z_front, z_half} over the part of the ray ro + t rd with
+// max(t_min, 0) <= t <= t_max.  rd is used as given: t is the ray parameter and the optical depth is integrated against it -- with
+// |rd| = 1, t is distance and tau the optical depth the renderers mean.
+//   start   t0 = max(box entry, t_min, 0) + 0; the state at t0 is the whole walk's rule (every plane with t <= t0 is behind the ray:
+//           planes_before(t0, true)), so where t0 falls inside a non-empty voxel z_front is exactly t0.
+//   end     min(box exit, t_max): a voxel's segment [ta, tb] counts as [ta, fminf(tb, t_max)], and the walk is done after the first trip
+//           whose far plane is at or beyond t_max -- the jump out of an empty cell is such a trip.  A segment of length 0 adds nothing.
+//   bits    t_min <= 0 and t_max = +inf: view_aov_walk's bits.  A ray cut at t_max = T keeps the whole ray's z_front, and its z_half
+//           wherever the cut ray has one (AovSum::add_cut); tau accumulates identically up to the cut segment.  The plain walk
+//           (NoOccupancy) and the walk with jumps agree in every bit for every range: a jump only leaves out segments that add an exact 0.
+//   empty   {0, 0, +inf, +inf} for t_max <= max(t_min, 0), a NaN in any of the eight numbers, a zero or non-finite direction, a non-finite
+//           origin, and a range that holds no medium.  Never a NaN.
+template <class Density, class Occ>
+NRC_HD inline ViewAov view_aov_walk_range(const AovGrid& g, const AovRay& r, float t_min, float t_max, const Density& density, const Occ& occupied)
+{
+    return view_aov_walk<Density, Occ, true>(g, r, density, occupied, t_min, t_max);
+}
+
+// ---- the rays of the image-shaped sources, as records {ox, oy, oz, t_min, dx, dy, dz, t_max} (fma, +, - and / only: the same bits on
+// host and device).  The camera ray is view_aov_camera_ray's, whole.  An orthographic view is a parallelogram origin + su du + sv dv,
+// su = (i + 1/2) / w, sv = (j + 1/2) / h for pixel (i, j) of w x h, every ray with the view's direction as given.
+struct AovOrthoView {
+    float origin[3], du[3], dv[3], dir[3];
+};
+NRC_HD inline AovRay ray_aov_ortho_ray(const AovOrthoView& view, uint32_t i, uint32_t j, uint32_t w, uint32_t h)
+{
+    const float su = ((float)i + 0.5f) / (float)w, sv = ((float)j + 0.5f) / (float)h;
+    AovRay r;
+    for (int k = 0; k < 3; k++) {
+        r.ro[k] = nrc_fmaf_(su, view.du[k], nrc_fmaf_(sv, view.dv[k], view.origin[k]));
+        r.rd[k] = view.dir[k];
+    }
+    return r;
 }
 
 }  // namespace nrc

@@ -373,6 +373,29 @@ class HpmScene:
         return True
 
 
+def light_view(scene, w, h, light_dir=None, margin=1.0):
+    """The orthographic view {origin, du, dv, dir} (fp32; api.OrthoAov, api.ortho_rays) of the scene's directional light: the medium's
+    shadow map.  Rays travel the way the light does, l = normalize(light_dir or the scene's dir_light_dir) in fp64 (the shadow rays of a
+    frame walk the other way, towards -l), across the square spanned by a = normalize(l x (0,1,0)) -- l x (1,0,0) when |l_y| > 0.9 -- and
+    b = l x a, of half-width rad = |size| / 2 * margin: the box's bounding sphere at margin 1.  origin = -rad (l + a + b), du = 2 rad a,
+    dv = 2 rad b; dir has length 1, so depths are distances from the plane the rays start on.  w, h are the image's size: the view does not
+    depend on them."""
+    if int(w) <= 0 or int(h) <= 0:
+        raise ValueError("light_view: the image size must be positive")
+    s = scene.scene if hasattr(scene, "scene") else scene
+    l = np.asarray(s["dir_light_dir"] if light_dir is None else light_dir, np.float64).reshape(3)
+    n = np.linalg.norm(l)
+    if not np.isfinite(n) or n == 0.0:
+        raise ValueError("light_view: the light direction must be finite and non-zero")
+    l = l / n
+    a = np.cross(l, (1.0, 0.0, 0.0) if abs(l[1]) > 0.9 else (0.0, 1.0, 0.0))
+    a /= np.linalg.norm(a)
+    b = np.cross(l, a)
+    rad = 0.5 * float(np.linalg.norm(np.asarray(s["size"], np.float64))) * float(margin)
+    return dict(origin=(-rad * (l + a + b)).astype(np.float32), du=(2.0 * rad * a).astype(np.float32), dv=(2.0 * rad * b).astype(np.float32),
+                dir=l.astype(np.float32))
+
+
 def frame_randoms(n, seed=1337):
     """Per-frame UniformData.random (src/NrcHpmRenderer.cu:308): n x 4 floats in [0,1), seeded (std::mt19937-like role)."""
     rng = np.random.default_rng(seed)
