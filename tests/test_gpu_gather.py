@@ -7,6 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import image_reference as ir
+
 pytestmark = pytest.mark.gpu
 
 
@@ -46,6 +48,8 @@ def test_gather_of_ragged_column_tiles_and_sharded_metrics(api, sc, torch_gpu):
     ref[..., 3] = (rng.random((H, W)) < 0.7).astype(np.float32)
     ref_full = torch.from_numpy(ref).cuda()
     want = api.CompareImages(ref_full, full)
+    exact = ir.metrics_exact(ref, full.cpu().numpy())      # each metric within one fp32 ulp of the exact sums (tests/image_reference.py)
+    assert ir.metric_violations(want, exact) == []
     # raw sums of every rank's pixels, as the library's pass 1 / pass 2 leave them (fp64): what the other ranks contribute
     keep = []
     for r in range(world):
@@ -108,6 +112,7 @@ def test_gather_of_ragged_column_tiles_and_sharded_metrics(api, sc, torch_gpu):
         for key in ("mse", "ref_mean", "own_mean", "own_var"):
             assert abs(res[key] - want[key]) <= 3e-7 * abs(want[key]), (r, key, res[key], want[key])
         assert res["valid"] == want["valid"] > 1000
+        assert ir.metric_violations(res, exact) == [], r
     for x in rens + [one]:
         x.Destroy()
     for c in caches + [nrc1]:
@@ -136,6 +141,8 @@ def test_unsharded_renderer_and_single_rank_cache_take_the_trivial_paths(api, sc
     ref = torch.from_numpy(ref).cuda()
     a, b = api.CompareImages(ref, img), api.CompareImagesSharded(nrc, ref, img)
     assert a["valid"] == b["valid"] > 1000
+    exact = ir.metrics_exact(ref.cpu().numpy(), img.cpu().numpy())
+    assert ir.metric_violations(a, exact) == [] and ir.metric_violations(b, exact) == []
     for k in ("mse", "ref_mean", "own_mean", "own_var"):
         assert abs(a[k] - b[k]) <= 3e-7 * abs(a[k]), (k, a[k], b[k])
     ren.Destroy()

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import image_reference as ir
 from conftest import FRAME_RANDOM, GOLDEN, nrc_debug
 
 pytestmark = pytest.mark.gpu
@@ -783,9 +784,12 @@ def test_compare_images_and_exr_export(api, orc, sc, sphere_scene, torch_gpu, tm
     b.Render()
     ia, ib = a.GetImage(), b.GetImage()
     res = api.CompareImages(ia, ib)
-    ref = orc.compare(ia.cpu().numpy(), ib.cpu().numpy())
-    for k in ("mse", "ref_mean", "own_mean", "own_var", "valid"):
-        assert abs(res[k] - ref[k]) <= 1e-5 * max(1.0, abs(ref[k])), k
+    # all five numbers against the exact-sum reference: each metric within one fp32 ulp, valid equal (tests/image_reference.py) -- the
+    # kernels and the oracle alike
+    want = ir.metrics_exact(ia.cpu().numpy(), ib.cpu().numpy())
+    assert ir.metric_violations(res, want) == []
+    assert ir.metric_violations(orc.compare(ia.cpu().numpy(), ib.cpu().numpy()), want) == []
+    assert 0 < res["valid"] <= W * H and res["mse"] > 0
     p = str(tmp_path / "out.exr")
     a.ExportOutputImageToFile(None, p)
     assert np.array_equal(io_exr.read_exr(p), ia.cpu().numpy())
@@ -852,6 +856,9 @@ def test_reference_exr_pin_per_pixel_and_it_bites(api, sc, cloud16, exr_stats, t
         r = api.CompareImages(torch_gpu.from_numpy(ref).cuda(), torch_gpu.from_numpy(own).cuda())
         m = exr_pin.result_metrics(ref, own)
         assert abs(r["mse"] - m["mse"]) < 1e-5 * max(1.0, m["mse"]) and r["valid"] == m["valid"]
+        # all five numbers, each metric within one fp32 ulp of the exact sums (the EXRs' alpha is 0 around the cloud: holes in the valid set)
+        assert ir.metric_violations(r, ir.metrics_exact(ref, own)) == []
+        assert 0 < r["valid"] < ref.shape[0] * ref.shape[1]
         assert abs((r["own_mean"] - r["ref_mean"]) / r["ref_mean"]) < 0.03            # GetRelBias
         assert r["mse"] < 0.01                                                         # measured 0.0048 / 0.0012
     flagged = {}
