@@ -758,6 +758,12 @@ int nrc_debug_live_allocations(void);
  * Test hooks (bit-parity of the math spec and RNG against the oracle; device pointers) */
 int nrc_test_math(int fn, const float* d_a, const float* d_b, uint32_t n, float* d_out, float* d_out2, void* stream);
 int nrc_test_rng(float u, float v, const float frame_random[4], uint32_t n, float* d_out, void* stream);
+/* the capped-state side of the empty-space skip, as the renderers use it: selects from the process-wide free-flight table (2^23 floats, one
+ * per RNG state: the optical distance of 128 free flights) the states whose entry does not exceed lambda.  d_count_and_list: 9 words, the
+ * count and the first eight states found (any order); d_bits: 2^18 + 2 words, bit (m & 31) of word (m >> 5) set for every selected state m
+ * (the two words behind them are the slack a renderer's own buffer has: never written).  d_table_out: NULL, or 2^23 floats that receive
+ * a copy of the table.  Everything is enqueued on `stream`; no product path calls this. */
+int nrc_test_flight_select(float lambda, float* d_table_out, uint32_t* d_count_and_list, uint32_t* d_bits, void* stream);
 
 #ifdef __cplusplus
 }

@@ -103,7 +103,7 @@ ABI_SYMBOLS = [
     "nrc_mc_renderer_create", "nrc_mc_renderer_render", "nrc_mc_renderer_set_camera", "nrc_mc_renderer_set_blend",
     "nrc_mc_renderer_set_frame_random", "nrc_mc_renderer_framebuffer", "nrc_mc_renderer_export_exr",
     "nrc_mc_renderer_frame_time_ms", "nrc_mc_renderer_count_fetches", "nrc_mc_renderer_destroy",
-    "nrc_compare_images", "nrc_test_math", "nrc_test_rng", "nrc_debug_check_guards", "nrc_debug_live_allocations", "nrc_image_create", "nrc_image_destroy",
+    "nrc_compare_images", "nrc_test_math", "nrc_test_rng", "nrc_test_flight_select", "nrc_debug_check_guards", "nrc_debug_live_allocations", "nrc_image_create", "nrc_image_destroy",
 ]
 
 _lib = None
@@ -212,6 +212,8 @@ def load_library():
         L.nrc_ortho_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.nrc_test_ray_aov_host.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     L.nrc_mc_renderer_frame_time_ms.restype = C.c_float
+    if hasattr(L, "nrc_test_flight_select"):      # (an older build loaded through NRC_HPM_LIB has no such hook)
+        L.nrc_test_flight_select.argtypes = [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in ("nrc_cache_get_loss", "nrc_cache_get_loss_blocking", "nrc_renderer_is_blending", "nrc_mc_renderer_is_blending",
                  "nrc_cache_get_infer_batch_count", "nrc_cache_get_train_batch_count",
                  "nrc_cache_get_infer_batch_size", "nrc_cache_get_train_batch_size", "nrc_cache_grad_ptr",
@@ -1385,3 +1387,30 @@ def test_rng(u, v, frame_random, n):
     fr = (C.c_float * 4)(*[float(x) for x in frame_random])
     _check(load_library().nrc_test_rng(C.c_float(u), C.c_float(v), fr, C.c_uint32(n), _dev_ptr(out), _stream_ptr(None)))
     return out
+
+
+FLIGHT_STATES = 1 << 23
+FLIGHT_BITS_SENTINEL = 0xA5C3F00D
+
+
+def test_flight_select(lambda_, want_table=False, buffers=None):
+    """nrc_test_flight_select: the capped-state selection skip_setup makes at `lambda_`, from the free-flight table the renderers read.
+    Returns (count, list, bits, slack[, table]) as numpy arrays: list = the 8 words behind the count as the device left them, bits = the
+    2^18 words, slack = the two words behind them (filled with FLIGHT_BITS_SENTINEL before the call: the kernel must leave them), table =
+    the 2^23 floats when want_table.  buffers: a pair (count_and_list, bits) of torch CUDA int32 tensors of 9 and 2^18 + 2 words to reuse
+    (as a renderer reuses its own from one medium to the next); fresh ones, filled with the sentinel, otherwise."""
+    import torch
+    n_words = FLIGHT_STATES // 32
+    if buffers is None:
+        fill = FLIGHT_BITS_SENTINEL - (1 << 32)
+        buffers = (torch.full((9,), fill, dtype=torch.int32, device="cuda"), torch.full((n_words + 2,), fill, dtype=torch.int32, device="cuda"))
+    sel, bits = buffers
+    assert sel.numel() == 9 and bits.numel() == n_words + 2 and sel.dtype == torch.int32 and bits.dtype == torch.int32
+    table = torch.empty(FLIGHT_STATES, dtype=torch.float32, device="cuda") if want_table else None
+    _check(load_library().nrc_test_flight_select(C.c_float(float(lambda_)), _dev_ptr(table) if want_table else None, _dev_ptr(sel), _dev_ptr(bits),
+                                                 _stream_ptr(None)))
+    torch.cuda.synchronize()
+    h_sel = sel.cpu().numpy().view(np.uint32)
+    h_bits = bits.cpu().numpy().view(np.uint32)
+    out = (int(h_sel[0]), h_sel[1:].copy(), h_bits[:n_words].copy(), h_bits[n_words:].copy())
+    return out + (table.cpu().numpy(),) if want_table else out

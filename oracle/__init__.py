@@ -98,6 +98,12 @@ class Oracle:
         self.lib.orc_rng_kat(C.c_float(u), C.c_float(v), _ptr(fr), C.c_int(n), _ptr(out))
         return out
 
+    def flight_table(self, first=0, count=1 << 23, threads=16):
+        """orc_flight_table: float32 [count], the optical distance 128 free flights cover from RNG states first .. first + count - 1"""
+        out = np.zeros(count, np.float32)
+        self.lib.orc_flight_table(C.c_uint32(first), C.c_uint32(count), _ptr(out), C.c_int(threads))
+        return out
+
     def math_eval(self, fn, a, b=None):
         a = np.ascontiguousarray(a, np.float32)
         b = np.ascontiguousarray(b if b is not None else np.zeros_like(a), np.float32)

@@ -346,6 +346,26 @@ void orc_rng_kat(float u, float v, const float frame_random[4], int n, float* ou
     for (int i = 0; i < n; i++) out[1 + i] = c.rand(1.0f);
 }
 
+/* delta_track through empty space in units of 1 / sigma_max: out[i] = the distance a walk whose randomState is float_construct(first + i)
+ * has covered after its 128 free flights when every collision is rejected (get_density = 0: the acceptance draw is made and lost) */
+void orc_flight_table(uint32_t first, uint32_t count, float* out, int n_threads)
+{
+    const uint32_t row = 4096, n_rows = (count + row - 1) / row;
+    parallel_rows(0, n_rows, n_threads, [&](uint32_t r, int) {
+        const uint32_t end = std::min(count, (r + 1) * row);
+        for (uint32_t i = r * row; i < end; i++) {
+            Ctx c; c.fetches = 0; c.sc = nullptr;
+            c.rng = float_construct(first + i);
+            float d = 0.0f;
+            for (uint32_t k = 0; k < 128; k++) {
+                d = d - orc_logf(1.0f - c.rand(1.0f));      /* the free flight */
+                (void)c.rand(1.0f);                         /* 0 > rand: never accepted */
+            }
+            out[i] = d;
+        }
+    });
+}
+
 void orc_math_eval(int fn, const float* a, const float* b, int n, float* out, float* out2)
 {
     for (int i = 0; i < n; i++) {

@@ -56,6 +56,11 @@ float orc_random1(float x);
 /* out[0] = state after InitRandom(uv), out[1..n] = n RandFloat(1.0) draws */
 void orc_rng_kat(float u, float v, const float frame_random[4], int n, float* out);
 
+/* out[i], i < count: the distance, in units of 1 / sigma_max, that DeltaTrack (path_trace.glsl:150-174) has covered after its 128 free
+ * flights when it starts with randomState = float_construct(first + i) and rejects every collision (draws alternate flight, acceptance;
+ * the flight term is d = d - orc_logf(1.0f - u)).  A walk whose segment is longer than that in optical depth runs into the cap. */
+void orc_flight_table(uint32_t first, uint32_t count, float* out, int n_threads);
+
 /* ---- math spec (oracle/orc_math.h), exported for the GPU bit-parity test ---- */
 void orc_math_eval(int fn, const float* a, const float* b, int n, float* out, float* out2);
 

@@ -42,14 +42,15 @@ def init_random(gx, y, gw, gh, frame_random):
     return random2(random2(u, v), random4(frame_random))
 
 
-def frame_random_for_state0(gx, y, gw, gh, tries=64):
-    """a frame random vector (4 floats in [0, 1)) for which pixel (gx, y) of a gw x gh frame starts in RNG state 0"""
+def frame_random_for_state(gx, y, gw, gh, state=0, tries=64):
+    """a frame random vector (4 floats in [0, 1)) for which pixel (gx, y) of a gw x gh frame starts in RNG state float_construct(state)
+    (state: the 23-bit mantissa, 0 = the chain's fixed point), or None when the pixel has none"""
     u = np.float32(gx) * (np.float32(1.0) / np.float32(gw))
     v = np.float32(y) * (np.float32(1.0) / np.float32(gh))
     p = f2u(random2(u, v))
     mq = np.arange(1 << 23, dtype=np.uint32)
     q = float_construct(mq)                                   # every value random4 can return
-    hit = np.nonzero((hash1(p ^ hash1(f2u(q))) & M23) == 0)[0]
+    hit = np.nonzero((hash1(p ^ hash1(f2u(q))) & M23) == np.uint32(state))[0]
     if hit.size == 0:
         return None
     want = set(int(h) for h in hit)                           # mantissas of suitable Q
@@ -61,9 +62,14 @@ def frame_random_for_state0(gx, y, gw, gh, tries=64):
         idx = np.nonzero(np.isin(got, hit))[0]
         if idx.size:
             fr = [float(v0[idx[0]]), float(rest[0]), float(rest[1]), float(rest[2])]
-            assert float(init_random(gx, y, gw, gh, fr)) == 0.0
+            assert float(init_random(gx, y, gw, gh, fr)) == float(float_construct(state))
             return fr
     return None
+
+
+def frame_random_for_state0(gx, y, gw, gh, tries=64):
+    """a frame random vector (4 floats in [0, 1)) for which pixel (gx, y) of a gw x gh frame starts in RNG state 0"""
+    return frame_random_for_state(gx, y, gw, gh, 0, tries)
 
 
 def unhash1(x):
@@ -141,6 +147,11 @@ if __name__ == "__main__":
     if sys.argv[1] == "pair":
         for fr, px in two_state0_pixels_in_one_tile(int(sys.argv[2]), int(sys.argv[3]), want=int(sys.argv[4]) if len(sys.argv) > 4 else 1):
             print(fr, px)
+        sys.exit(0)
+    if sys.argv[1] == "state":      # state W H x y [x y ...]: the vector that pins each pixel into RNG state `state`
+        st, gw, gh = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
+        for gx, y in [(int(a), int(b)) for a, b in zip(sys.argv[5::2], sys.argv[6::2])]:
+            print((gx, y), frame_random_for_state(gx, y, gw, gh, st))
         sys.exit(0)
     gw, gh = int(sys.argv[1]), int(sys.argv[2])
     for gx, y in [(int(a), int(b)) for a, b in zip(sys.argv[3::2], sys.argv[4::2])]:

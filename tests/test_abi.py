@@ -25,6 +25,16 @@ def test_library_exports_every_declared_symbol(api):
     assert sorted(api.ABI_SYMBOLS) == decl           # the Python mirror binds exactly the declared surface
 
 
+def test_flight_select_hook_is_declared_bound_and_checks_its_arguments(api):
+    """nrc_test_flight_select (tests/test_gpu_flight_states.py): declared with the test hooks, bound with its argument types, and a call
+    without its output buffers is refused before anything touches a device"""
+    L = api.load_library()
+    assert "nrc_test_flight_select" in declared_symbols() and "nrc_test_flight_select" in api.ABI_SYMBOLS
+    assert L.nrc_test_flight_select.argtypes == [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    assert L.nrc_test_flight_select(80.0, None, None, None, None) == -1
+    assert b"SkyRenderer ERROR: null argument" in L.nrc_last_error()
+
+
 def test_version_and_default_config(api):
     L = api.load_library()
     assert b"gfx950" in L.nrc_version()
