@@ -744,6 +744,42 @@ int nrc_camera_rays(const nrc_camera* camera, uint32_t w, uint32_t h, const nrc_
 int nrc_ortho_rays(const nrc_ortho_view* view, uint32_t w, uint32_t h, float* host_rays);
 int nrc_test_ray_aov_host(const nrc_scene* scene, size_t n, const float* host_rays, float* host_out);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Deep AOV: the depths at which a ray reaches given optical depths -- the transmittance FUNCTION of a pixel (a deep image) or of a light-map
+ * texel (a deep shadow map), for depths that are not known when the call is made: an object can be placed inside the medium later without
+ * another walk.  Same records, ranges, medium and walk as the ray AOV; both renderers; ONE walk per ray whatever the number of levels.
+ *   Levels.  n_levels host floats L[0] < L[1] < .. < L[n_levels - 1], 1 <= n_levels <= 32, finite, L[0] > 0: optical depths (alpha =
+ *            1 - exp(-L)).  They are read during the call; the caller may reuse the array at once.
+ *   Result.  z[k] is the ray parameter at which the accumulated optical depth of the record's range reaches L[k], formed exactly as z_half
+ *            is: in the non-empty voxel whose segment [ta, tb] (cut at te = fminf(tb, t_max)) takes tau to tau_new = fma(sigma, te - ta, tau),
+ *            every level tau < L[k] <= tau_new gets z[k] = fminf(ta + (L[k] - tau) / sigma, tb).  A level the range never reaches is +inf.
+ *            z[k] is finite exactly when the flat result's tau >= L[k] (an fp32 compare); finite depths do not decrease with k; z_front <=
+ *            z[0].  With one level L = {ln 2 as fp32, 0x1.62e430p-1f} the plane is z_half bit for bit, and a level's plane does not depend
+ *            on the other levels of the call.
+ *   Layout.  Planar: level k of ray i is d_z[k * n + i] -- [n_levels][n], or [n_levels][h][w] for the image-shaped calls.  d_flat is NULL or
+ *            receives the ray AOV's {alpha, tau, z_front, z_half} of the same records ([n][4] / [h][w][4], 16-byte aligned), with the bits
+ *            the ray AOV's calls give.
+ *   Empty.   An empty or degenerate record (the ray AOV's list) gives +inf in every plane and the empty flat result; never a NaN.
+ * Every call enqueues ONE launch where the ray AOV's calls put theirs (behind the volume rebuilds enqueued so far and, for the camera's
+ * rays, behind the view's tile mask when one is due); no host wait, nothing kept, nothing allocated; a renderer on which none of them is
+ * made launches nothing for them.  NRC_ERR_INVALID, with a message and before anything is enqueued: n_levels == 0 or > 32; levels that
+ * are not strictly ascending, not finite or <= 0; NULL levels or d_z; NULL d_rays with n > 0.  n == 0 is a no-op.
+ * nrc_renderer_deep_ray_aov: ray i of d_rays [n][8].
+ * nrc_renderer_deep_view_aov: every pixel's camera ray up to d_depth [h][w] (nrc_renderer_view_aov_to_depth's rays); d_depth NULL: whole
+ *   rays.  A tile the view's mask rejects holds +inf in every plane.
+ * nrc_renderer_deep_ortho_aov: the orthographic view of nrc_renderer_ortho_aov, whole rays: a deep shadow map.
+ * nrc_test_deep_ray_aov_host (test hook): the list call on the CPU inside the library, by the header's plain voxel walk; host memory. */
+int nrc_renderer_deep_ray_aov(nrc_renderer_t* r, size_t n, const float* d_rays, uint32_t n_levels, const float* levels, float* d_z, float* d_flat);
+int nrc_renderer_deep_view_aov(nrc_renderer_t* r, const float* d_depth, uint32_t n_levels, const float* levels, float* d_z, float* d_flat);
+int nrc_renderer_deep_ortho_aov(nrc_renderer_t* r, const nrc_ortho_view* view, uint32_t w, uint32_t h, uint32_t n_levels, const float* levels,
+                                float* d_z, float* d_flat);
+int nrc_mc_renderer_deep_ray_aov(nrc_mc_renderer_t* r, size_t n, const float* d_rays, uint32_t n_levels, const float* levels, float* d_z, float* d_flat);
+int nrc_mc_renderer_deep_view_aov(nrc_mc_renderer_t* r, const float* d_depth, uint32_t n_levels, const float* levels, float* d_z, float* d_flat);
+int nrc_mc_renderer_deep_ortho_aov(nrc_mc_renderer_t* r, const nrc_ortho_view* view, uint32_t w, uint32_t h, uint32_t n_levels,
+                                   const float* levels, float* d_z, float* d_flat);
+int nrc_test_deep_ray_aov_host(const nrc_scene* scene, size_t n, const float* host_rays, uint32_t n_levels, const float* levels, float* host_z,
+                               float* host_flat);
+
 /* THE environment switch of the library: NRC_DEBUG="name[=value],..." -- diagnostic and test switches only, none changes a result
  * (the list and what each does: csrc/nrc_common.hpp, debug_switch).
  * diagnostics (read when the library first allocates): NRC_DEBUG=poison_alloc fills every device allocation with 0xFF

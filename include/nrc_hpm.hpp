@@ -494,6 +494,22 @@ public:
     void ViewAovToDepth(const float* dDepth, float* dOut) const { nrc_check(nrc_renderer_view_aov_to_depth(h_, dDepth, dOut)); }
     void OrthoAov(const nrc_ortho_view& view, uint32_t w, uint32_t h, float* dOut) const { nrc_check(nrc_renderer_ortho_aov(h_, &view, w, h, dOut)); }
     void SetPathAovDepths(const float* dDepths, uint32_t nViews) { nrc_check(nrc_renderer_set_path_aov_depths(h_, dDepths, nViews)); }
+    // The deep AOV (include/nrc_hpm.h, "Deep AOV"): the depths at which the same rays reach nLevels optical depths `levels` (host, ascending,
+    // positive, at most 32), one walk and one launch whatever nLevels.  dZ: planar, level k of ray i at dZ[k * n + i] ([nLevels][n] /
+    // [nLevels][height][width] / [nLevels][h][w]), +inf where a level is never reached; dFlat: nullptr, or the flat result of the same walk
+    // (RayAov's bits).  DeepViewAov: dDepth nullptr walks whole rays.  DeepOrthoAov: a deep shadow map.
+    void DeepRayAov(size_t n, const float* dRays, uint32_t nLevels, const float* levels, float* dZ, float* dFlat = nullptr) const
+    {
+        nrc_check(nrc_renderer_deep_ray_aov(h_, n, dRays, nLevels, levels, dZ, dFlat));
+    }
+    void DeepViewAov(const float* dDepth, uint32_t nLevels, const float* levels, float* dZ, float* dFlat = nullptr) const
+    {
+        nrc_check(nrc_renderer_deep_view_aov(h_, dDepth, nLevels, levels, dZ, dFlat));
+    }
+    void DeepOrthoAov(const nrc_ortho_view& view, uint32_t w, uint32_t h, uint32_t nLevels, const float* levels, float* dZ, float* dFlat = nullptr) const
+    {
+        nrc_check(nrc_renderer_deep_ortho_aov(h_, &view, w, h, nLevels, levels, dZ, dFlat));
+    }
     // ExportOutputImageToFile with the AOV beside the colours: FLOAT channels A (= alpha), B, G, R, Z (= z_front), Zhalf, tau; this renderer's pixels
     void ExportOutputImageWithAovToFile(void* /*queue*/, const std::string& filePath) const { nrc_check(nrc_renderer_export_exr_aov(h_, filePath.c_str())); }
     // diagnostics: the empty-space tile mask in use (synchronises; empty: the frame uses none) -- nrc_renderer_tile_mask
@@ -595,6 +611,19 @@ public:
     void ViewAovToDepth(const float* dDepth, float* dOut) const { nrc_check(nrc_mc_renderer_view_aov_to_depth(h_, dDepth, dOut)); }
     void OrthoAov(const nrc_ortho_view& view, uint32_t w, uint32_t h, float* dOut) const { nrc_check(nrc_mc_renderer_ortho_aov(h_, &view, w, h, dOut)); }
     void SetPathAovDepths(const float* dDepths, uint32_t nViews) { nrc_check(nrc_mc_renderer_set_path_aov_depths(h_, dDepths, nViews)); }
+    // see NrcHpmRenderer::DeepRayAov / DeepViewAov / DeepOrthoAov
+    void DeepRayAov(size_t n, const float* dRays, uint32_t nLevels, const float* levels, float* dZ, float* dFlat = nullptr) const
+    {
+        nrc_check(nrc_mc_renderer_deep_ray_aov(h_, n, dRays, nLevels, levels, dZ, dFlat));
+    }
+    void DeepViewAov(const float* dDepth, uint32_t nLevels, const float* levels, float* dZ, float* dFlat = nullptr) const
+    {
+        nrc_check(nrc_mc_renderer_deep_view_aov(h_, dDepth, nLevels, levels, dZ, dFlat));
+    }
+    void DeepOrthoAov(const nrc_ortho_view& view, uint32_t w, uint32_t h, uint32_t nLevels, const float* levels, float* dZ, float* dFlat = nullptr) const
+    {
+        nrc_check(nrc_mc_renderer_deep_ortho_aov(h_, &view, w, h, nLevels, levels, dZ, dFlat));
+    }
     void ExportOutputImageWithAovToFile(void* /*queue*/, const std::string& filePath) const { nrc_check(nrc_mc_renderer_export_exr_aov(h_, filePath.c_str())); }
     std::vector<uint32_t> TileMask() const
     {

@@ -96,6 +96,8 @@ ABI_SYMBOLS = [
     "nrc_renderer_ray_aov", "nrc_mc_renderer_ray_aov", "nrc_renderer_view_aov_to_depth", "nrc_mc_renderer_view_aov_to_depth",
     "nrc_renderer_ortho_aov", "nrc_mc_renderer_ortho_aov", "nrc_renderer_set_path_aov_depths", "nrc_mc_renderer_set_path_aov_depths",
     "nrc_camera_rays", "nrc_ortho_rays", "nrc_test_ray_aov_host",
+    "nrc_renderer_deep_ray_aov", "nrc_mc_renderer_deep_ray_aov", "nrc_renderer_deep_view_aov", "nrc_mc_renderer_deep_view_aov",
+    "nrc_renderer_deep_ortho_aov", "nrc_mc_renderer_deep_ortho_aov", "nrc_test_deep_ray_aov_host",
     "nrc_renderer_set_show_nrc", "nrc_renderer_set_frame_random", "nrc_renderer_framebuffer", "nrc_renderer_framebuffer_on",
     "nrc_renderer_export_exr",
     "nrc_renderer_frame_time_ms", "nrc_renderer_stage_stats", "nrc_renderer_frame_timeline", "nrc_set_wave_priority_raise", "nrc_renderer_destroy", "nrc_renderer_buffer", "nrc_renderer_count_fetches",
@@ -211,6 +213,14 @@ def load_library():
         L.nrc_camera_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.nrc_ortho_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.nrc_test_ray_aov_host.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    if hasattr(L, "nrc_renderer_deep_ray_aov"):      # (an older build loaded through NRC_HPM_LIB has no deep AOV)
+        for name in ("nrc_renderer_deep_ray_aov", "nrc_mc_renderer_deep_ray_aov"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ("nrc_renderer_deep_view_aov", "nrc_mc_renderer_deep_view_aov"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ("nrc_renderer_deep_ortho_aov", "nrc_mc_renderer_deep_ortho_aov"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nrc_test_deep_ray_aov_host.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.nrc_mc_renderer_frame_time_ms.restype = C.c_float
     if hasattr(L, "nrc_test_flight_select"):      # (an older build loaded through NRC_HPM_LIB has no such hook)
         L.nrc_test_flight_select.argtypes = [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -454,6 +464,21 @@ def _aov_out(what, out, shape):
     return _check_device_floats(what + ": out", out, shape)
 
 
+def _deep_levels_arg(levels):
+    """(contiguous float32 array, K) of the deep AOV's levels; the library checks their order and range"""
+    lv = np.ascontiguousarray(np.asarray(levels, np.float32).reshape(-1))
+    if lv.size == 0 or lv.size > 32:
+        raise ValueError("deep AOV: 1 .. 32 levels, not %d" % lv.size)
+    return lv, int(lv.size)
+
+
+def _deep_flat(what, flat, shape):
+    """the optional flat result: None, True (a new tensor) or the caller's tensor, checked"""
+    if flat is None or flat is False:
+        return None
+    return _aov_out(what + ": flat", None if flat is True else flat, shape)
+
+
 class NrcOrthoView(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3), ("dir", C.c_float * 3)]
 
@@ -586,6 +611,51 @@ class _LiveMedium:
         out = _aov_out("OrthoAov", out, (h, w, 4))
         _check(self._medium("ortho_aov")(self.h, C.byref(v), C.c_uint32(w), C.c_uint32(h), _dev_ptr(out)))
         return out
+
+    def DeepRayAov(self, rays, levels, out=None, flat=None):
+        """the deep AOV of a list of segments (include/nrc_hpm.h, "Deep AOV"; nrc_renderer_deep_ray_aov): rays as for RayAov, levels the
+        K optical depths (scene.deep_levels; ascending, positive, K <= 32).  Returns the planes [K][n] -- z[k][i]: the ray parameter at which
+        ray i reaches levels[k], +inf where it never does -- in `out` or a new tensor.  flat: None, True (a new tensor) or a tensor [n][4]
+        that receives RayAov's result of the same walk; with it the return value is (planes, flat).  One launch, no host wait."""
+        import torch
+        if not isinstance(rays, torch.Tensor) or rays.dim() != 2:
+            raise ValueError("DeepRayAov: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
+        _check_device_floats("DeepRayAov: rays", rays, (rays.shape[0], 8))
+        n = int(rays.shape[0])
+        lv, k = _deep_levels_arg(levels)
+        out = _aov_out("DeepRayAov", out, (k, n))
+        flat = _deep_flat("DeepRayAov", flat, (n, 4))
+        if n == 0:      # (no rays, no work -- and an empty tensor has no address for the library's NULL check)
+            return out if flat is None else (out, flat)
+        _check(self._medium("deep_ray_aov")(self.h, C.c_size_t(n), _dev_ptr(rays), C.c_uint32(k), lv.ctypes.data_as(C.c_void_p), _dev_ptr(out),
+                                            _dev_ptr(flat) if flat is not None else None))
+        return out if flat is None else (out, flat)
+
+    def DeepViewAov(self, levels, depth=None, out=None, flat=None):
+        """the deep AOV of every pixel's camera ray (nrc_renderer_deep_view_aov): a deep image's samples, planes [K][height][width].
+        depth: None (whole rays) or a depth image as for ViewAovToDepth.  flat as for DeepRayAov, [height][width][4]."""
+        if depth is not None:
+            _check_device_floats("DeepViewAov: depth", depth, (self.height, self.width))
+        lv, k = _deep_levels_arg(levels)
+        out = _aov_out("DeepViewAov", out, (k, self.height, self.width))
+        flat = _deep_flat("DeepViewAov", flat, (self.height, self.width, 4))
+        _check(self._medium("deep_view_aov")(self.h, _dev_ptr(depth) if depth is not None else None, C.c_uint32(k), lv.ctypes.data_as(C.c_void_p),
+                                             _dev_ptr(out), _dev_ptr(flat) if flat is not None else None))
+        return out if flat is None else (out, flat)
+
+    def DeepOrthoAov(self, view, w, h, levels, out=None, flat=None):
+        """the deep AOV of an orthographic view (scene.light_view): a deep shadow map, planes [K][h][w] (nrc_renderer_deep_ortho_aov).
+        flat as for DeepRayAov, [h][w][4]."""
+        w, h = int(w), int(h)
+        if w <= 0 or h <= 0:
+            raise ValueError("DeepOrthoAov: the image size must be positive")
+        v = make_c_ortho_view(view)
+        lv, k = _deep_levels_arg(levels)
+        out = _aov_out("DeepOrthoAov", out, (k, h, w))
+        flat = _deep_flat("DeepOrthoAov", flat, (h, w, 4))
+        _check(self._medium("deep_ortho_aov")(self.h, C.byref(v), C.c_uint32(w), C.c_uint32(h), C.c_uint32(k), lv.ctypes.data_as(C.c_void_p),
+                                              _dev_ptr(out), _dev_ptr(flat) if flat is not None else None))
+        return out if flat is None else (out, flat)
 
     def ExportImageWithAovToFile(self, filePath):
         """ExportOutputImageToFile with the view AOV beside the colours: a scan-line EXR with FLOAT channels A (alpha of the AOV), B, G, R,
@@ -1379,6 +1449,22 @@ def test_ray_aov_host(scene, rays):
     n = r.size // 8
     _check(load_library().nrc_test_ray_aov_host(C.byref(sc_), C.c_size_t(n), r.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+def deep_ray_aov_host(scene, rays, levels):
+    """nrc_test_deep_ray_aov_host: (planes [K][...], flat [...][4]) (numpy) of the records rays [...][8] through `scene`, computed on the CPU
+    inside the library by csrc/nrc_view_aov.hpp's plain deep range walk.  The levels go to the library as given: it refuses a bad set."""
+    sc_ = make_c_scene(scene.scene if hasattr(scene, "scene") else scene)
+    r = np.ascontiguousarray(rays, np.float32)
+    if r.ndim < 1 or r.shape[-1] != 8:
+        raise ValueError("deep_ray_aov_host: rays must have 8 numbers per record")
+    lv = np.ascontiguousarray(np.asarray(levels, np.float32).reshape(-1))
+    k, n = int(lv.size), r.size // 8
+    z = np.empty((k,) + r.shape[:-1], np.float32)
+    flat = np.empty(r.shape[:-1] + (4,), np.float32)
+    _check(load_library().nrc_test_deep_ray_aov_host(C.byref(sc_), C.c_size_t(n), r.ctypes.data_as(C.c_void_p), C.c_uint32(k),
+                                                     lv.ctypes.data_as(C.c_void_p), z.ctypes.data_as(C.c_void_p), flat.ctypes.data_as(C.c_void_p)))
+    return z, flat
 
 
 def test_rng(u, v, frame_random, n):

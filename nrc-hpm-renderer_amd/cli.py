@@ -98,6 +98,36 @@ def check_ray_aov_args(args):
             raise SystemExit("SkyRenderer ERROR: --shadow-size must be at least 1")
 
 
+DEEP_TAU_MAX = 3.0      # --deep: the levels run up to optical depth 3 (opacity 0.95) in equal steps of opacity
+
+
+def check_deep_args(args):
+    """what --deep can be combined with (raises SystemExit)"""
+    k = getattr(args, "deep", None)
+    if k is None:
+        return
+    if not 1 <= k <= 32:
+        raise SystemExit("SkyRenderer ERROR: --deep takes 1 .. 32 levels")
+    if not getattr(args, "aov", False) and not getattr(args, "shadow_map", None):
+        raise SystemExit("SkyRenderer ERROR: --deep adds channels to the --aov export or to the --shadow-map: give one of them")
+    if getattr(args, "aov", False) and "%" in (getattr(args, "export", None) or ""):
+        raise SystemExit("SkyRenderer ERROR: --deep is not available for a file per view (a path has no deep target)")
+
+
+def deep_planes(z):
+    """the channels Zd00 .. of a --deep export from the planes [K][h][w] (api.DeepViewAov / DeepOrthoAov)"""
+    return {"Zd%02d" % k: z[k] for k in range(z.shape[0])}
+
+
+def write_deep_sidecar(path, levels):
+    """the levels of a --deep export beside it: <file without .exr>.json = {"tau_max", "levels", "channels"}; returns the name"""
+    import json
+    name = os.path.splitext(path)[0] + ".json"
+    with open(name, "w") as f:
+        json.dump({"tau_max": DEEP_TAU_MAX, "levels": [float(x) for x in levels], "channels": ["Zd%02d" % k for k in range(len(levels))]}, f)
+    return name
+
+
 def shadow_planes(aov):
     """the channels of a --shadow-map file from the light view's [h][w][4] ray AOV"""
     return {"A": aov[..., 0], "tau": aov[..., 1], "Z": aov[..., 2], "Zhalf": aov[..., 3]}
@@ -172,6 +202,10 @@ def main(argv=None):
     ap.add_argument("--shadow-map", default=None, metavar="PATH",
                     help="write the medium's shadow map to this EXR: FLOAT channels A, Z, Zhalf, tau along the directional light's rays "
                          "(scene.light_view; include/nrc_hpm.h, nrc_renderer_ortho_aov), of the medium the run ends with")
+    ap.add_argument("--deep", type=int, default=None, metavar="K",
+                    help="with --aov and/or --shadow-map: K (1 .. 32) more FLOAT channels Zd00 .. Zd<K-1>, the depths at which the pixel's ray "
+                         "reaches K optical depths equally spaced in opacity up to tau 3 (scene.deep_levels; include/nrc_hpm.h, \"Deep AOV\"); "
+                         "the levels are printed and written beside the file as .json")
     ap.add_argument("--shadow-size", type=int, default=1024, metavar="N", help="--shadow-map: the map is N x N pixels")
     ap.add_argument("--orbit", type=int, default=None, metavar="N",
                     help="render an N-view turntable around the volume with one RenderPath call (include/nrc_hpm.h, nrc_renderer_render_path): "
@@ -201,6 +235,7 @@ def main(argv=None):
     n_views = check_orbit_args(args)
     check_aov_args(args)
     check_ray_aov_args(args)
+    check_deep_args(args)
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # start the ranks before anything touches the GPU in this process (a process that has initialised HIP must not spawn them)
@@ -376,9 +411,20 @@ def main(argv=None):
     if args.skip_nonfinite and rank == 0:
         print("skipped %d of %d steps" % (nrc.GetSkippedSteps()[0], nrc.GetStep()))
     if args.export and not failed and not (n_views and "%" in args.export):
+        cam = views[-1] if n_views else camera
+        depth = None
         if args.aov and args.holdout_sphere is not None:
-            cam = views[-1] if n_views else camera
-            held = nrc_renderer.ViewAovToDepth(torch.from_numpy(sphere_depth(api.camera_rays(cam, lw, H), args.holdout_sphere)).cuda())
+            depth = torch.from_numpy(sphere_depth(api.camera_rays(cam, lw, H), args.holdout_sphere)).cuda()
+        if args.aov and args.deep:      # the flat AOV and the K depths of one walk (whole rays, or out to the sphere)
+            levels = sc.deep_levels(args.deep, DEEP_TAU_MAX)
+            z, held = nrc_renderer.DeepViewAov(levels, depth=depth, flat=True)
+            planes = aov_planes(nrc_renderer.GetImage().cpu().numpy(), held.cpu().numpy())
+            planes.update(deep_planes(z.cpu().numpy()))
+            io_exr.write_exr_channels(args.export, planes)
+            if rank == 0:
+                print("deep levels %s -> %s" % (" ".join("%.6g" % x for x in levels), write_deep_sidecar(args.export, levels)))
+        elif depth is not None:
+            held = nrc_renderer.ViewAovToDepth(depth)
             io_exr.write_exr_channels(args.export, aov_planes(nrc_renderer.GetImage().cpu().numpy(), held.cpu().numpy()))
         elif args.aov:
             nrc_renderer.ExportImageWithAovToFile(args.export)
@@ -386,8 +432,16 @@ def main(argv=None):
             nrc_renderer.ExportOutputImageToFile(None, args.export)      # sharded: collective, rank 0 writes the whole frame
     if args.shadow_map and not failed and rank == 0:      # (every rank holds the whole medium: rank 0's map is the map)
         n = args.shadow_size
-        shadow = nrc_renderer.OrthoAov(sc.light_view(scene, n, n), n, n)
-        io_exr.write_exr_channels(args.shadow_map, shadow_planes(shadow.cpu().numpy()))
+        if args.deep:      # a deep shadow map: the same four channels and the K depths, one walk
+            levels = sc.deep_levels(args.deep, DEEP_TAU_MAX)
+            z, shadow = nrc_renderer.DeepOrthoAov(sc.light_view(scene, n, n), n, n, levels, flat=True)
+            planes = shadow_planes(shadow.cpu().numpy())
+            planes.update(deep_planes(z.cpu().numpy()))
+            io_exr.write_exr_channels(args.shadow_map, planes)
+            print("deep levels %s -> %s" % (" ".join("%.6g" % x for x in levels), write_deep_sidecar(args.shadow_map, levels)))
+        else:
+            shadow = nrc_renderer.OrthoAov(sc.light_view(scene, n, n), n, n)
+            io_exr.write_exr_channels(args.shadow_map, shadow_planes(shadow.cpu().numpy()))
     nrc_renderer.Destroy()
     if ref is not None:
         eval_renderer.Destroy()

@@ -1182,6 +1182,69 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK) void k_ray_aov(DevScen
     src.out[ln.at] = make_float4(r.alpha, r.tau, r.z_front, r.z_half);
 }
 
+// ------------------------------------------------------------------------------------------------ the deep AOV (nrc_view_aov.hpp, deep_aov_walk_range)
+// The depths at which a ray reaches the caller's K optical depths, in the one walk that also forms the flat result: k_ray_aov's kernel
+// over the same three sources (a source's `out` is the flat image here, and may be null), with the header's deep sum in the walk.
+//   output   planar: level k of ray i at z[k * n + i], so the 64 stores a wave makes of one level are neighbours.  A lane stores z[k] when
+//            it crosses level k (the sum keeps no depth: K registers would not fit) and +inf to the planes it never reached after the walk.
+//   levels   the same for every ray, but `next` is the lane's own: they come by value in the kernel arguments and every wave copies them to
+//            its own 128 bytes of LDS (beside the 8 KB table and the 1 KB log table), where a per-lane index costs neither scratch nor K
+//            registers.  The copy is the wave's own -- a wave fence, no workgroup barrier, as for the table.
+//   rejected a wave whose tile the mask rejects stores +inf to all K planes (and the empty flat result) and is gone before either copy.
+struct AovLevels { float v[kAovDeepMaxLevels]; };
+struct DeepOut {
+    float* __restrict__ z;
+    size_t n;                // rays: the stride of a plane
+    uint32_t n_levels;
+    AovLevels levels;        // (those beyond n_levels: 0, never read by the walk)
+};
+// the lane's ray and range: the source's, but the view's depth image is optional here -- null: every pixel's whole ray
+template <typename Src>
+__device__ __forceinline__ void deep_aov_ray(const Src& src, const typename Src::Lane& ln, AovRay* r, float* t_min, float* t_max)
+{
+    src.ray(ln, r, t_min, t_max);
+}
+__device__ __forceinline__ void deep_aov_ray(const ViewDepth& src, const ViewDepthLane& ln, AovRay* r, float* t_min, float* t_max)
+{
+    const uint32_t gx = global_x(src.fr, ln.lx);
+    *r = view_aov_camera_ray(src.cam.m, src.cam.pos, (float)gx * src.fr.inv_gw, (float)ln.y * src.fr.inv_gh);      // k_view_aov's ray
+    *t_min = 0.0f;
+    *t_max = src.depth != nullptr ? src.depth[ln.at] : NRC_AOV_INF;
+}
+template <typename Src>
+__global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK) void k_deep_aov(DevScene sc, Src src, DeepOut deep)
+{
+    if (!((NRC_DIAG_LOWPRIO) & 8) && src.raise != 0u) __builtin_amdgcn_s_setprio(NRC_WAVE_PRIORITY);      // camera_wave_priority
+    __shared__ uint32_t s_occ[kOccMaxWords];
+    __shared__ float s_levels[CAMERA_WAVES_PER_BLOCK][kAovDeepMaxLevels];
+    typename Src::Lane ln;
+    const bool inside = src.lane(&ln);
+    if (__ballot(inside) == 0ull) return;      // a wave beyond the rays
+    if (src.rejected(ln)) {
+        if (inside) {
+            for (uint32_t k = 0; k < deep.n_levels; k++) deep.z[(size_t)k * deep.n + ln.at] = NRC_AOV_INF;
+            if (src.out != nullptr) src.out[ln.at] = make_float4(0.0f, 0.0f, NRC_AOV_INF, NRC_AOV_INF);
+        }
+        return;
+    }
+    float* levels = s_levels[threadIdx.x >> 6];
+    if ((threadIdx.x & 63u) < kAovDeepMaxLevels) levels[threadIdx.x & 63u] = deep.levels.v[threadIdx.x & 63u];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint32_t* occ = load_occupancy_per_wave(sc, s_occ);
+    if (!inside) return;
+    AovRay ray;
+    float t_min, t_max;
+    deep_aov_ray(src, ln, &ray, &t_min, &t_max);
+    const AovGrid g{sc.nx, sc.ny, sc.nz, {sc.size[0], sc.size[1], sc.size[2]}, sc.density_factor, sc.occ_shift, sc.occ_gx, sc.occ_gy};
+    const AovDensity den{__builtin_amdgcn_make_buffer_rsrc((void*)sc.density, 0, (int)(sc.nx * sc.ny * sc.nz), 0x00020000), sc.nx, sc.ny};
+    AovDeepArray sink{deep.z + ln.at, deep.n};
+    const ViewAov r = occ != nullptr ? deep_aov_walk_range(g, ray, t_min, t_max, den, AovOccupancyBits{occ}, levels, deep.n_levels, &sink)
+                                     : deep_aov_walk_range(g, ray, t_min, t_max, den, NoOccupancy{}, levels, deep.n_levels, &sink);
+    if (src.out != nullptr) src.out[ln.at] = make_float4(r.alpha, r.tau, r.z_front, r.z_half);
+}
+
 // ------------------------------------------------------------------------------------------------ nrc/gen_rays.comp + prep_infer_rays.comp
 #ifndef NRC_GEN_WAVES_PER_SIMD
 #define NRC_GEN_WAVES_PER_SIMD NRC_CAMERA_WAVES_PER_SIMD
@@ -2529,6 +2592,50 @@ void launch_ray_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrtho
     if (((uintptr_t)out) & 15u) fail("ray AOV: out must be 16-byte aligned");
     hipLaunchKernelGGL(k_ray_aov<OrthoView>, dim3((uint32_t)blocks), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,
                        OrthoView{view, w, h, (float4*)out, ray_aov_raise(fr)});
+    NRC_HIP(hipGetLastError());
+}
+
+// the deep AOV over the same three sources; levels: n_levels host floats the caller has checked (deep_aov_levels_error); z: [n_levels][rays];
+// flat: null, or the rays' flat results
+static DeepOut deep_out(float* z, size_t n, uint32_t n_levels, const float* levels, const float* flat)
+{
+    if (n_levels == 0u || n_levels > kAovDeepMaxLevels) fail("deep AOV: the number of levels must be 1 .. 32");
+    if (((uintptr_t)flat) & 15u) fail("deep AOV: flat must be 16-byte aligned");
+    DeepOut d{z, n, n_levels, {}};
+    for (uint32_t k = 0; k < n_levels; k++) d.levels.v[k] = levels[k];
+    return d;
+}
+void launch_deep_aov_list(const DevScene& sc, const DevFrame& fr, size_t n, const float* rays, uint32_t n_levels, const float* levels, float* z,
+                          float* flat, hipStream_t s)
+{
+    const size_t blocks = (n + 64u * CAMERA_WAVES_PER_BLOCK - 1u) / (64u * CAMERA_WAVES_PER_BLOCK);
+    if (blocks == 0u) return;
+    if (blocks > 0x7fffffffull) fail("deep AOV: too many rays for one launch");
+    if (((uintptr_t)rays) & 15u) fail("deep AOV: rays must be 16-byte aligned");
+    hipLaunchKernelGGL(k_deep_aov<RayList>, dim3((uint32_t)blocks), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,
+                       RayList{(const float4*)rays, (float4*)flat, n, ray_aov_raise(fr)}, deep_out(z, n, n_levels, levels, flat));
+    NRC_HIP(hipGetLastError());
+}
+void launch_deep_aov_view_depth(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const float* depth, uint32_t n_levels,
+                                const float* levels, float* z, float* flat, hipStream_t s)
+{
+    DevFrame fa = fr;      // as for launch_view_aov: the default tile order, no hot tiles, no cost samples
+    fa.tile_order = nullptr;
+    fa.tile_cost = nullptr;
+    fa.hot_front = fa.hot_n = 0u;
+    hipLaunchKernelGGL(k_deep_aov<ViewDepth>, wave_tile_grid(fr.w, fr.h), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,
+                       ViewDepth{cam, fa, depth, (float4*)flat, ray_aov_raise(fr)}, deep_out(z, (size_t)fr.w * fr.h, n_levels, levels, flat));
+    NRC_HIP(hipGetLastError());
+}
+void launch_deep_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrthoView& view, uint32_t w, uint32_t h, uint32_t n_levels,
+                           const float* levels, float* z, float* flat, hipStream_t s)
+{
+    if (w == 0u || h == 0u) return;
+    const uint64_t tiles = (uint64_t)ceil_div(w, 8) * ceil_div(h, 8);
+    const uint64_t blocks = (tiles + CAMERA_WAVES_PER_BLOCK - 1u) / CAMERA_WAVES_PER_BLOCK;
+    if (tiles > 0x7fffffffull) fail("deep AOV: the orthographic view is too large for one launch");      // (the kernel numbers its tiles in 32 bits)
+    hipLaunchKernelGGL(k_deep_aov<OrthoView>, dim3((uint32_t)blocks), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,
+                       OrthoView{view, w, h, (float4*)flat, ray_aov_raise(fr)}, deep_out(z, (size_t)w * h, n_levels, levels, flat));
     NRC_HIP(hipGetLastError());
 }
 

@@ -186,6 +186,15 @@ void launch_view_aov(const DevScene& sc, const DevCamera& cam, const DevFrame& f
 void launch_ray_aov_list(const DevScene& sc, const DevFrame& fr, size_t n, const float* rays, float* out, hipStream_t s);
 void launch_ray_aov_view_depth(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const float* depth, float* out, hipStream_t s);
 void launch_ray_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrthoView& view, uint32_t w, uint32_t h, float* out, hipStream_t s);
+// the deep AOV (nrc_view_aov.hpp, deep_aov_walk_range): the depths at which the same rays reach the n_levels optical depths `levels` (host
+// floats, already checked: deep_aov_levels_error), one launch of k_deep_aov each.  z [n_levels][rays] (planar), flat: null or the rays' flat
+// results [rays][4], 16-byte aligned; depth: null or as above.
+void launch_deep_aov_list(const DevScene& sc, const DevFrame& fr, size_t n, const float* rays, uint32_t n_levels, const float* levels, float* z,
+                          float* flat, hipStream_t s);
+void launch_deep_aov_view_depth(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const float* depth, uint32_t n_levels,
+                                const float* levels, float* z, float* flat, hipStream_t s);
+void launch_deep_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrthoView& view, uint32_t w, uint32_t h, uint32_t n_levels,
+                           const float* levels, float* z, float* flat, hipStream_t s);
 
 // ring: {uint head, uint tail, RayInfo[ring_size]}; scratch: uint32[2*T + 4]
 // start == nullptr: the whole of prep_train_rays.comp (scan, pop / trace / write, ring push).  start != nullptr (long train paths, the split

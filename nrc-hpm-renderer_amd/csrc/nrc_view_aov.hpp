@@ -2,6 +2,8 @@
 // ray segment ("Ray AOV": view_aov_walk_range).  Device-free: plain C++17 over nrc_math.h, every function host + device (NRC_HD).
 // k_view_aov and k_ray_aov (nrc_integrator.hip) and the host restatements (nrc_test_view_aov_host, nrc_test_ray_aov_host,
 // tests/cpp/view_aov_main.cpp and ray_aov_main.cpp under the sanitizers) run THIS code, so the fp32 arithmetic is stated once.
+// The deep AOV ("Deep AOV": deep_aov_walk_range, at the end) is the same walk with another sum: k_deep_aov, nrc_test_deep_ray_aov_host and
+// tests/cpp/deep_aov_main.cpp run it.
 //
 // The medium is piecewise constant (get_density samples an R8 grid NEAREST), so the optical depth of a ray is the sum over the voxels
 // it crosses of sigma_i * (length inside voxel i).  The arithmetic is arranged so that the result does not depend on HOW a traversal
@@ -189,9 +191,16 @@ constexpr uint32_t kAovRound = 4;
 // Ranged (view_aov_walk_range below, which states the rules): the part of the ray with max(t_min, 0) <= t <= t_max; otherwise the whole
 // ray, t in [max(box entry, 0), box exit], and t_min, t_max are not looked at -- every line the range adds is behind `if constexpr
 // (Ranged)`, so the whole-ray walk is the code it was.
-template <class Density, class Occ, bool Ranged = false>
+// Policy: what is made of the segments.  policy.sum() is the walk's sum, made where the walk starts summing -- add / add_cut as AovSum has
+// them, and its tau, z_front, z_half.  The default, AovFlat, makes AovSum itself, so the view and ray AOV's instantiations are the code
+// they were (the deep AOV's policy: AovDeep below).
+struct AovFlat {
+    using Sum = AovSum;
+    NRC_HD AovSum sum() const { return AovSum(); }
+};
+template <class Density, class Occ, bool Ranged = false, class Policy = AovFlat>
 NRC_HD inline ViewAov view_aov_walk(const AovGrid& g, const AovRay& r, const Density& density, const Occ& occupied, float t_min = 0.0f,
-                                    float t_max = NRC_AOV_INF)
+                                    float t_max = NRC_AOV_INF, const Policy& policy = Policy())
 {
     float t_from = 0.0f;
     if constexpr (Ranged) {
@@ -222,7 +231,7 @@ NRC_HD inline ViewAov view_aov_walk(const AovGrid& g, const AovRay& r, const Den
     vx = (vx < 1u ? 1u : (vx > X.n ? X.n : vx)) - 1u;
     vy = (vy < 1u ? 1u : (vy > Y.n ? Y.n : vy)) - 1u;
     vz = (vz < 1u ? 1u : (vz > Z.n ? Z.n : vz)) - 1u;
-    AovSum sum;
+    typename Policy::Sum sum = policy.sum();
     float t_cur = t0;
     const uint32_t sh = g.occ_shift;
     // Every trip crosses at least one plane: at most nx + ny + nz trips.  They are made in rounds of kAovRound: the first trip of a round is
@@ -336,6 +345,77 @@ NRC_HD inline AovRay ray_aov_ortho_ray(const AovOrthoView& view, uint32_t i, uin
         r.rd[k] = view.dir[k];
     }
     return r;
+}
+
+// ---- the deep AOV (include/nrc_hpm.h, "Deep AOV"): the ray parameters z[k] at which the accumulated optical depth of a ray segment reaches
+// the caller's levels L[0] < L[1] < .. < L[K - 1] (1 <= K <= kAovDeepMaxLevels, finite, L[0] > 0), in the SAME single walk that forms the
+// flat {alpha, tau, z_front, z_half}.  z_half is the one-level case and the rule is its rule: in the non-empty voxel whose segment
+// [ta, tb], cut at te, takes tau to tau_new = fma(sigma, te - ta, tau),
+//     while (next < K && tau_new >= L[next]) { z[next] = fminf(ta + (L[next] - tau) / sigma, tb); next++; }
+// tau < L[next] holds on entry (next has moved past every level tau has reached), so for K = 1, L = {NRC_AOV_LN2} the plane is z_half bit
+// for bit; several levels may be crossed in one voxel; the clamp is to the voxel's own far plane, as in add_cut.  A crossing is handed to
+// the sink, emit(k, z), when it happens -- the sum keeps no depth.  tau never decreases along the walk and the flat result's tau is the
+// last tau_new, so level k was emitted exactly when the result's tau >= L[k] (an fp32 compare): the levels never reached are the tail
+// behind the last one that compare admits, and they are emitted as +inf after the walk -- for an empty or degenerate record all K.
+constexpr uint32_t kAovDeepMaxLevels = 32;
+template <class Sink>
+struct AovDeepSum {
+    const float* levels;
+    uint32_t n_levels;
+    Sink* sink;
+    uint32_t next = 0u;
+    float tau = 0.0f, z_front = NRC_AOV_INF, z_half = NRC_AOV_INF;
+    NRC_HD void add_cut(float density_factor, uint32_t byte, float ta, float tb, float te)
+    {
+        if (byte == 0u) return;
+        const float sigma = density_factor * ((float)byte * (1.0f / 255.0f));      // get_density's value
+        const float tau_new = nrc_fmaf_(sigma, te - ta, tau);
+        z_front = fminf(z_front, ta);
+        if (tau < NRC_AOV_LN2 && tau_new >= NRC_AOV_LN2) z_half = fminf(ta + (NRC_AOV_LN2 - tau) / sigma, tb);
+        while (next < n_levels && tau_new >= levels[next]) {
+            sink->emit(next, fminf(ta + (levels[next] - tau) / sigma, tb));
+            next++;
+        }
+        tau = tau_new;
+    }
+    NRC_HD void add(float density_factor, uint32_t byte, float ta, float tb) { add_cut(density_factor, byte, ta, tb, tb); }
+};
+template <class Sink>
+struct AovDeep {
+    using Sum = AovDeepSum<Sink>;
+    const float* levels;
+    uint32_t n_levels;
+    Sink* sink;
+    NRC_HD Sum sum() const { return Sum{levels, n_levels, sink}; }
+};
+// the range walk's record and rules (above), its flat result with the same bits, and the K depths through sink.emit(k, z): every k once
+template <class Density, class Occ, class Sink>
+NRC_HD inline ViewAov deep_aov_walk_range(const AovGrid& g, const AovRay& r, float t_min, float t_max, const Density& density, const Occ& occupied,
+                                          const float* levels, uint32_t n_levels, Sink* sink)
+{
+    const ViewAov a = view_aov_walk<Density, Occ, true, AovDeep<Sink>>(g, r, density, occupied, t_min, t_max, AovDeep<Sink>{levels, n_levels, sink});
+    uint32_t k = 0u;
+    while (k < n_levels && a.tau >= levels[k]) k++;
+    for (; k < n_levels; k++) sink->emit(k, NRC_AOV_INF);
+    return a;
+}
+// the host sink: plane k of the ray into z[k * stride]
+struct AovDeepArray {
+    float* z;
+    size_t stride;
+    NRC_HD void emit(uint32_t k, float v) { z[(size_t)k * stride] = v; }
+};
+// the levels' rule, for every entry point: NULL when they are in order, otherwise what is wrong with them
+inline const char* deep_aov_levels_error(uint32_t n_levels, const float* levels)
+{
+    if (n_levels == 0u || n_levels > kAovDeepMaxLevels) return "the number of levels must be 1 .. 32";
+    if (levels == nullptr) return "levels is NULL";
+    for (uint32_t k = 0; k < n_levels; k++) {
+        if (!(fabsf(levels[k]) < NRC_AOV_INF)) return "every level must be finite";
+        if (!(levels[k] > 0.0f)) return "every level must be positive";
+        if (k > 0u && !(levels[k] > levels[k - 1u])) return "the levels must be strictly ascending";
+    }
+    return nullptr;
 }
 
 }  // namespace nrc

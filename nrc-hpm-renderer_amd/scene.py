@@ -396,6 +396,52 @@ def light_view(scene, w, h, light_dir=None, margin=1.0):
                 dir=l.astype(np.float32))
 
 
+def deep_levels(k, tau_max):
+    """The k levels (fp32, ascending) of a deep AOV (api.DeepRayAov / DeepViewAov / DeepOrthoAov) that are equally spaced in opacity up to
+    optical depth tau_max: alpha_i = (i + 1) / k * (1 - exp(-tau_max)), level i = -log1p(-alpha_i).  Equal steps of alpha are equal steps of
+    what a compositor sees; the last level is tau_max itself."""
+    k = int(k)
+    if not 1 <= k <= 32:
+        raise ValueError("deep_levels: 1 .. 32 levels")
+    if not (math.isfinite(tau_max) and tau_max > 0.0):
+        raise ValueError("deep_levels: tau_max must be finite and positive")
+    alpha = (np.arange(1, k + 1, dtype=np.float64) / k) * -np.expm1(-float(tau_max))
+    levels = (-np.log1p(-alpha)).astype(np.float32)
+    if not (levels[0] > 0.0 and np.isfinite(levels).all() and (np.diff(levels) > 0.0).all()):
+        raise ValueError("deep_levels: %d levels up to %g do not separate in fp32" % (k, tau_max))
+    return levels
+
+
+def deep_tau_bracket(levels, z, flat, depth):
+    """What a deep AOV's samples say about the optical depth in front of `depth` -- what a compositor or a shadow look-up does with them.
+    levels [K], z [K][...] (the planes), flat [...][4] (the flat result of the same call), depth [...] (an image or array, or a scalar).
+    The samples are the knots (z_front, 0), (z[0], L[0]), ..., (z[m - 1], L[m - 1]) of the m finite planes, in depth order, and the total
+    tau, which lies somewhere beyond the last knot.  tau(depth) does not decrease, so between knots j - 1 and j it lies in
+    [tau_lo, tau_hi] = [tau of knot j - 1, tau of knot j]; in front of z_front it is 0; beyond the last knot it lies in [its tau, total].
+    Returns (tau_lo, tau_hi, tau_est) as fp64 arrays of depth's shape: tau_est interpolates linearly in depth between the two knots, and is
+    the total beyond the last one (where the samples do not say how far the medium goes on)."""
+    L = np.asarray(levels, np.float64).reshape(-1)
+    z = np.asarray(z, np.float64)
+    flat = np.asarray(flat, np.float64)
+    if z.shape[0] != L.size or flat.shape[-1] != 4 or z.shape[1:] != flat.shape[:-1]:
+        raise ValueError("deep_tau_bracket: z must be [K][...] and flat [...][4] of the same rays")
+    d = np.broadcast_to(np.asarray(depth, np.float64), z.shape[1:])
+    total = flat[..., 1]
+    knot_t = np.concatenate([flat[..., 2][None], z], axis=0)                               # [K + 1][...], non-decreasing where finite
+    knot_tau = np.concatenate([[0.0], L]).reshape((-1,) + (1,) * d.ndim)
+    finite = np.isfinite(knot_t)
+    m = finite.sum(axis=0)                                                                 # knots a ray has: 0 (saw nothing) .. K + 1
+    j = (finite & (knot_t <= d[None])).sum(axis=0)                                         # knots at or in front of depth
+    take = lambda a, i: np.take_along_axis(np.broadcast_to(a, knot_t.shape), np.clip(i, 0, L.size)[None], axis=0)[0]
+    lo = np.where(j > 0, take(knot_tau, j - 1), 0.0)
+    hi = np.where(j == 0, 0.0, np.where(j < m, take(knot_tau, j), total))
+    t_lo, t_hi = take(knot_t, j - 1), take(knot_t, j)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        w = np.where(t_hi > t_lo, (d - t_lo) / (t_hi - t_lo), 1.0)
+    est = np.where((j > 0) & (j < m), lo + (hi - lo) * np.clip(w, 0.0, 1.0), hi)
+    return lo, hi, est
+
+
 def frame_randoms(n, seed=1337):
     """Per-frame UniformData.random (src/NrcHpmRenderer.cu:308): n x 4 floats in [0,1), seeded (std::mt19937-like role)."""
     rng = np.random.default_rng(seed)

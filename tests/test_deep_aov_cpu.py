@@ -1,0 +1,328 @@
+"""The deep AOV (the depths at which a ray segment reaches given optical depths: include/nrc_hpm.h "Deep AOV", csrc/nrc_view_aov.hpp
+deep_aov_walk_range), the parts that need no GPU: the bit contract (plain walk == walk with jumps == library hook; K = 1 at ln 2 ==
+z_half of the ray AOV; every plane independent of the other levels), the exact per-ray properties, the fp64 reference
+(tests/deep_aov_reference.py), scene.deep_tau_bracket, and the surface with its validation.
+tests/cpp/deep_aov_main.cpp -- its own main, the device-free headers alone, ASan + UBSan without recovery -- is built once and run
+directly; nothing is loaded into Python under a sanitizer."""
+import ctypes as C
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import deep_aov_reference as D
+import ray_aov_reference as Q
+import view_aov_reference as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "nrc-hpm-renderer_amd", "csrc")
+
+
+@pytest.fixture(scope="module")
+def program():
+    build = os.path.join(ROOT, "tests", "cpp", "_build")
+    os.makedirs(build, exist_ok=True)
+    exe = os.path.join(build, "deep_aov_main")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "deep_aov_main.cpp"), "-o", exe])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+
+    def run(*args):
+        r = subprocess.run([exe] + list(args), capture_output=True, text=True, timeout=600, env=env)
+        out = r.stdout + r.stderr
+        assert r.returncode == 0, out[-4000:]
+        assert "AddressSanitizer" not in out and "runtime error" not in out and "FAILED" not in out, out[-4000:]
+        return out
+    return run
+
+
+def program_rays(program, tmp_path, scene, rays, levels):
+    """(planes [K][...], flat [...][4]) of the program's plain deep walk; the program itself fails when its walk with jumps differs in a
+    bit, when the flat result is not the range walk's, or when a level is not emitted exactly once"""
+    nx, ny, nz = scene["dims"]
+    recs = np.ascontiguousarray(rays, np.float32)
+    n, K = recs.size // 8, len(levels)
+    head = struct.pack("<4I", nx, ny, nz, n)
+    floats = np.concatenate([np.asarray(scene["size"], np.float32), [np.float32(scene["density_factor"])]]).astype("<f4")
+    src, rs, lv, dst = (str(tmp_path / f) for f in ("scene.bin", "rays.bin", "levels.bin", "out.bin"))
+    with open(src, "wb") as f:
+        f.write(head + floats.tobytes() + np.ascontiguousarray(scene["density"], np.uint8).tobytes())
+    recs.astype("<f4").tofile(rs)
+    np.asarray(levels, "<f4").tofile(lv)
+    out = program("rays", src, rs, lv, dst)
+    assert " 0 differ between the plain walk and the walk with jumps; 0 flat results differ from the range walk; 0 levels not emitted" in out, out
+    raw = np.fromfile(dst, "<f4")
+    return raw[:K * n].reshape((K,) + recs.shape[:-1]), raw[K * n:].reshape(recs.shape[:-1] + (4,))
+
+
+_HOST = {}
+
+
+def host(api, sc, name, lname):
+    """(planes, flat) of the library's host hook on ray set `name` with level set `lname`, once per session"""
+    if (name, lname) not in _HOST:
+        scene, rays = D.ray_sets(api, sc)[name]
+        z, flat = api.deep_ray_aov_host(scene, rays, D.level_sets(sc)[lname])
+        z.setflags(write=False)
+        flat.setflags(write=False)
+        _HOST[(name, lname)] = (z, flat)
+    return _HOST[(name, lname)]
+
+
+def check_properties(levels, z, flat):
+    """the exact per-ray properties: z[k] finite iff flat.tau >= L[k] (an fp32 compare); finite planes non-decreasing in k; z_front <= z[0];
+    no NaN; a ray that saw nothing has the empty flat result"""
+    L = np.asarray(levels, np.float32)
+    K = L.size
+    z, flat = np.asarray(z).reshape(K, -1), np.asarray(flat).reshape(-1, 4)
+    assert z.dtype == np.float32 and flat.dtype == np.float32
+    assert not np.isnan(z).any() and not np.isnan(flat).any()
+    assert not np.isneginf(z).any()
+    assert (np.isfinite(z) == (flat[None, :, 1] >= L[:, None])).all()
+    for k in range(1, K):
+        fin = np.isfinite(z[k])
+        assert (z[k - 1][fin] <= z[k][fin]).all()
+    fin = np.isfinite(z[0])
+    assert (flat[:, 2][fin] <= z[0][fin]).all()
+    assert Q.is_empty(flat[flat[:, 1] == 0.0]).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1. the bit contract
+@pytest.mark.parametrize("lname", D.LEVEL_SET_NAMES)
+@pytest.mark.parametrize("name", D.SET_NAMES)
+def test_plain_walk_walk_with_jumps_library_and_ray_aov_agree_bitwise(sc, api, program, tmp_path, name, lname):
+    """the sanitized program (g++) and nrc_test_deep_ray_aov_host (the library's host compiler) run the same header: the same bits in every
+    plane and in the flat result; the program has walked every record with the occupancy jumps too; the flat result is
+    nrc_test_ray_aov_host's -- code that existed before the deep AOV -- bit for bit; and the exact properties hold on every ray"""
+    scene, rays = D.ray_sets(api, sc)[name]
+    levels = D.level_sets(sc)[lname]
+    pz, pflat = program_rays(program, tmp_path, scene, rays, levels)
+    z, flat = host(api, sc, name, lname)
+    assert R.same_bits(pz, z) and R.same_bits(pflat, flat)
+    assert R.same_bits(flat, api.test_ray_aov_host(scene, rays))
+    check_properties(levels, z, flat)
+    assert (flat[..., 1] > 0.0).sum() > 100
+    assert np.isfinite(z[0]).sum() > 50
+    if lname == "beyond":
+        assert np.isposinf(z[-1]).all() and flat[..., 1].max() < levels[-1]      # the top level exceeds every ray's tau
+
+
+@pytest.mark.parametrize("name", D.SET_NAMES)
+def test_one_level_at_ln2_is_z_half_of_the_ray_aov(sc, api, name):
+    """against code that exists without the deep AOV: K = 1, {NRC_AOV_LN2} -- the plane is nrc_test_ray_aov_host's z_half, all bits"""
+    scene, rays = D.ray_sets(api, sc)[name]
+    z, _ = host(api, sc, name, "ln2")
+    want = api.test_ray_aov_host(scene, rays)
+    assert R.same_bits(z[0], want[..., 3])
+    assert np.isfinite(z[0]).sum() > 50
+
+
+@pytest.mark.parametrize("name", ("holdout_blocks_v3", "holdout_cloud_v3", "light_cloud_other", "random_blocks", "random_dense", "random_cloud"))
+def test_every_plane_is_independent_of_the_other_levels(sc, api, name):
+    """each plane of the K = 7 call is the K = 1 call on that level, all bits"""
+    scene, rays = D.ray_sets(api, sc)[name]
+    levels = D.level_sets(sc)["k7"]
+    z, flat = host(api, sc, name, "k7")
+    for k in range(levels.size):
+        zk, fk = api.deep_ray_aov_host(scene, rays, levels[k:k + 1])
+        assert R.same_bits(zk[0], z[k]), k
+        assert R.same_bits(fk, flat)
+
+
+def test_degenerate_records_are_empty_and_leave_their_neighbours_alone(sc, api, program, tmp_path):
+    """every degenerate record of the ray AOV's list: +inf in all planes and the empty flat result, from the library and the sanitized program;
+    interleaved with good records, the good records keep the bits they have on their own"""
+    recs, what = Q.degenerate_records()
+    for volume in ("blocks", "cloud"):
+        scene = Q.volume_scene(sc, volume)
+        for lname in ("ln2", "k7", "k32"):
+            levels = D.level_sets(sc)[lname]
+            z, flat = api.deep_ray_aov_host(scene, recs, levels)
+            pz, pflat = program_rays(program, tmp_path, scene, recs, levels)
+            assert R.same_bits(z, pz) and R.same_bits(flat, pflat)
+            bad = [w for w, e, zz in zip(what, Q.is_empty(flat), z.T) if not (e and np.isposinf(zz).all())]
+            assert not bad, bad
+        good = Q.random_segments(scene)[:recs.shape[0]]
+        mixed = np.empty((2 * recs.shape[0], 8), np.float32)
+        mixed[0::2], mixed[1::2] = good, recs
+        levels = D.level_sets(sc)["k7"]
+        zm, fm = api.deep_ray_aov_host(scene, mixed, levels)
+        zg, fg = api.deep_ray_aov_host(scene, good, levels)
+        assert R.same_bits(zm[:, 0::2], zg) and R.same_bits(fm[0::2], fg)
+        assert np.isposinf(zm[:, 1::2]).all() and Q.is_empty(fm[1::2]).all()
+    z, flat = api.deep_ray_aov_host(Q.volume_scene(sc, "cloud"), np.zeros((0, 8), np.float32), [1.0])
+    assert z.shape == (1, 0) and flat.shape == (0, 4)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2. the fp64 reference
+def test_one_dense_voxel_crosses_several_of_the_32_levels(sc, api):
+    """from the fp64 reference alone: with the 32 fine levels some ray of the dense blocks volume reaches two or more levels inside ONE voxel
+    segment -- the inner loop of the rule runs more than once"""
+    ref = D.reference(api, sc, "random_dense")
+    same = ref["same_voxel"][ref["where"]["k32"]]
+    print("rays with two levels of k32 in one voxel: %d; most levels sharing a voxel with their predecessor on one ray: %d"
+          % (same.any(axis=0).sum(), same.sum(axis=0).max()))
+    assert same.any(axis=0).sum() >= 1
+
+
+@pytest.mark.parametrize("lname", D.LEVEL_SET_NAMES)
+@pytest.mark.parametrize("name", D.ACCURACY_SETS)
+def test_planes_against_the_fp64_reference(sc, api, name, lname):
+    """Every finite plane against the fp64 reference of the same fp32 record and level, on the rays the five-ray rule calls stable, within
+    view_aov_reference.tolerances' z_half bound evaluated with the level's own crossing voxel:
+        |d z[k]| <= S_z + tol_tau / sigma_cross + 8 ulp32(z),   tol_tau = S_tau + 8 N sigma_max ulp32(t1) + N ulp32(tau)
+    (the level is reached where the accumulated tau, wrong by at most tol_tau, meets it: a voxel of density sigma_cross turns that into a
+    depth).  The cap, from the reference alone: in EVERY plane of the set at most UNSTABLE_CAP of the hit rays are unstable -- the rule is the ray
+    AOV's, with the plane standing where z_half stands, so each plane is compared on at least 95 % of the rays that see the medium."""
+    scene, _ = D.ray_sets(api, sc)[name]
+    ref = D.reference(api, sc, name)
+    z, _ = host(api, sc, name, lname)
+    sigma_max = float(np.float32(scene["density_factor"]))
+    sl = ref["where"][lname]
+    worst = 0.0
+    per_level = []
+    for a in range(sl.start, sl.stop):
+        lr = D.level_reference(ref, a)
+        per_level.append((lr, R.tolerances(lr, sigma_max)["z_half"]))
+    shares = [R.unstable_share(lr) for lr, _ in per_level]
+    hit = shares[0][1]
+    print("%s / %s: at most %d unstable of %d hit rays in a plane" % (name, lname, max(u for u, _ in shares), hit))
+    assert hit > 100 and all(u <= R.UNSTABLE_CAP * hit for u, _ in shares)
+    for k, (lr, bound) in enumerate(per_level):
+        want = lr["z_half"][..., 0]
+        g = z[k].astype(np.float64)
+        st = lr["stable"]
+        assert (np.isfinite(g) == np.isfinite(want))[st].all(), k
+        m = st & np.isfinite(want)
+        if m.any():
+            err = np.abs(g[m] - want[m])
+            worst = max(worst, float(np.where(err > 0.0, err / np.maximum(bound[m], 1e-300), 0.0).max()))
+    print("%s / %s: largest error-to-bound ratio %.3f" % (name, lname, worst))
+    assert worst <= 1.0
+
+
+# ---------------------------------------------------------------------------------------------------------------- 3. deep_tau_bracket
+@pytest.mark.parametrize("volume", ("blocks", "dense", "cloud"))
+def test_tau_bracket_holds_the_tau_of_the_cut_record(sc, api, volume):
+    """4096 depths uniform in [0, 1.6 |size|] over the random segments and the K = 7 levels: the optical depth in front of the depth -- the
+    ray AOV's tau of the record cut there (t_max = min(t_max, depth): a cut beyond the record's end leaves the record) -- lies in
+    [tau_lo - eps, tau_hi + eps], eps = sigma_max 16 ulp32(depth) + tol_tau (a knot's depth is wrong by a few ulp of itself, and a depth
+    error d moves tau by at most sigma_max d; tol_tau: view_aov_reference.tolerances' bound of a walk's tau, with the spread 0 -- both walks
+    follow the same fp32 ray); the linear estimate is within tau_hi - tau_lo + eps.  No case is excluded."""
+    scene = D.volume_scene(sc, volume)
+    rays = Q.random_segments(scene)
+    levels = D.level_sets(sc)["k7"]
+    z, flat = api.deep_ray_aov_host(scene, rays, levels)
+    rng = np.random.default_rng(23)
+    pick = rng.integers(0, rays.shape[0], 4096)
+    depth = (rng.random(4096) * 1.6 * Q.scene_diagonal(scene)).astype(np.float32)
+    cut = rays[pick].copy()
+    cut[:, 7] = np.minimum(cut[:, 7], depth)
+    tau = api.test_ray_aov_host(scene, cut)[:, 1].astype(np.float64)
+    lo, hi, est = sc.deep_tau_bracket(levels, z[:, pick], flat[pick], depth)
+    assert lo.shape == hi.shape == est.shape == (4096,) and (lo <= hi).all() and (lo <= est).all() and (est <= hi).all()
+    ref = Q.reference_rays(scene, rays, centre_only=True)
+    sigma_max = float(np.float32(scene["density_factor"]))
+    N = ref["crossings"].astype(np.float64)[pick]
+    tol_tau = 8.0 * N * sigma_max * R.ulp32(ref["t1"][pick]) + N * R.ulp32(flat[pick][:, 1])
+    eps = sigma_max * 16.0 * R.ulp32(depth) + tol_tau
+    inside = (tau > 0.0) & (tau < flat[pick][:, 1])
+    print("%s: %d of 4096 cuts inside the medium, %d brackets of positive width; largest excess over the bracket / eps: %.3f" %
+          (volume, inside.sum(), (hi > lo).sum(), float((np.maximum(np.maximum(lo - tau, tau - hi), 0.0) / np.maximum(eps, 1e-300)).max())))
+    assert inside.sum() > 50 and ((hi > lo) & (lo > 0.0)).sum() > 100
+    assert (tau >= lo - eps).all() and (tau <= hi + eps).all()
+    assert (np.abs(est - tau) <= hi - lo + eps).all()
+
+
+def test_deep_levels_are_equally_spaced_in_alpha(sc):
+    for k, tau_max in ((1, 0.7), (4, 3.0), (7, 3.0), (32, 1.6), (32, 8.0)):
+        L = sc.deep_levels(k, tau_max)
+        assert L.dtype == np.float32 and L.shape == (k,) and L[0] > 0.0 and (np.diff(L) > 0.0).all()
+        alpha = -np.expm1(-L.astype(np.float64))
+        np.testing.assert_allclose(alpha, np.arange(1, k + 1) / k * -np.expm1(-tau_max), rtol=1e-6)
+        assert abs(float(L[-1]) - tau_max) <= 1e-6 * tau_max
+    for bad in ((0, 1.0), (33, 1.0), (4, 0.0), (4, float("inf")), (4, float("nan"))):
+        with pytest.raises(ValueError):
+            sc.deep_levels(*bad)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 4. the surface
+NEW_SYMBOLS = ("nrc_renderer_deep_ray_aov", "nrc_mc_renderer_deep_ray_aov", "nrc_renderer_deep_view_aov", "nrc_mc_renderer_deep_view_aov",
+               "nrc_renderer_deep_ortho_aov", "nrc_mc_renderer_deep_ortho_aov", "nrc_test_deep_ray_aov_host")
+
+
+def test_the_new_symbols_exist_in_the_library_the_header_and_the_mirrors(api, sc):
+    L = api.load_library()
+    header = open(os.path.join(ROOT, "include", "nrc_hpm.h")).read()
+    hpp = open(os.path.join(ROOT, "include", "nrc_hpm.hpp")).read()
+    assert "Deep AOV" in header
+    for s in NEW_SYMBOLS:
+        assert hasattr(L, s) and s in api.ABI_SYMBOLS and s + "(" in header, s
+    for cls in (api.NrcHpmRenderer, api.McHpmRenderer):
+        assert callable(cls.DeepRayAov) and callable(cls.DeepViewAov) and callable(cls.DeepOrthoAov)
+    assert callable(api.deep_ray_aov_host) and callable(sc.deep_levels) and callable(sc.deep_tau_bracket)
+    for name in ("DeepRayAov", "DeepViewAov", "DeepOrthoAov"):
+        assert hpp.count("void " + name + "(") == 2, name
+    kernels = open(os.path.join(CSRC, "nrc_integrator.hip")).read()
+    assert "k_deep_aov" in kernels and "deep_aov_walk_range(" in kernels
+
+
+def test_bad_levels_and_null_arguments_are_refused_without_a_device(api, sc):
+    """n_levels == 0 or > 32; levels not strictly ascending, not finite or <= 0; NULL levels or planes; NULL rays with n > 0:
+    NRC_ERR_INVALID (-1) with a message -- through the host hook, which shares the entry points' check, and with a NULL renderer"""
+    L = api.load_library()
+    scene = Q.volume_scene(sc, "blocks")
+    c_scene = api.make_c_scene(scene)
+    rays = np.ascontiguousarray(Q.random_segments(scene)[:4])
+    z = np.full((33, 4), 7.0, np.float32)
+    flat = np.full((4, 4), 7.0, np.float32)
+
+    def call(n, rays_p, levels, z_p=z.ctypes.data, k=None):
+        lv = np.asarray(levels, np.float32) if levels is not None else None
+        return L.nrc_test_deep_ray_aov_host(C.byref(c_scene), C.c_size_t(n), rays_p, C.c_uint32(len(levels) if k is None else k),
+                                            lv.ctypes.data if lv is not None else None, z_p, flat.ctypes.data)
+    inf, nan = np.inf, np.nan
+    bad_levels = ([], list(np.linspace(0.1, 3.0, 33)), [1.0, 1.0], [2.0, 1.0], [0.5, 1.0, 0.75], [0.0, 1.0], [-1.0, 1.0], [-0.0], [inf], [1.0, inf],
+                  [nan], [0.5, nan, 1.0], [-inf, 1.0])
+    for levels in bad_levels:
+        assert call(4, rays.ctypes.data, levels) == -1, levels
+        assert b"deep AOV" in L.nrc_last_error(), levels
+        assert call(0, None, levels) == -1, levels                              # (the levels are checked before "no rays is no work")
+    assert call(4, rays.ctypes.data, None, k=3) == -1 and b"levels is NULL" in L.nrc_last_error()
+    assert call(4, rays.ctypes.data, [1.0], z_p=None) == -1 and b"d_z" in L.nrc_last_error()
+    assert call(4, None, [1.0]) == -1 and b"null argument" in L.nrc_last_error()
+    assert (z == 7.0).all() and (flat == 7.0).all()                              # nothing was written by a refused call
+    assert call(0, None, [1.0]) == 0
+    assert call(4, rays.ctypes.data, list(np.linspace(0.1, 3.0, 32))) == 0
+    lv = np.array([1.0], np.float32)
+    for fn in (L.nrc_renderer_deep_ray_aov, L.nrc_mc_renderer_deep_ray_aov):
+        assert fn(None, 0, None, 1, lv.ctypes.data, z.ctypes.data, None) == -1
+    for fn in (L.nrc_renderer_deep_view_aov, L.nrc_mc_renderer_deep_view_aov):
+        assert fn(None, None, 1, lv.ctypes.data, z.ctypes.data, None) == -1
+    for fn in (L.nrc_renderer_deep_ortho_aov, L.nrc_mc_renderer_deep_ortho_aov):
+        assert fn(None, None, 4, 4, 1, lv.ctypes.data, z.ctypes.data, None) == -1
+
+
+def test_the_header_states_the_deep_rule_once_and_stays_device_free():
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-include", "nrc_view_aov.hpp", "-x", "c++", os.devnull],
+                       capture_output=True, text=True, cwd=CSRC)
+    assert r.returncode == 0, r.stderr[-4000:]
+    code = open(os.path.join(CSRC, "nrc_view_aov.hpp")).read()
+    assert "hip_runtime" not in code and "__global__" not in code and "threadIdx" not in code
+    assert code.count("sink->emit(next,") == 1 and code.count("deep_aov_walk_range(") == 1
+
+
+def test_cli_deep_argument_rules_and_channel_names():
+    import argparse
+    from nrc_hpm_renderer_amd import cli
+    ok = dict(aov=True, export="out.exr", gpus=1, shadow_map=None, shadow_size=512, holdout_sphere=None, deep=4)
+    cli.check_deep_args(argparse.Namespace(export=None, gpus=1))                  # (a namespace without the flag)
+    cli.check_deep_args(argparse.Namespace(**ok))
+    cli.check_deep_args(argparse.Namespace(**dict(ok, aov=False, export=None, shadow_map="s.exr")))
+    for bad in (dict(ok, deep=0), dict(ok, deep=33), dict(ok, deep=-1), dict(ok, aov=False), dict(ok, export="out_%04d.exr")):
+        with pytest.raises(SystemExit):
+            cli.check_deep_args(argparse.Namespace(**bad))
+    planes = cli.deep_planes(np.arange(24, dtype=np.float32).reshape(3, 2, 4))
+    assert list(planes) == ["Zd00", "Zd01", "Zd02"] and planes["Zd01"][1, 2] == 14.0
