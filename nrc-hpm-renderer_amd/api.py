@@ -580,82 +580,76 @@ class _LiveMedium:
         else:
             _check(self._medium("set_path_aov_depths")(self.h, _dev_ptr(depths), C.c_uint32(int(depths.shape[0]) if views is None else int(views))))
 
+    def _aov(self, what, source, arg, levels=None, out=None, flat=None):
+        """What the ray AOV's and the deep AOV's methods share.  source / arg: "rays" / the [n][8] tensor, "depth" / the view's depth image
+        (None: whole rays, the deep call only) or "ortho" / (view, w, h); it sets the rays' shape and the head of the C call.
+        levels None: the flat call, the result [*shape][4] in `out` or a new tensor.  Otherwise the deep call nrc_*_deep_*: the planes
+        [K][*shape] in `out` or a new tensor, and (planes, flat) when a flat result is asked for."""
+        import torch
+        deep = levels is not None
+        if source == "rays":
+            if not isinstance(arg, torch.Tensor) or arg.dim() != 2:
+                raise ValueError("%s: rays must be a contiguous float32 CUDA tensor of shape (n, 8)" % what)
+            _check_device_floats(what + ": rays", arg, (arg.shape[0], 8))
+            shape = (int(arg.shape[0]),)
+            name, head = "ray_aov", (C.c_size_t(shape[0]), _dev_ptr(arg))
+        elif source == "depth":
+            shape = (self.height, self.width)
+            if arg is not None or not deep:
+                _check_device_floats(what + ": depth", arg, shape)
+            name, head = ("view_aov" if deep else "view_aov_to_depth"), (_dev_ptr(arg) if arg is not None else None,)
+        else:
+            view, w, h = arg[0], int(arg[1]), int(arg[2])
+            if w <= 0 or h <= 0:
+                raise ValueError("%s: the image size must be positive" % what)
+            v = make_c_ortho_view(view)
+            shape = (h, w)
+            name, head = "ortho_aov", (C.byref(v), C.c_uint32(w), C.c_uint32(h))
+        if not deep:
+            out = _aov_out(what, out, shape + (4,))
+            _check(self._medium(name)(self.h, *head, _dev_ptr(out)))
+            return out
+        lv, k = _deep_levels_arg(levels)
+        out = _aov_out(what, out, (k,) + shape)
+        flat = _deep_flat(what, flat, shape + (4,))
+        if shape[0] != 0:      # (no rays, no work -- and an empty tensor has no address for the library's NULL check)
+            _check(self._medium("deep_" + name)(self.h, *head, C.c_uint32(k), lv.ctypes.data_as(C.c_void_p), _dev_ptr(out),
+                                                _dev_ptr(flat) if flat is not None else None))
+        return out if flat is None else (out, flat)
+
     def RayAov(self, rays, out=None):
         """the ray AOV of a list of segments through the current medium (include/nrc_hpm.h, "Ray AOV"; nrc_renderer_ray_aov): rays is a
         contiguous float32 CUDA tensor [n][8] of {ox, oy, oz, t_min, dx, dy, dz, t_max}, the result [n][4] of {alpha, tau, z_front, z_half}
         (`out`, or a new tensor).  One launch on the renderer's stream, no host wait."""
-        import torch
-        if not isinstance(rays, torch.Tensor) or rays.dim() != 2:
-            raise ValueError("RayAov: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
-        _check_device_floats("RayAov: rays", rays, (rays.shape[0], 8))
-        out = _aov_out("RayAov", out, (rays.shape[0], 4))
-        _check(self._medium("ray_aov")(self.h, C.c_size_t(int(rays.shape[0])), _dev_ptr(rays), _dev_ptr(out)))
-        return out
+        return self._aov("RayAov", "rays", rays, out=out)
 
     def ViewAovToDepth(self, depth, out=None):
         """the view AOV held out to a depth image (nrc_renderer_view_aov_to_depth): depth is a contiguous float32 CUDA tensor
         [height][width], the distance along each pixel's camera ray (the unit of z_front) at which the ray ends; +inf gives ViewAov()'s
         bits, a depth <= 0 or NaN the empty result.  Returns [height][width][4] (`out`, or a new tensor)."""
-        _check_device_floats("ViewAovToDepth: depth", depth, (self.height, self.width))
-        out = _aov_out("ViewAovToDepth", out, (self.height, self.width, 4))
-        _check(self._medium("view_aov_to_depth")(self.h, _dev_ptr(depth), _dev_ptr(out)))
-        return out
+        return self._aov("ViewAovToDepth", "depth", depth, out=out)
 
     def OrthoAov(self, view, w, h, out=None):
         """the ray AOV of an orthographic view {origin, du, dv, dir} (scene.light_view: the medium's shadow map) of w x h pixels, whatever
         the renderer's size (nrc_renderer_ortho_aov).  Returns [h][w][4] (`out`, or a new tensor)."""
-        w, h = int(w), int(h)
-        if w <= 0 or h <= 0:
-            raise ValueError("OrthoAov: the image size must be positive")
-        v = make_c_ortho_view(view)
-        out = _aov_out("OrthoAov", out, (h, w, 4))
-        _check(self._medium("ortho_aov")(self.h, C.byref(v), C.c_uint32(w), C.c_uint32(h), _dev_ptr(out)))
-        return out
+        return self._aov("OrthoAov", "ortho", (view, w, h), out=out)
 
     def DeepRayAov(self, rays, levels, out=None, flat=None):
         """the deep AOV of a list of segments (include/nrc_hpm.h, "Deep AOV"; nrc_renderer_deep_ray_aov): rays as for RayAov, levels the
         K optical depths (scene.deep_levels; ascending, positive, K <= 32).  Returns the planes [K][n] -- z[k][i]: the ray parameter at which
         ray i reaches levels[k], +inf where it never does -- in `out` or a new tensor.  flat: None, True (a new tensor) or a tensor [n][4]
         that receives RayAov's result of the same walk; with it the return value is (planes, flat).  One launch, no host wait."""
-        import torch
-        if not isinstance(rays, torch.Tensor) or rays.dim() != 2:
-            raise ValueError("DeepRayAov: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
-        _check_device_floats("DeepRayAov: rays", rays, (rays.shape[0], 8))
-        n = int(rays.shape[0])
-        lv, k = _deep_levels_arg(levels)
-        out = _aov_out("DeepRayAov", out, (k, n))
-        flat = _deep_flat("DeepRayAov", flat, (n, 4))
-        if n == 0:      # (no rays, no work -- and an empty tensor has no address for the library's NULL check)
-            return out if flat is None else (out, flat)
-        _check(self._medium("deep_ray_aov")(self.h, C.c_size_t(n), _dev_ptr(rays), C.c_uint32(k), lv.ctypes.data_as(C.c_void_p), _dev_ptr(out),
-                                            _dev_ptr(flat) if flat is not None else None))
-        return out if flat is None else (out, flat)
+        return self._aov("DeepRayAov", "rays", rays, levels, out, flat)
 
     def DeepViewAov(self, levels, depth=None, out=None, flat=None):
         """the deep AOV of every pixel's camera ray (nrc_renderer_deep_view_aov): a deep image's samples, planes [K][height][width].
         depth: None (whole rays) or a depth image as for ViewAovToDepth.  flat as for DeepRayAov, [height][width][4]."""
-        if depth is not None:
-            _check_device_floats("DeepViewAov: depth", depth, (self.height, self.width))
-        lv, k = _deep_levels_arg(levels)
-        out = _aov_out("DeepViewAov", out, (k, self.height, self.width))
-        flat = _deep_flat("DeepViewAov", flat, (self.height, self.width, 4))
-        _check(self._medium("deep_view_aov")(self.h, _dev_ptr(depth) if depth is not None else None, C.c_uint32(k), lv.ctypes.data_as(C.c_void_p),
-                                             _dev_ptr(out), _dev_ptr(flat) if flat is not None else None))
-        return out if flat is None else (out, flat)
+        return self._aov("DeepViewAov", "depth", depth, levels, out, flat)
 
     def DeepOrthoAov(self, view, w, h, levels, out=None, flat=None):
         """the deep AOV of an orthographic view (scene.light_view): a deep shadow map, planes [K][h][w] (nrc_renderer_deep_ortho_aov).
         flat as for DeepRayAov, [h][w][4]."""
-        w, h = int(w), int(h)
-        if w <= 0 or h <= 0:
-            raise ValueError("DeepOrthoAov: the image size must be positive")
-        v = make_c_ortho_view(view)
-        lv, k = _deep_levels_arg(levels)
-        out = _aov_out("DeepOrthoAov", out, (k, h, w))
-        flat = _deep_flat("DeepOrthoAov", flat, (h, w, 4))
-        _check(self._medium("deep_ortho_aov")(self.h, C.byref(v), C.c_uint32(w), C.c_uint32(h), C.c_uint32(k), lv.ctypes.data_as(C.c_void_p),
-                                              _dev_ptr(out), _dev_ptr(flat) if flat is not None else None))
-        return out if flat is None else (out, flat)
+        return self._aov("DeepOrthoAov", "ortho", (view, w, h), levels, out, flat)
 
     def ExportImageWithAovToFile(self, filePath):
         """ExportOutputImageToFile with the view AOV beside the colours: a scan-line EXR with FLOAT channels A (alpha of the AOV), B, G, R,

@@ -1128,7 +1128,7 @@ struct ViewDepth {
         const uint32_t gx = global_x(fr, ln.lx);
         *r = view_aov_camera_ray(cam.m, cam.pos, (float)gx * fr.inv_gw, (float)ln.y * fr.inv_gh);      // k_view_aov's ray
         *t_min = 0.0f;
-        *t_max = depth[ln.at];
+        *t_max = depth != nullptr ? depth[ln.at] : NRC_AOV_INF;      // (null: every pixel's whole ray)
     }
 };
 // an orthographic image of w x h pixels, its size the caller's: one 8x8 pixel tile per wave in row-major tile order, so that a wave's
@@ -1158,8 +1158,29 @@ struct OrthoView {
         *t_max = NRC_AOV_INF;
     }
 };
-template <typename Src>
-__global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK) void k_ray_aov(DevScene sc, Src src)
+// ------------------------------------------------------------------------------------------------ the deep AOV (nrc_view_aov.hpp, deep_aov_walk_range)
+// The depths at which a ray reaches the caller's K optical depths, in the one walk that also forms the flat result: the same kernel over
+// the same three sources with another OUTPUT -- FlatOut: the four numbers alone, to the source's `out`; DeepOut: the header's deep sum in
+// the walk (a source's `out` is the flat image there, and may be null).
+//   output   planar: level k of ray i at z[k * n + i], so the 64 stores a wave makes of one level are neighbours.  A lane stores z[k] when
+//            it crosses level k (the sum keeps no depth: K registers would not fit) and +inf to the planes it never reached after the walk.
+//   levels   the same for every ray, but `next` is the lane's own: they come by value in the kernel arguments and every wave copies them to
+//            its own 128 bytes of LDS (beside the 8 KB table and the 1 KB log table), where a per-lane index costs neither scratch nor K
+//            registers.  The copy is the wave's own -- a wave fence, no workgroup barrier, as for the table.
+//   rejected a wave whose tile the mask rejects stores +inf to all K planes (and the empty flat result) and is gone before either copy.
+struct AovLevels { float v[kAovDeepMaxLevels]; };
+struct FlatOut {
+    static constexpr bool deep = false;
+};
+struct DeepOut {
+    static constexpr bool deep = true;
+    float* __restrict__ z;
+    size_t n;                // rays: the stride of a plane
+    uint32_t n_levels;
+    AovLevels levels;        // (those beyond n_levels: 0, never read by the walk)
+};
+template <typename Src, typename Out>
+__global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK) void k_ray_aov(DevScene sc, Src src, Out o)
 {
     if (!((NRC_DIAG_LOWPRIO) & 8) && src.raise != 0u) __builtin_amdgcn_s_setprio(NRC_WAVE_PRIORITY);      // camera_wave_priority
     __shared__ uint32_t s_occ[kOccMaxWords];
@@ -1167,8 +1188,21 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK) void k_ray_aov(DevScen
     const bool inside = src.lane(&ln);
     if (__ballot(inside) == 0ull) return;      // a wave beyond the rays
     if (src.rejected(ln)) {
-        if (inside) src.out[ln.at] = make_float4(0.0f, 0.0f, NRC_AOV_INF, NRC_AOV_INF);
+        if (inside) {
+            if constexpr (Out::deep)
+                for (uint32_t k = 0; k < o.n_levels; k++) o.z[(size_t)k * o.n + ln.at] = NRC_AOV_INF;
+            if (!Out::deep || src.out != nullptr) src.out[ln.at] = make_float4(0.0f, 0.0f, NRC_AOV_INF, NRC_AOV_INF);
+        }
         return;
+    }
+    float* levels = nullptr;
+    if constexpr (Out::deep) {
+        __shared__ float s_levels[CAMERA_WAVES_PER_BLOCK][kAovDeepMaxLevels];
+        levels = s_levels[threadIdx.x >> 6];
+        if ((threadIdx.x & 63u) < kAovDeepMaxLevels) levels[threadIdx.x & 63u] = o.levels.v[threadIdx.x & 63u];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
     const uint32_t* occ = load_occupancy_per_wave(sc, s_occ);
     if (!inside) return;
@@ -1177,72 +1211,16 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK) void k_ray_aov(DevScen
     src.ray(ln, &ray, &t_min, &t_max);
     const AovGrid g{sc.nx, sc.ny, sc.nz, {sc.size[0], sc.size[1], sc.size[2]}, sc.density_factor, sc.occ_shift, sc.occ_gx, sc.occ_gy};
     const AovDensity den{__builtin_amdgcn_make_buffer_rsrc((void*)sc.density, 0, (int)(sc.nx * sc.ny * sc.nz), 0x00020000), sc.nx, sc.ny};
-    const ViewAov r = occ != nullptr ? view_aov_walk_range(g, ray, t_min, t_max, den, AovOccupancyBits{occ})
-                                     : view_aov_walk_range(g, ray, t_min, t_max, den, NoOccupancy{});
-    src.out[ln.at] = make_float4(r.alpha, r.tau, r.z_front, r.z_half);
-}
-
-// ------------------------------------------------------------------------------------------------ the deep AOV (nrc_view_aov.hpp, deep_aov_walk_range)
-// The depths at which a ray reaches the caller's K optical depths, in the one walk that also forms the flat result: k_ray_aov's kernel
-// over the same three sources (a source's `out` is the flat image here, and may be null), with the header's deep sum in the walk.
-//   output   planar: level k of ray i at z[k * n + i], so the 64 stores a wave makes of one level are neighbours.  A lane stores z[k] when
-//            it crosses level k (the sum keeps no depth: K registers would not fit) and +inf to the planes it never reached after the walk.
-//   levels   the same for every ray, but `next` is the lane's own: they come by value in the kernel arguments and every wave copies them to
-//            its own 128 bytes of LDS (beside the 8 KB table and the 1 KB log table), where a per-lane index costs neither scratch nor K
-//            registers.  The copy is the wave's own -- a wave fence, no workgroup barrier, as for the table.
-//   rejected a wave whose tile the mask rejects stores +inf to all K planes (and the empty flat result) and is gone before either copy.
-struct AovLevels { float v[kAovDeepMaxLevels]; };
-struct DeepOut {
-    float* __restrict__ z;
-    size_t n;                // rays: the stride of a plane
-    uint32_t n_levels;
-    AovLevels levels;        // (those beyond n_levels: 0, never read by the walk)
-};
-// the lane's ray and range: the source's, but the view's depth image is optional here -- null: every pixel's whole ray
-template <typename Src>
-__device__ __forceinline__ void deep_aov_ray(const Src& src, const typename Src::Lane& ln, AovRay* r, float* t_min, float* t_max)
-{
-    src.ray(ln, r, t_min, t_max);
-}
-__device__ __forceinline__ void deep_aov_ray(const ViewDepth& src, const ViewDepthLane& ln, AovRay* r, float* t_min, float* t_max)
-{
-    const uint32_t gx = global_x(src.fr, ln.lx);
-    *r = view_aov_camera_ray(src.cam.m, src.cam.pos, (float)gx * src.fr.inv_gw, (float)ln.y * src.fr.inv_gh);      // k_view_aov's ray
-    *t_min = 0.0f;
-    *t_max = src.depth != nullptr ? src.depth[ln.at] : NRC_AOV_INF;
-}
-template <typename Src>
-__global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK) void k_deep_aov(DevScene sc, Src src, DeepOut deep)
-{
-    if (!((NRC_DIAG_LOWPRIO) & 8) && src.raise != 0u) __builtin_amdgcn_s_setprio(NRC_WAVE_PRIORITY);      // camera_wave_priority
-    __shared__ uint32_t s_occ[kOccMaxWords];
-    __shared__ float s_levels[CAMERA_WAVES_PER_BLOCK][kAovDeepMaxLevels];
-    typename Src::Lane ln;
-    const bool inside = src.lane(&ln);
-    if (__ballot(inside) == 0ull) return;      // a wave beyond the rays
-    if (src.rejected(ln)) {
-        if (inside) {
-            for (uint32_t k = 0; k < deep.n_levels; k++) deep.z[(size_t)k * deep.n + ln.at] = NRC_AOV_INF;
-            if (src.out != nullptr) src.out[ln.at] = make_float4(0.0f, 0.0f, NRC_AOV_INF, NRC_AOV_INF);
-        }
-        return;
+    ViewAov r;
+    if constexpr (Out::deep) {
+        AovDeepArray sink{o.z + ln.at, o.n};
+        r = occ != nullptr ? deep_aov_walk_range(g, ray, t_min, t_max, den, AovOccupancyBits{occ}, levels, o.n_levels, &sink)
+                           : deep_aov_walk_range(g, ray, t_min, t_max, den, NoOccupancy{}, levels, o.n_levels, &sink);
+    } else {
+        r = occ != nullptr ? view_aov_walk_range(g, ray, t_min, t_max, den, AovOccupancyBits{occ})
+                           : view_aov_walk_range(g, ray, t_min, t_max, den, NoOccupancy{});
     }
-    float* levels = s_levels[threadIdx.x >> 6];
-    if ((threadIdx.x & 63u) < kAovDeepMaxLevels) levels[threadIdx.x & 63u] = deep.levels.v[threadIdx.x & 63u];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const uint32_t* occ = load_occupancy_per_wave(sc, s_occ);
-    if (!inside) return;
-    AovRay ray;
-    float t_min, t_max;
-    deep_aov_ray(src, ln, &ray, &t_min, &t_max);
-    const AovGrid g{sc.nx, sc.ny, sc.nz, {sc.size[0], sc.size[1], sc.size[2]}, sc.density_factor, sc.occ_shift, sc.occ_gx, sc.occ_gy};
-    const AovDensity den{__builtin_amdgcn_make_buffer_rsrc((void*)sc.density, 0, (int)(sc.nx * sc.ny * sc.nz), 0x00020000), sc.nx, sc.ny};
-    AovDeepArray sink{deep.z + ln.at, deep.n};
-    const ViewAov r = occ != nullptr ? deep_aov_walk_range(g, ray, t_min, t_max, den, AovOccupancyBits{occ}, levels, deep.n_levels, &sink)
-                                     : deep_aov_walk_range(g, ray, t_min, t_max, den, NoOccupancy{}, levels, deep.n_levels, &sink);
-    if (src.out != nullptr) src.out[ln.at] = make_float4(r.alpha, r.tau, r.z_front, r.z_half);
+    if (!Out::deep || src.out != nullptr) src.out[ln.at] = make_float4(r.alpha, r.tau, r.z_front, r.z_half);
 }
 
 // ------------------------------------------------------------------------------------------------ nrc/gen_rays.comp + prep_infer_rays.comp
@@ -2549,94 +2527,70 @@ void launch_gen_rays(const DevScene& sc, const DevCamera& cam, const DevFrame& f
     NRC_HIP(hipGetLastError());
 }
 
+static uint32_t ray_aov_raise(const DevFrame& fr) { return (g_host_raise_wave_priority != 0 && fr.camera_priority_low == 0u) ? 1u : 0u; }
+// the frame of the AOV kernels: the view's geometry and mask; the default tile order, no hot tiles, no cost samples
+static DevFrame aov_frame(const DevFrame& fr)
+{
+    DevFrame fa = fr;
+    fa.tile_order = nullptr;
+    fa.tile_cost = nullptr;
+    fa.hot_front = fa.hot_n = 0u;
+    fa.raise_priority = ray_aov_raise(fr);
+    return fa;
+}
 void launch_view_aov(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, float* out, hipStream_t s)
 {
-    DevFrame fa = fr;      // the view's geometry and mask; the default tile order, no hot tiles, no cost samples
-    fa.tile_order = nullptr;
-    fa.tile_cost = nullptr;
-    fa.hot_front = fa.hot_n = 0u;
-    fa.raise_priority = (g_host_raise_wave_priority != 0 && fr.camera_priority_low == 0u) ? 1u : 0u;
-    hipLaunchKernelGGL(k_view_aov, wave_tile_grid(fr.w, fr.h), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc, cam, fa, (float4*)out);
+    hipLaunchKernelGGL(k_view_aov, wave_tile_grid(fr.w, fr.h), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc, cam, aov_frame(fr), (float4*)out);
     NRC_HIP(hipGetLastError());
 }
 
-// the ray AOV's three sources; fr: the renderer's frame -- the view's geometry and mask for the depth source, the priority switch for all
-static uint32_t ray_aov_raise(const DevFrame& fr) { return (g_host_raise_wave_priority != 0 && fr.camera_priority_low == 0u) ? 1u : 0u; }
-void launch_ray_aov_list(const DevScene& sc, const DevFrame& fr, size_t n, const float* rays, float* out, hipStream_t s)
+// the ray and the deep AOV.  A launcher per source owns that source's checks and grid; the launch itself is the same for all of them.
+// fr: the renderer's frame -- the view's geometry and mask for the depth source, the priority switch for all
+template <class Src, class Out>
+static void launch_ray_aov(const DevScene& sc, dim3 grid, const Src& src, const Out& out, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_ray_aov<Src, Out>), grid, dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc, src, out);
+    NRC_HIP(hipGetLastError());
+}
+// n: the source's rays (the stride of a deep plane); deep: null for the flat result alone, which then goes to src.out
+template <class Src>
+static void launch_ray_aov(const DevScene& sc, dim3 grid, const Src& src, size_t n, const AovPlanes* deep, hipStream_t s)
+{
+    if (deep == nullptr) {
+        if (((uintptr_t)src.out) & 15u) fail("ray AOV: out must be 16-byte aligned");
+        return launch_ray_aov(sc, grid, src, FlatOut{}, s);
+    }
+    if (deep->n_levels == 0u || deep->n_levels > kAovDeepMaxLevels) fail("deep AOV: the number of levels must be 1 .. 32");
+    if (((uintptr_t)src.out) & 15u) fail("deep AOV: flat must be 16-byte aligned");
+    DeepOut d{deep->z, n, deep->n_levels, {}};
+    for (uint32_t k = 0; k < deep->n_levels; k++) d.levels.v[k] = deep->levels[k];
+    launch_ray_aov(sc, grid, src, d, s);
+}
+static std::string aov_name(const AovPlanes* deep) { return deep != nullptr ? "deep AOV" : "ray AOV"; }
+
+void launch_ray_aov_list(const DevScene& sc, const DevFrame& fr, size_t n, const float* rays, float* out, const AovPlanes* deep, hipStream_t s)
 {
     const size_t blocks = (n + 64u * CAMERA_WAVES_PER_BLOCK - 1u) / (64u * CAMERA_WAVES_PER_BLOCK);
     if (blocks == 0u) return;
-    if (blocks > 0x7fffffffull) fail("ray AOV: too many rays for one launch");
-    if ((((uintptr_t)rays) | ((uintptr_t)out)) & 15u) fail("ray AOV: rays and out must be 16-byte aligned");
-    hipLaunchKernelGGL(k_ray_aov<RayList>, dim3((uint32_t)blocks), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,
-                       RayList{(const float4*)rays, (float4*)out, n, ray_aov_raise(fr)});
-    NRC_HIP(hipGetLastError());
+    if (blocks > 0x7fffffffull) fail(aov_name(deep) + ": too many rays for one launch");
+    if (deep == nullptr) {
+        if ((((uintptr_t)rays) | ((uintptr_t)out)) & 15u) fail("ray AOV: rays and out must be 16-byte aligned");
+    } else if (((uintptr_t)rays) & 15u) fail("deep AOV: rays must be 16-byte aligned");
+    launch_ray_aov(sc, dim3((uint32_t)blocks), RayList{(const float4*)rays, (float4*)out, n, ray_aov_raise(fr)}, n, deep, s);
 }
-void launch_ray_aov_view_depth(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const float* depth, float* out, hipStream_t s)
+void launch_ray_aov_view_depth(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const float* depth, float* out, const AovPlanes* deep,
+                               hipStream_t s)
 {
-    DevFrame fa = fr;      // as for launch_view_aov: the default tile order, no hot tiles, no cost samples
-    fa.tile_order = nullptr;
-    fa.tile_cost = nullptr;
-    fa.hot_front = fa.hot_n = 0u;
-    if (((uintptr_t)out) & 15u) fail("ray AOV: out must be 16-byte aligned");
-    hipLaunchKernelGGL(k_ray_aov<ViewDepth>, wave_tile_grid(fr.w, fr.h), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,
-                       ViewDepth{cam, fa, depth, (float4*)out, ray_aov_raise(fr)});
-    NRC_HIP(hipGetLastError());
+    launch_ray_aov(sc, wave_tile_grid(fr.w, fr.h), ViewDepth{cam, aov_frame(fr), depth, (float4*)out, ray_aov_raise(fr)}, (size_t)fr.w * fr.h, deep, s);
 }
-void launch_ray_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrthoView& view, uint32_t w, uint32_t h, float* out, hipStream_t s)
+void launch_ray_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrthoView& view, uint32_t w, uint32_t h, float* out, const AovPlanes* deep,
+                          hipStream_t s)
 {
     if (w == 0u || h == 0u) return;
     const uint64_t tiles = (uint64_t)ceil_div(w, 8) * ceil_div(h, 8);
     const uint64_t blocks = (tiles + CAMERA_WAVES_PER_BLOCK - 1u) / CAMERA_WAVES_PER_BLOCK;
-    if (tiles > 0x7fffffffull) fail("ray AOV: the orthographic view is too large for one launch");      // (the kernel numbers its tiles in 32 bits)
-    if (((uintptr_t)out) & 15u) fail("ray AOV: out must be 16-byte aligned");
-    hipLaunchKernelGGL(k_ray_aov<OrthoView>, dim3((uint32_t)blocks), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,
-                       OrthoView{view, w, h, (float4*)out, ray_aov_raise(fr)});
-    NRC_HIP(hipGetLastError());
-}
-
-// the deep AOV over the same three sources; levels: n_levels host floats the caller has checked (deep_aov_levels_error); z: [n_levels][rays];
-// flat: null, or the rays' flat results
-static DeepOut deep_out(float* z, size_t n, uint32_t n_levels, const float* levels, const float* flat)
-{
-    if (n_levels == 0u || n_levels > kAovDeepMaxLevels) fail("deep AOV: the number of levels must be 1 .. 32");
-    if (((uintptr_t)flat) & 15u) fail("deep AOV: flat must be 16-byte aligned");
-    DeepOut d{z, n, n_levels, {}};
-    for (uint32_t k = 0; k < n_levels; k++) d.levels.v[k] = levels[k];
-    return d;
-}
-void launch_deep_aov_list(const DevScene& sc, const DevFrame& fr, size_t n, const float* rays, uint32_t n_levels, const float* levels, float* z,
-                          float* flat, hipStream_t s)
-{
-    const size_t blocks = (n + 64u * CAMERA_WAVES_PER_BLOCK - 1u) / (64u * CAMERA_WAVES_PER_BLOCK);
-    if (blocks == 0u) return;
-    if (blocks > 0x7fffffffull) fail("deep AOV: too many rays for one launch");
-    if (((uintptr_t)rays) & 15u) fail("deep AOV: rays must be 16-byte aligned");
-    hipLaunchKernelGGL(k_deep_aov<RayList>, dim3((uint32_t)blocks), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,
-                       RayList{(const float4*)rays, (float4*)flat, n, ray_aov_raise(fr)}, deep_out(z, n, n_levels, levels, flat));
-    NRC_HIP(hipGetLastError());
-}
-void launch_deep_aov_view_depth(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const float* depth, uint32_t n_levels,
-                                const float* levels, float* z, float* flat, hipStream_t s)
-{
-    DevFrame fa = fr;      // as for launch_view_aov: the default tile order, no hot tiles, no cost samples
-    fa.tile_order = nullptr;
-    fa.tile_cost = nullptr;
-    fa.hot_front = fa.hot_n = 0u;
-    hipLaunchKernelGGL(k_deep_aov<ViewDepth>, wave_tile_grid(fr.w, fr.h), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,
-                       ViewDepth{cam, fa, depth, (float4*)flat, ray_aov_raise(fr)}, deep_out(z, (size_t)fr.w * fr.h, n_levels, levels, flat));
-    NRC_HIP(hipGetLastError());
-}
-void launch_deep_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrthoView& view, uint32_t w, uint32_t h, uint32_t n_levels,
-                           const float* levels, float* z, float* flat, hipStream_t s)
-{
-    if (w == 0u || h == 0u) return;
-    const uint64_t tiles = (uint64_t)ceil_div(w, 8) * ceil_div(h, 8);
-    const uint64_t blocks = (tiles + CAMERA_WAVES_PER_BLOCK - 1u) / CAMERA_WAVES_PER_BLOCK;
-    if (tiles > 0x7fffffffull) fail("deep AOV: the orthographic view is too large for one launch");      // (the kernel numbers its tiles in 32 bits)
-    hipLaunchKernelGGL(k_deep_aov<OrthoView>, dim3((uint32_t)blocks), dim3(64 * CAMERA_WAVES_PER_BLOCK), 0, s, sc,
-                       OrthoView{view, w, h, (float4*)flat, ray_aov_raise(fr)}, deep_out(z, (size_t)w * h, n_levels, levels, flat));
-    NRC_HIP(hipGetLastError());
+    if (tiles > 0x7fffffffull) fail(aov_name(deep) + ": the orthographic view is too large for one launch");      // (the kernel numbers its tiles in 32 bits)
+    launch_ray_aov(sc, dim3((uint32_t)blocks), OrthoView{view, w, h, (float4*)out, ray_aov_raise(fr)}, (size_t)w * h, deep, s);
 }
 
 uint32_t camera_slots(uint32_t w, uint32_t h) { return camera_row_blocks(w) * CAMERA_WAVES_PER_BLOCK * ceil_div(h, 8); }

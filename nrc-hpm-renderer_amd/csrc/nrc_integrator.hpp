@@ -181,20 +181,14 @@ void launch_mc_render(const DevScene& sc, const DevCamera& cam, const DevFrame& 
 void launch_view_aov(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, float* out, hipStream_t s);
 // the ray AOV (nrc_view_aov.hpp, view_aov_walk_range): the same four numbers of caller-supplied ray segments, one launch of k_ray_aov each.
 // fr is the renderer's frame.  rays [n][8] = {ox, oy, oz, t_min, dx, dy, dz, t_max} -> out [n][4]; the frame's camera rays up to depth [h][w]
-// (fr's geometry and tile mask, as for launch_view_aov) -> out [h][w][4]; an orthographic view of w x h pixels -> out [h][w][4].  rays and
-// out 16-byte aligned.
-void launch_ray_aov_list(const DevScene& sc, const DevFrame& fr, size_t n, const float* rays, float* out, hipStream_t s);
-void launch_ray_aov_view_depth(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const float* depth, float* out, hipStream_t s);
-void launch_ray_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrthoView& view, uint32_t w, uint32_t h, float* out, hipStream_t s);
-// the deep AOV (nrc_view_aov.hpp, deep_aov_walk_range): the depths at which the same rays reach the n_levels optical depths `levels` (host
-// floats, already checked: deep_aov_levels_error), one launch of k_deep_aov each.  z [n_levels][rays] (planar), flat: null or the rays' flat
-// results [rays][4], 16-byte aligned; depth: null or as above.
-void launch_deep_aov_list(const DevScene& sc, const DevFrame& fr, size_t n, const float* rays, uint32_t n_levels, const float* levels, float* z,
-                          float* flat, hipStream_t s);
-void launch_deep_aov_view_depth(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const float* depth, uint32_t n_levels,
-                                const float* levels, float* z, float* flat, hipStream_t s);
-void launch_deep_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrthoView& view, uint32_t w, uint32_t h, uint32_t n_levels,
-                           const float* levels, float* z, float* flat, hipStream_t s);
+// (fr's geometry and tile mask, as for launch_view_aov; depth null: whole rays) -> out [h][w][4]; an orthographic view of w x h pixels ->
+// out [h][w][4].  rays and out 16-byte aligned.
+// deep: null, or the deep AOV (nrc_view_aov.hpp, deep_aov_walk_range) in the same launch -- the depths at which the rays reach the n_levels
+// optical depths `levels` (host floats, already checked: deep_aov_levels_error) go to z [n_levels][rays] (planar), and out may then be null.
+struct AovPlanes { uint32_t n_levels; const float* levels; float* z; };
+void launch_ray_aov_list(const DevScene& sc, const DevFrame& fr, size_t n, const float* rays, float* out, const AovPlanes* deep, hipStream_t s);
+void launch_ray_aov_view_depth(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const float* depth, float* out, const AovPlanes* deep, hipStream_t s);
+void launch_ray_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrthoView& view, uint32_t w, uint32_t h, float* out, const AovPlanes* deep, hipStream_t s);
 
 // ring: {uint head, uint tail, RayInfo[ring_size]}; scratch: uint32[2*T + 4]
 // start == nullptr: the whole of prep_train_rays.comp (scan, pop / trace / write, ring push).  start != nullptr (long train paths, the split

@@ -50,9 +50,17 @@ def build(native=False, out_dir=None):
     if os.path.exists(so) and not native and all(os.path.getmtime(so) >= os.path.getmtime(d) for d in deps):
         return so
     opt = ["-O3", "-march=native"] if native else ["-O2"]
+    # written beside `so` and moved over it in one step: two processes that find the library stale at the same time (the ranks of
+    # tests/test_dist_gloo.py) each build their own copy, and neither ever opens a half-written file
+    tmp = "%s.%d.tmp" % (so, os.getpid())
     cmd = ["g++"] + opt + ["-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-pthread",
-                           "-shared", "-o", so, src]
-    subprocess.check_call(cmd)
+                           "-shared", "-o", tmp, src]
+    try:
+        subprocess.check_call(cmd)
+        os.replace(tmp, so)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
     return so
 
 

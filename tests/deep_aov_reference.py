@@ -1,15 +1,15 @@
 """What the deep-AOV tests share (test_deep_aov_cpu.py, test_gpu_deep_aov.py): the level sets, the ray sets (ray_aov_reference's, and the
 blocks volume with a dense block), and an fp64 reference of the depths at which a ray SEGMENT reaches given optical depths.
 
-The reference is ray_aov_reference.reference_segment's construction with a level in place of ln 2: the ray is the fp32 record taken
+The reference (aov_reference.reference_segment) is ray_aov_reference.reference_segment's with a level in place of ln 2: the ray is the fp32 record taken
 exactly, the parameters of all voxel planes inside its range are sorted, every segment's voxel is looked up at its midpoint, and level L is
 crossed in the segment k with cum[k] < L <= cum[k + 1], at t[k] + (L - cum[k]) / sigma[k].  One pass over a ray serves every level of every
 level set, so a ray set is walked once."""
 import functools
-import math
 
 import numpy as np
 
+import aov_reference as A
 import ray_aov_reference as Q
 import view_aov_reference as R
 
@@ -68,53 +68,7 @@ def ray_sets(api, sc):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the fp64 reference
-def reference_segment(vol, size, density_factor, ro, rd, t_min, t_max, levels):
-    """(tau, z_front, z [K], crossings, sigma of the voxel where tau reaches each level [K], the range's end, index of that voxel's segment
-    [K]) over t in [max(t_min, 0), t_max] of one ray in fp64; nothing there: (0, inf, inf.., 0, 0.., 0, -1..)"""
-    K = len(levels)
-    none = (0.0, math.inf, np.full(K, math.inf), 0, np.zeros(K), 0.0, np.full(K, -1))
-    nz, ny, nx = vol.shape
-    n = np.array([nx, ny, nz])
-    size = np.asarray(size, np.float64)
-    lo, hi = -0.5 * size, 0.5 * size
-    if not (np.isfinite(ro).all() and np.isfinite(rd).all()) or math.isnan(t_min) or math.isnan(t_max):
-        return none
-    t0, t1 = max(0.0, t_min), math.inf
-    for a in range(3):
-        if rd[a] == 0.0:
-            if not (lo[a] < ro[a] < hi[a]):
-                return none
-            continue
-        ta, tb = (lo[a] - ro[a]) / rd[a], (hi[a] - ro[a]) / rd[a]
-        t0, t1 = max(t0, min(ta, tb)), min(t1, max(ta, tb))
-    if not math.isfinite(t1):
-        return none
-    t1 = min(t1, t_max)
-    if not (t0 < t1):
-        return none
-    ts = [np.array([t0, t1])]
-    for a in range(3):
-        if rd[a] != 0.0:
-            t = (lo[a] + np.arange(1, n[a]) * (size[a] / n[a]) - ro[a]) / rd[a]
-            ts.append(t[(t > t0) & (t < t1)])
-    t = np.sort(np.concatenate(ts))
-    mid = 0.5 * (t[1:] + t[:-1])
-    p = ro[None, :] + mid[:, None] * rd[None, :]
-    idx = np.clip(np.floor((p - lo) / (size / n)).astype(np.int64), 0, n - 1)
-    sigma = density_factor * vol[idx[:, 2], idx[:, 1], idx[:, 0]].astype(np.float64) / 255.0
-    seg = t[1:] - t[:-1]
-    cum = np.concatenate([[0.0], np.cumsum(sigma * seg)])
-    tau = float(cum[-1])
-    lit = np.nonzero((sigma > 0.0) & (seg > 0.0))[0]
-    z_front = float(t[lit[0]]) if lit.size else math.inf
-    z, s_cross, where = np.full(K, math.inf), np.zeros(K), np.full(K, -1)
-    for i, L in enumerate(levels):
-        if tau >= L:
-            k = int(np.searchsorted(cum, L, side="left")) - 1      # cum[k] < L <= cum[k + 1]
-            s_cross[i] = sigma[k]
-            z[i] = t[k] + (L - cum[k]) / sigma[k]
-            where[i] = k
-    return tau, z_front, z, int(t.size - 2), s_cross, float(t1), where
+reference_segment = A.reference_segment      # (vol, size, density_factor, ro, rd, t_min, t_max, levels): the shared reference as it is
 
 
 def all_levels(sc):
@@ -139,36 +93,17 @@ def reference(api, sc, name):
         return _REF[name]
     scene, rays = ray_sets(api, sc)[name]
     levels, where = all_levels(sc)
-    A = levels.size
-    vol = np.asarray(scene["density"])
-    size = np.asarray(scene["size"], np.float32).astype(np.float64)
-    rho = float(np.float32(scene["density_factor"]))
     recs = np.asarray(rays, np.float32).astype(np.float64)
     shape = recs.shape[:-1]
-    flat = recs.reshape(-1, 8)
-    n = flat.shape[0]
-    tau = np.zeros((n, 5))
-    zf = np.full((n, 5), math.inf)
-    z = np.full((A, n, 5), math.inf)
-    s_cross = np.zeros((A, n))
-    seg_of = np.full((A, n), -1)
-    crossings = np.zeros(n, np.int64)
-    t1 = np.zeros(n)
-    for i in range(n):
-        q = flat[i]
-        if not np.isfinite(q[4:7]).all() or not q[4:7].any():
-            continue
-        for k, d in enumerate(Q.perturbed(q[4:7])):
-            r = reference_segment(vol, size, rho, q[0:3], d, q[3], q[7], levels)
-            tau[i, k], zf[i, k], z[:, i, k] = r[0], r[1], r[2]
-            if k == 0:
-                crossings[i], s_cross[:, i], t1[i], seg_of[:, i] = (max(r[3], 1) if r[5] > 0.0 else 0), r[4], r[5], r[6]      # (N: ray_aov_reference.reference_rays)
-    same = np.zeros((A, n), bool)
+    ref = A.reference_records(scene, recs.reshape(-1, 8), Q.perturbed, levels)
+    seg_of = ref["segment"]
+    same = np.zeros(seg_of.shape, bool)
     for sl in where.values():
         same[sl.start + 1:sl.stop] = (seg_of[sl.start + 1:sl.stop] >= 0) & (seg_of[sl.start + 1:sl.stop] == seg_of[sl.start:sl.stop - 1])
-    _REF[name] = dict(tau=tau.reshape(shape + (5,)), z_front=zf.reshape(shape + (5,)), z=z.reshape((A,) + shape + (5,)),
-                      sigma_cross=s_cross.reshape((A,) + shape), crossings=crossings.reshape(shape), t1=t1.reshape(shape),
-                      same_voxel=same.reshape((A,) + shape), where=where)
+    K = (levels.size,)
+    _REF[name] = dict(tau=ref["tau"].reshape(shape + (5,)), z_front=ref["z_front"].reshape(shape + (5,)), z=ref["z"].reshape(K + shape + (5,)),
+                      sigma_cross=ref["sigma_cross"].reshape(K + shape), crossings=A.segments_summed(ref).reshape(shape),      # (N: a segment's)
+                      t1=ref["t1"].reshape(shape), same_voxel=same.reshape(K + shape), where=where)
     return _REF[name]
 
 

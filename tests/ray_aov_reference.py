@@ -1,15 +1,15 @@
 """What the ray-AOV tests share (test_ray_aov_cpu.py, test_gpu_ray_aov.py): the ray sets, an fp64 reference of {tau, z_front, z_half} over a
 ray SEGMENT, and the stable-ray rule -- view_aov_reference's, applied to records {ox, oy, oz, t_min, dx, dy, dz, t_max}.
 
-The reference is of the range: the ray is the fp32 record taken exactly, the range [t0, t1] = [max(box entry, t_min, 0), min(box exit,
-t_max)], the parameters of all voxel planes inside it are sorted and every segment's voxel is looked up at its midpoint (what
-view_aov_reference.reference_ray does for the whole ray).  The five rays of the stable rule share the record's origin and range and
+The reference is of the range (aov_reference.reference_segment): the ray is the fp32 record taken exactly, the range [t0, t1] =
+[max(box entry, t_min, 0), min(box exit, t_max)], the parameters of all voxel planes inside it are sorted and every segment's voxel is
+looked up at its midpoint (what view_aov_reference.reference_ray asks of the whole ray).  The five rays of the stable rule share the record's origin and range and
 differ in direction alone; they keep the record's |d|, so that t means the same on all five."""
 import functools
-import math
 
 import numpy as np
 
+import aov_reference as A
 import view_aov_reference as R
 
 W, H = R.W, R.H
@@ -133,47 +133,8 @@ def is_empty(a):
 def reference_segment(vol, size, density_factor, ro, rd, t_min, t_max):
     """(tau, z_front, z_half, crossings, sigma of the voxel where tau reaches ln 2, the range's end) over t in [max(t_min, 0), t_max] of
     one ray in fp64; nothing there: (0, inf, inf, 0, 0, 0)"""
-    none = (0.0, math.inf, math.inf, 0, 0.0, 0.0)
-    nz, ny, nx = vol.shape
-    n = np.array([nx, ny, nz])
-    size = np.asarray(size, np.float64)
-    lo, hi = -0.5 * size, 0.5 * size
-    if not (np.isfinite(ro).all() and np.isfinite(rd).all()) or math.isnan(t_min) or math.isnan(t_max):
-        return none
-    t0, t1 = max(0.0, t_min), math.inf
-    for a in range(3):
-        if rd[a] == 0.0:
-            if not (lo[a] < ro[a] < hi[a]):
-                return none
-            continue
-        ta, tb = (lo[a] - ro[a]) / rd[a], (hi[a] - ro[a]) / rd[a]
-        t0, t1 = max(t0, min(ta, tb)), min(t1, max(ta, tb))
-    if not math.isfinite(t1):
-        return none
-    t1 = min(t1, t_max)
-    if not (t0 < t1):
-        return none
-    ts = [np.array([t0, t1])]
-    for a in range(3):
-        if rd[a] != 0.0:
-            t = (lo[a] + np.arange(1, n[a]) * (size[a] / n[a]) - ro[a]) / rd[a]
-            ts.append(t[(t > t0) & (t < t1)])
-    t = np.sort(np.concatenate(ts))
-    mid = 0.5 * (t[1:] + t[:-1])
-    p = ro[None, :] + mid[:, None] * rd[None, :]
-    idx = np.clip(np.floor((p - lo) / (size / n)).astype(np.int64), 0, n - 1)
-    sigma = density_factor * vol[idx[:, 2], idx[:, 1], idx[:, 0]].astype(np.float64) / 255.0
-    seg = t[1:] - t[:-1]
-    cum = np.concatenate([[0.0], np.cumsum(sigma * seg)])
-    tau = float(cum[-1])
-    lit = np.nonzero((sigma > 0.0) & (seg > 0.0))[0]
-    z_front = float(t[lit[0]]) if lit.size else math.inf
-    z_half, s_cross = math.inf, 0.0
-    if tau >= R.LN2:
-        k = int(np.searchsorted(cum, R.LN2, side="left")) - 1      # cum[k] < ln 2 <= cum[k + 1]
-        s_cross = float(sigma[k])
-        z_half = float(t[k] + (R.LN2 - cum[k]) / sigma[k])
-    return tau, z_front, z_half, int(t.size - 2), s_cross, float(t1)
+    tau, z_front, z, crossings, s_cross, t1, _ = A.reference_segment(vol, size, density_factor, ro, rd, t_min, t_max, (R.LN2,))
+    return tau, z_front, float(z[0]), crossings, float(s_cross[0]), t1
 
 
 def perturbed(d):
@@ -189,33 +150,10 @@ def reference_rays(scene, rays, centre_only=False):
     """the reference of every record on its five rays, as view_aov_reference.reference_view returns it: arrays [...][5] (tau, z_front,
     z_half), [...] (crossings, sigma_cross, t1 of the centre ray) and the masks and spreads of summarize().  centre_only: the centre ray
     alone is evaluated (for its crossings and t1; the other four columns repeat it, so nothing is unstable)"""
-    vol = np.asarray(scene["density"])
-    size = np.asarray(scene["size"], np.float32).astype(np.float64)
-    rho = float(np.float32(scene["density_factor"]))
     recs = np.asarray(rays, np.float32).astype(np.float64)
     shape = recs.shape[:-1]
-    flat = recs.reshape(-1, 8)
-    n = flat.shape[0]
-    tau = np.zeros((n, 5))
-    zf = np.full((n, 5), math.inf)
-    zh = np.full((n, 5), math.inf)
-    crossings = np.zeros(n, np.int64)
-    s_cross = np.zeros(n)
-    t1 = np.zeros(n)
-    for i in range(n):
-        q = flat[i]
-        if not np.isfinite(q[4:7]).all() or not q[4:7].any():
-            continue
-        for k, d in enumerate(perturbed(q[4:7])):
-            r = reference_segment(vol, size, rho, q[0:3], d, q[3], q[7])
-            tau[i, k], zf[i, k], zh[i, k] = r[0], r[1], r[2]
-            if k == 0:
-                # N of view_aov_reference.tolerances counts the roundings of a walk, one per segment summed.  A whole ray sums N + 1 segments
-                # for its N planes and N is large; a range inside ONE voxel crosses no plane and still sums one segment, whose product no
-                # fp32 walk gets exactly: N = 1 there.  With a plane inside the range N is the planes' number, as for the whole ray.
-                crossings[i], s_cross[i], t1[i] = (max(r[3], 1) if r[5] > 0.0 else 0), r[4], r[5]
-                if centre_only:
-                    tau[i, :], zf[i, :], zh[i, :] = r[0], r[1], r[2]
-                    break
-    return R.summarize(dict(tau=tau.reshape(shape + (5,)), z_front=zf.reshape(shape + (5,)), z_half=zh.reshape(shape + (5,)),
-                            crossings=crossings.reshape(shape), sigma_cross=s_cross.reshape(shape), t1=t1.reshape(shape)))
+    ref = A.reference_records(scene, recs.reshape(-1, 8), perturbed, (R.LN2,), centre_only)
+    # crossings: a segment's N, not the whole ray's number of planes (aov_reference.segments_summed)
+    return R.summarize(dict(tau=ref["tau"].reshape(shape + (5,)), z_front=ref["z_front"].reshape(shape + (5,)),
+                            z_half=ref["z"][0].reshape(shape + (5,)), crossings=A.segments_summed(ref).reshape(shape),
+                            sigma_cross=ref["sigma_cross"][0].reshape(shape), t1=ref["t1"].reshape(shape)))

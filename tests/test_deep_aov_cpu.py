@@ -266,7 +266,7 @@ def test_the_new_symbols_exist_in_the_library_the_header_and_the_mirrors(api, sc
     for name in ("DeepRayAov", "DeepViewAov", "DeepOrthoAov"):
         assert hpp.count("void " + name + "(") == 2, name
     kernels = open(os.path.join(CSRC, "nrc_integrator.hip")).read()
-    assert "k_deep_aov" in kernels and "deep_aov_walk_range(" in kernels
+    assert "k_ray_aov<Src, Out>" in kernels and "struct DeepOut" in kernels and "deep_aov_walk_range(" in kernels
 
 
 def test_bad_levels_and_null_arguments_are_refused_without_a_device(api, sc):

@@ -1,4 +1,4 @@
-"""The deep AOV on the GPU (include/nrc_hpm.h "Deep AOV"; k_deep_aov<RayList | ViewDepth | OrthoView>): every plane and the flat result
+"""The deep AOV on the GPU (include/nrc_hpm.h "Deep AOV"; k_ray_aov<RayList | ViewDepth | OrthoView, DeepOut>): every plane and the flat result
 equal, bit for bit, the host restatement nrc_test_deep_ray_aov_host -- the plain deep range walk of csrc/nrc_view_aov.hpp, which
 tests/test_deep_aov_cpu.py pins to an fp64 reference -- although the kernel jumps out of empty cells by the occupancy bits, keeps its levels
 in LDS, stores a depth when it is crossed and, for the camera's rays, skips tiles by the empty-space mask.  Every ray, every plane, no
@@ -189,6 +189,25 @@ def test_views_equal_the_host_restatement_and_the_list_call(api, sc, torch_gpu, 
                     if lname in ("k7", "k32"):
                         assert _same(_list(torch, ren[0], recs, levels), want), (name, lname)
         _destroy(ren)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_no_depth_image_is_a_depth_image_of_inf(api, sc, torch_gpu, kind):
+    """the view source's null depth at 48 x 32, blocks V3 and the inside view, every level set: DeepViewAov without a depth image returns
+    ViewAov()'s bits as its flat result and, plane for plane, what it returns with a depth image of +inf"""
+    torch = torch_gpu
+    scene = Q.volume_scene(sc, "blocks")
+    views = (R.orbit_view(sc, 3), R.inside_view(sc, R.blocks_volume(), scene["size"]))
+    ren = _make(api, kind, scene, views[0])
+    inf = torch.full((R.H, R.W), float("inf"), device="cuda")
+    for i, cam in enumerate(views):
+        ren[0].SetCamera(None, cam)
+        whole = ren[0].ViewAov().cpu().numpy()
+        for lname, levels in D.level_sets(sc).items():
+            none = _np(ren[0].DeepViewAov(levels, depth=None, flat=True))
+            assert R.same_bits(none[1], whole) and _same(none, _np(ren[0].DeepViewAov(levels, depth=inf, flat=True))), (i, lname)
+            assert np.isfinite(none[0][0]).sum() > 50, (i, lname)
+    _destroy(ren)
 
 
 @pytest.mark.parametrize("kind", KINDS)

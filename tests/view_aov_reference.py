@@ -1,9 +1,9 @@
 """What the view-AOV tests share (test_view_aov_cpu.py, test_gpu_view_aov.py): the fixtures, an fp64 reference of {tau, z_front, z_half}
 per camera ray, and the stable-pixel rule.
 
-The reference knows nothing of a voxel walk: per ray, the parameters of ALL voxel planes the ray meets inside the box are sorted, and the
-voxel of every segment between two neighbours is looked up at the segment's midpoint.  The ray itself is the renderer's fp32 inv_proj_view
-and position, evaluated in fp64.
+The reference (aov_reference.reference_segment over the whole ray) knows nothing of a voxel walk: per ray, the parameters of ALL voxel
+planes the ray meets inside the box are sorted, and the voxel of every segment between two neighbours is looked up at the segment's
+midpoint.  The ray itself is the renderer's fp32 inv_proj_view and position, evaluated in fp64.
 
 Stable pixels.  The fp32 code and the fp64 reference do not follow the same ray to the last bit, and where a ray grazes a voxel's edge the
 AOV jumps.  The reference is therefore evaluated on five rays per pixel -- the centre ray d and d + 2e-6 * {+a, -a, +b, -b}, renormalised,
@@ -16,6 +16,8 @@ import math
 import os
 
 import numpy as np
+
+import aov_reference as A
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 LN2 = math.log(2.0)
@@ -142,65 +144,21 @@ def perturbed(d):
 
 # ---------------------------------------------------------------------------------------------------------------- the fp64 reference
 def reference_ray(vol, size, density_factor, ro, rd):
-    """(tau, z_front, z_half, crossings, sigma of the voxel where tau reaches ln 2, t1) of one ray in fp64; misses: (0, inf, inf, 0, 0, 0)"""
-    nz, ny, nx = vol.shape
-    n = np.array([nx, ny, nz])
-    size = np.asarray(size, np.float64)
-    lo, hi = -0.5 * size, 0.5 * size
-    t0, t1 = 0.0, math.inf
-    for a in range(3):
-        if rd[a] == 0.0:
-            if not (lo[a] < ro[a] < hi[a]):
-                return 0.0, math.inf, math.inf, 0, 0.0, 0.0
-            continue
-        ta, tb = (lo[a] - ro[a]) / rd[a], (hi[a] - ro[a]) / rd[a]
-        t0, t1 = max(t0, min(ta, tb)), min(t1, max(ta, tb))
-    if not (t0 < t1) or not math.isfinite(t1):
-        return 0.0, math.inf, math.inf, 0, 0.0, 0.0
-    ts = [np.array([t0, t1])]
-    for a in range(3):
-        if rd[a] != 0.0:
-            t = (lo[a] + np.arange(1, n[a]) * (size[a] / n[a]) - ro[a]) / rd[a]
-            ts.append(t[(t > t0) & (t < t1)])
-    t = np.sort(np.concatenate(ts))
-    mid = 0.5 * (t[1:] + t[:-1])
-    p = ro[None, :] + mid[:, None] * rd[None, :]
-    idx = np.clip(np.floor((p - lo) / (size / n)).astype(np.int64), 0, n - 1)
-    sigma = density_factor * vol[idx[:, 2], idx[:, 1], idx[:, 0]].astype(np.float64) / 255.0
-    seg = t[1:] - t[:-1]
-    cum = np.concatenate([[0.0], np.cumsum(sigma * seg)])
-    tau = float(cum[-1])
-    lit = np.nonzero((sigma > 0.0) & (seg > 0.0))[0]
-    z_front = float(t[lit[0]]) if lit.size else math.inf
-    z_half, s_cross = math.inf, 0.0
-    if tau >= LN2:
-        k = int(np.searchsorted(cum, LN2, side="left")) - 1      # cum[k] < ln 2 <= cum[k + 1]
-        s_cross = float(sigma[k])
-        z_half = float(t[k] + (LN2 - cum[k]) / sigma[k])
-    return tau, z_front, z_half, int(t.size - 2), s_cross, float(t1)
+    """(tau, z_front, z_half, crossings, sigma of the voxel where tau reaches ln 2, t1) of one whole ray in fp64; misses: (0, inf, inf, 0, 0, 0)"""
+    tau, z_front, z, crossings, s_cross, t1, _ = A.reference_segment(vol, size, density_factor, ro, rd, 0.0, math.inf, (LN2,))
+    return tau, z_front, float(z[0]), crossings, float(s_cross[0]), t1
 
 
 def reference_view(scene, cam, w=W, h=H):
     """the reference of every pixel on its five rays: dict of arrays [h][w][5] (tau, z_front, z_half), [h][w] (crossings, sigma_cross, t1
     of the centre ray) and the derived masks `hit`, `stable` and spreads S_tau, S_zf, S_zh"""
-    vol = np.asarray(scene["density"])
-    size = np.asarray(scene["size"], np.float32).astype(np.float64)
-    rho = float(np.float32(scene["density_factor"]))
     dirs, pos = ray_directions(cam, w, h)
-    tau = np.zeros((h, w, 5))
-    zf = np.full((h, w, 5), math.inf)
-    zh = np.full((h, w, 5), math.inf)
-    crossings = np.zeros((h, w), np.int64)
-    s_cross = np.zeros((h, w))
-    t1 = np.zeros((h, w))
-    for y in range(h):
-        for x in range(w):
-            for k, d in enumerate(perturbed(dirs[y, x])):
-                r = reference_ray(vol, size, rho, pos, d)
-                tau[y, x, k], zf[y, x, k], zh[y, x, k] = r[0], r[1], r[2]
-                if k == 0:
-                    crossings[y, x], s_cross[y, x], t1[y, x] = r[3], r[4], r[5]
-    return summarize(dict(tau=tau, z_front=zf, z_half=zh, crossings=crossings, sigma_cross=s_cross, t1=t1, dirs=dirs))
+    records = np.concatenate([np.broadcast_to(pos, (h, w, 3)), np.zeros((h, w, 1)), dirs, np.full((h, w, 1), math.inf)], axis=-1)
+    ref = A.reference_records(scene, records.reshape(-1, 8), perturbed, (LN2,))
+    # crossings: a whole ray's N is the number of voxel planes it meets (aov_reference.segments_summed: where a ray segment's differs)
+    return summarize(dict(tau=ref["tau"].reshape(h, w, 5), z_front=ref["z_front"].reshape(h, w, 5), z_half=ref["z"][0].reshape(h, w, 5),
+                          crossings=ref["planes"].reshape(h, w), sigma_cross=ref["sigma_cross"][0].reshape(h, w), t1=ref["t1"].reshape(h, w),
+                          dirs=dirs))
 
 
 def _spread(z):

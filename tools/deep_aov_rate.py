@@ -1,11 +1,11 @@
-"""What the deep AOV (DeepViewAov / DeepOrthoAov: k_deep_aov) costs beside the flat kernel of the same rays, on the bench scene (fBm cloud
-256^3, scene 4) at 1920 x 1080.
+"""What the deep AOV (DeepViewAov / DeepOrthoAov: k_ray_aov<Src, DeepOut>) costs beside the flat kernel of the same rays, on the bench scene
+(fBm cloud 256^3, scene 4) at 1920 x 1080.
 
   rocprofv3 --kernel-trace -d <dir> -- python tools/deep_aov_rate.py --trace [--views 16]
-      per view of an orbit, in this order: ViewAovToDepth with depth +inf (k_ray_aov<ViewDepth>, the flat kernel), DeepViewAov with the flat
-      result at K = 1 (ln 2), K = 8 and K = 32 (scene.deep_levels(K, 3.0)) (k_deep_aov<ViewDepth>), and the flat kernel once more: the
-      difference between a view's two flat launches is the trace's run-to-run spread.  Behind the views a 1024^2 scene.light_view the same
-      way, five times (k_ray_aov<OrthoView>, k_deep_aov<OrthoView>).  One warm-up pass runs in front of each.
+      per view of an orbit, in this order: ViewAovToDepth with depth +inf (k_ray_aov<ViewDepth, FlatOut>, the flat kernel), DeepViewAov with
+      the flat result at K = 1 (ln 2), K = 8 and K = 32 (scene.deep_levels(K, 3.0)) (k_ray_aov<ViewDepth, DeepOut>), and the flat kernel once
+      more: the difference between a view's two flat launches is the trace's run-to-run spread.  Behind the views a 1024^2 scene.light_view
+      the same way, five times (k_ray_aov<OrthoView, FlatOut | DeepOut>).  One warm-up pass runs in front of each.
   python tools/deep_aov_rate.py --trace-csv <dir>/.../..._kernel_trace.csv [--views 16]      (a second step, no GPU)
       the mean duration of each of those launches from the trace's rows, told apart by kernel name and by their order; the ratios to the
       flat kernel of the same trace; the spread; and K flat walks -- what the one deep launch replaces -- against it.
@@ -76,7 +76,8 @@ def trace(args):
 
 def trace_csv(path, views):
     names = None
-    rows = {("k_ray_aov", "ViewDepth"): [], ("k_deep_aov", "ViewDepth"): [], ("k_ray_aov", "OrthoView"): [], ("k_deep_aov", "OrthoView"): []}
+    # k_ray_aov<source, output>: the flat kernel and the deep one differ in the output's name
+    rows = {("FlatOut", "ViewDepth"): [], ("DeepOut", "ViewDepth"): [], ("FlatOut", "OrthoView"): [], ("DeepOut", "OrthoView"): []}
     with open(path) as f:
         for r in csv.DictReader(f):
             if names is None:
@@ -84,7 +85,7 @@ def trace_csv(path, views):
                 names = (cols["kernel_name"], cols["start_timestamp"], cols["end_timestamp"])
             name = r[names[0]]
             for key in rows:
-                if key[0] in name and key[1] in name:
+                if "k_ray_aov" in name and key[0] in name and key[1] in name:
                     rows[key].append((float(r[names[1]]), float(r[names[2]]) - float(r[names[1]])))
     for v in rows.values():
         v.sort()
@@ -100,13 +101,13 @@ def trace_csv(path, views):
 
     res = dict(what="deep_aov_kernels", views=views)
     for tag, src, passes in (("view", "ViewDepth", views), ("light_1024", "OrthoView", LIGHT_REPEATS)):
-        first, last = series(("k_ray_aov", src), 2, passes, 0), series(("k_ray_aov", src), 2, passes, 1)
+        first, last = series(("FlatOut", src), 2, passes, 0), series(("FlatOut", src), 2, passes, 1)
         flat = mean(first + last)
         res[tag + "_flat_ms"] = flat
         # run-to-run: a pass's two flat launches walk the same rays
         res[tag + "_flat_spread"] = mean([abs(a - b) for a, b in zip(first, last)]) / flat
         for j, k in enumerate(KS):
-            d = series(("k_deep_aov", src), len(KS), passes, j)
+            d = series(("DeepOut", src), len(KS), passes, j)
             per_pass = [x / (0.5 * (a + b)) for x, a, b in zip(d, first, last)]
             res["%s_deep_k%d_ms" % (tag, k)] = mean(d)
             res["%s_deep_k%d_over_flat" % (tag, k)] = mean(d) / flat

@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """Compare the gfx950 kernel bodies inside two builds of libnrc_hpm.so, kernel by kernel (llvm-objdump -d of the embedded code objects).
 
-    python tools/kernel_body_diff.py OLD.so NEW.so [name-substring ...]
+    python tools/kernel_body_diff.py OLD.so NEW.so [--rename FROM=TO ...] [--diff] [name-substring ...]
 
+--rename pairs a kernel whose name changed: OLD.so's kernel FROM is compared with NEW.so's kernel TO, each named by the end of its demangled
+name without "(anonymous namespace)::" and without the parameter list, for example
+--rename 'k_deep_aov<nrc::RayList>=k_ray_aov<nrc::RayList, nrc::DeepOut>'.  --diff prints the unified diff of every kernel that differs.
 Prints, for every kernel both libraries hold (by demangled name; or only those whose name contains one of the substrings), whether the instruction
 streams are identical; kernels only one side holds are listed.  What depends on where a kernel lies inside its code object is stripped
 before the comparison: addresses, branch-target labels, the pc-relative offsets of the two additions behind an s_getpc_b64 (the address
 of a __device__ variable) and the padding behind the last s_endpgm.  Exit status 1 when a common kernel differs.
 What a pull request quotes when it claims that a path it did not mean to touch is unchanged."""
+import difflib
 import glob
 import os
 import re
@@ -53,9 +57,26 @@ def kernel_bodies(lib, tmp, tag):
 
 
 def main():
-    old, new, want = sys.argv[1], sys.argv[2], sys.argv[3:]
+    args, renames, show = [], [], False
+    argv = sys.argv[1:]
+    while argv:
+        arg = argv.pop(0)
+        if arg == "--rename":
+            renames.append(argv.pop(0))
+        elif arg == "--diff":
+            show = True
+        else:
+            args.append(arg)
+    old, new, want = args[0], args[1], args[2:]
     with tempfile.TemporaryDirectory() as tmp:
         a, b = kernel_bodies(old, tmp, "old"), kernel_bodies(new, tmp, "new")
+    short = lambda n: n.replace("(anonymous namespace)::", "").split("(")[0]      # noqa: E731
+    for r in renames:      # OLD's kernel FROM is compared under the full name of NEW's kernel TO
+        frm, to = r.split("=", 1)
+        was, now = [n for n in a if short(n).endswith(frm)], [n for n in b if short(n).endswith(to)]
+        if len(was) != 1 or len(now) != 1:
+            sys.exit("--rename %s: %d kernels of %s and %d of %s are named so" % (r, len(was), old, len(now), new))
+        a[now[0]] = a.pop(was[0])
     keep = lambda n: not want or any(w in n for w in want)      # noqa: E731
     same = differ = 0
     for name in sorted(set(a) & set(b)):
@@ -67,6 +88,8 @@ def main():
         else:
             differ += 1
             print("DIFFERENT  %5d -> %5d instructions  %s" % (len(a[name]), len(b[name]), name))
+            if show:
+                print("\n".join(difflib.unified_diff(a[name], b[name], "old", "new", n=2, lineterm="")))
     for name in sorted(set(a) - set(b)):
         if keep(name):
             print("only in old  %s" % name)
