@@ -780,6 +780,71 @@ int nrc_mc_renderer_deep_ortho_aov(nrc_mc_renderer_t* r, const nrc_ortho_view* v
 int nrc_test_deep_ray_aov_host(const nrc_scene* scene, size_t n, const float* host_rays, uint32_t n_levels, const float* levels, float* host_z,
                                float* host_flat);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Denoise: an edge-avoiding a-trous filter over a frame, guided by the view AOV of the same view (both renderers; every renderer call has
+ * an nrc_mc_renderer_ twin).  The guide is exact and noise-free -- a function of camera and medium alone -- so the filter never smooths
+ * across the medium's silhouette or a step in depth, and never touches sky.  It is a deterministic function of two images, opt-in, and
+ * BIASED: it is for low frame counts and previews (DESIGN.md section 4.19 has the measured gains, the bias and where it starts to lose).
+ *   Inputs.   colour c [h][w][4] fp32 RGBA (the framebuffer's layout); guide g [h][w][4] fp32 {alpha, tau, z_front, z_half} (a view AOV), of
+ *             which only alpha and z_front are read; output [h][w][4].  All 16-byte aligned device memory.
+ *   Params.   nrc_denoise_params: passes 1 .. 6 (default 3); sigma_alpha (0.1); sigma_depth (4.0, in the units of t); sigma_color (+inf:
+ *             the term is off); color_decay (0.5), in (0, 1].  Every sigma must be > 0, +inf allowed, and large enough that 1 / sigma --
+ *             for the colour term 1 / (sigma_color color_decay^(passes - 1)) -- is finite in fp32.  NaN and anything out of range:
+ *             NRC_ERR_INVALID.  nrc_denoise_params_default fills the defaults.
+ *   Passes.   Pass p = 0 .. passes - 1 has stride s = 1 << p, reads c_p (c_0 = c) and writes c_{p+1}; the result is c_passes.
+ *   Copied.   Pixel P = (x, y) is copied bit for bit when alpha_P == 0 (sky and mask-rejected tiles, whose guide is {0, 0, +inf, +inf}:
+ *             nothing is computed from their z_front) or when R, G or B of c_p(P) is not finite.
+ *   Taps.     Otherwise Q = (x + i s, y + j s) for j = -2 .. 2 (outer loop), i = -2 .. 2 (inner loop), in that order, skipping a tap that
+ *             lies outside the image, has alpha_Q == 0, or has a non-finite R, G or B in c_p.  For every kept tap, in fp32:
+ *               k = h[i + 2] h[j + 2],  h = {1, 4, 6, 4, 1} / 16                      (exact)
+ *               d = |alpha_Q - alpha_P| inv_sa
+ *               d = fma(|z_front_Q - z_front_P|, inv_sz, d)
+ *               d = fma(|lum_Q - lum_P|, inv_sc_p, d),   lum = fma(.114f, b, fma(.587f, g, .299f r)) of c_p
+ *               wgt = k (1.0f - nrc_expm1_negf(d))                                     (csrc/nrc_math.h)
+ *               acc_c = fma(wgt, c_Q - c_P, acc_c) for R, G, B;   acc_w += wgt
+ *             with inv_sa = 1.0f / sigma_alpha, inv_sz = 1.0f / sigma_depth and inv_sc_p = 1.0f / (sigma_color color_decay^p), the power
+ *             formed by p fp32 multiplications of sigma_color.  sigma = +inf gives an inverse, and a term, of exactly 0.
+ *             out = c_P + acc_c / acc_w: the weighted mean sum(wgt c_Q) / sum(wgt), formed around the centre so that the roundings are of
+ *             the size of the local contrast -- a constant colour over a constant guide comes back bit for bit.  d is not clamped: nrc_expm1_negf is exactly 1 from 17.5 on (such a tap adds nothing) and 0 for a NaN,
+ *             which only a guide outside the view AOV's contract can produce (alpha != 0 beside a non-finite z_front) and which so counts
+ *             as d = 0.  The centre tap has wgt = 36 / 256: acc_w is never 0.
+ *   Alpha.    The output's alpha channel is the colour input's bits in every case.
+ * The fp32 arithmetic is defined once, in csrc/nrc_denoise.hpp, which the kernel and the host (nrc_test_denoise_host) both run: the same
+ * bits.  No in-place operation: an output that overlaps the colour, the guide or the scratch returns NRC_ERR_INVALID.
+ * nrc_denoise: the free function over whole images -- what a caller with a gathered frame uses.  d_scratch: nrc_denoise_scratch_bytes
+ *   bytes (0 for refused arguments).  One launch that packs the guide and one launch per pass on `stream`; no host wait.
+ * nrc_renderer_denoised_frame: the current framebuffer filtered with the current view AOV (computed through nrc_renderer_view_aov's path
+ *   if stale); device memory owned by the renderer, valid until it is destroyed, rewritten by the next call.  Enqueued on the renderer's
+ *   streams behind the frames enqueued so far and in front of the framebuffer's next blend or clear; no host wait; the creation stream is
+ *   ordered behind it, as for nrc_renderer_framebuffer.  The image and the scratch are allocated by the first call: a renderer on which it
+ *   is never made allocates and launches nothing.  NULL on failure.
+ * nrc_renderer_set_path_denoise_target: the next nrc_renderer_render_path / _render_path_timed call writes view i's filtered final frame
+ *   to d_denoised + i * h * w * 4 (device memory, n_views * h * w * 4 floats), behind the view's last blend and in front of the next view's
+ *   clear.  It needs an AOV target in the same call (nrc_renderer_set_path_aov_target): view i's guide is the caller's own d_aovs[i], so
+ *   no view overwrites another's guide.  AOV depths are forbidden (the guide would be a held-out AOV).  A path call with an n_views
+ *   mismatch, without an AOV target or with depths fails with NRC_ERR_INVALID, enqueues nothing and drops every target.  Consumed by that
+ *   call; d_denoised == NULL cancels.  When the path call returns the creation stream is ordered behind the last filtered frame.
+ *   Frames, d_frames, AOVs and training state are bit for bit what they are without the target.
+ * nrc_renderer_export_exr_denoised: nrc_renderer_export_exr_aov's channels with B, G, R taken from the filtered frame.
+ * A renderer that draws one rank's column strips of a sharded frame (nrc_renderer_create_tiled with x_stride > 1) refuses every renderer
+ *   call above with NRC_ERR_INVALID: its local image has no pixel neighbours.  Gather the frame and the AOV and call nrc_denoise.
+ * nrc_test_denoise_host (test hook): the header's arithmetic on the CPU inside the library; host memory, no device. */
+typedef struct nrc_denoise_params {
+    uint32_t passes;
+    float sigma_alpha, sigma_depth, sigma_color, color_decay;
+} nrc_denoise_params;
+void nrc_denoise_params_default(nrc_denoise_params* p);
+size_t nrc_denoise_scratch_bytes(uint32_t w, uint32_t h, const nrc_denoise_params* params);
+int nrc_denoise(const float* d_rgba, const float* d_aov, uint32_t w, uint32_t h, const nrc_denoise_params* params, float* d_out, void* d_scratch,
+                void* stream);
+const float* nrc_renderer_denoised_frame(nrc_renderer_t* r, const nrc_denoise_params* params);
+int nrc_renderer_set_path_denoise_target(nrc_renderer_t* r, float* d_denoised, uint32_t n_views, const nrc_denoise_params* params);
+int nrc_renderer_export_exr_denoised(nrc_renderer_t* r, const char* path, const nrc_denoise_params* params);
+const float* nrc_mc_renderer_denoised_frame(nrc_mc_renderer_t* r, const nrc_denoise_params* params);
+int nrc_mc_renderer_set_path_denoise_target(nrc_mc_renderer_t* r, float* d_denoised, uint32_t n_views, const nrc_denoise_params* params);
+int nrc_mc_renderer_export_exr_denoised(nrc_mc_renderer_t* r, const char* path, const nrc_denoise_params* params);
+int nrc_test_denoise_host(const float* rgba, const float* aov, uint32_t w, uint32_t h, const nrc_denoise_params* params, float* out);
+
 /* THE environment switch of the library: NRC_DEBUG="name[=value],..." -- diagnostic and test switches only, none changes a result
  * (the list and what each does: csrc/nrc_common.hpp, debug_switch).
  * diagnostics (read when the library first allocates): NRC_DEBUG=poison_alloc fills every device allocation with 0xFF

@@ -512,6 +512,25 @@ public:
     }
     // ExportOutputImageToFile with the AOV beside the colours: FLOAT channels A (= alpha), B, G, R, Z (= z_front), Zhalf, tau; this renderer's pixels
     void ExportOutputImageWithAovToFile(void* /*queue*/, const std::string& filePath) const { nrc_check(nrc_renderer_export_exr_aov(h_, filePath.c_str())); }
+    // The denoise filter (include/nrc_hpm.h, "Denoise"; en::Denoise below is the free function): opt-in and biased, for low frame counts and
+    // previews.  DenoisedFrame: the current framebuffer filtered with the current view AOV -- device [height][width][4], owned by the renderer,
+    // enqueued behind the frames so far, the creation stream ordered behind it; throws on failure (a renderer of a sharded frame's strips
+    // refuses).  SetPathDenoiseTarget: with SetPathAovTarget and without depths, the next RenderPath writes view i's filtered final frame
+    // to dDenoised + i * height * width * 4 (nullptr cancels).  ExportDenoisedImageToFile: ExportOutputImageWithAovToFile with B, G, R filtered.
+    const float* DenoisedFrame(const nrc_denoise_params& params) const
+    {
+        const float* p = nrc_renderer_denoised_frame(h_, &params);
+        if (p == nullptr) nrc_check(NRC_ERR_INVALID);
+        return p;
+    }
+    void SetPathDenoiseTarget(float* dDenoised, uint32_t nViews, const nrc_denoise_params* params)
+    {
+        nrc_check(nrc_renderer_set_path_denoise_target(h_, dDenoised, nViews, params));
+    }
+    void ExportDenoisedImageToFile(void* /*queue*/, const std::string& filePath, const nrc_denoise_params& params) const
+    {
+        nrc_check(nrc_renderer_export_exr_denoised(h_, filePath.c_str(), &params));
+    }
     // diagnostics: the empty-space tile mask in use (synchronises; empty: the frame uses none) -- nrc_renderer_tile_mask
     std::vector<uint32_t> TileMask() const
     {
@@ -625,6 +644,21 @@ public:
         nrc_check(nrc_mc_renderer_deep_ortho_aov(h_, &view, w, h, nLevels, levels, dZ, dFlat));
     }
     void ExportOutputImageWithAovToFile(void* /*queue*/, const std::string& filePath) const { nrc_check(nrc_mc_renderer_export_exr_aov(h_, filePath.c_str())); }
+    // see NrcHpmRenderer::DenoisedFrame / SetPathDenoiseTarget / ExportDenoisedImageToFile
+    const float* DenoisedFrame(const nrc_denoise_params& params) const
+    {
+        const float* p = nrc_mc_renderer_denoised_frame(h_, &params);
+        if (p == nullptr) nrc_check(NRC_ERR_INVALID);
+        return p;
+    }
+    void SetPathDenoiseTarget(float* dDenoised, uint32_t nViews, const nrc_denoise_params* params)
+    {
+        nrc_check(nrc_mc_renderer_set_path_denoise_target(h_, dDenoised, nViews, params));
+    }
+    void ExportDenoisedImageToFile(void* /*queue*/, const std::string& filePath, const nrc_denoise_params& params) const
+    {
+        nrc_check(nrc_mc_renderer_export_exr_denoised(h_, filePath.c_str(), &params));
+    }
     std::vector<uint32_t> TileMask() const
     {
         std::vector<uint32_t> m(nrc_mc_renderer_tile_mask(h_, nullptr, 0));
@@ -663,6 +697,21 @@ private:
     nrc_mc_renderer_t* h_ = nullptr;
     float frame_ms_ = 0.0f;
 };
+
+// The denoise filter over whole device images (include/nrc_hpm.h, "Denoise": nrc_denoise) -- what a caller with a gathered frame uses.
+// dRgba, dAov -> dOut, all [height][width][4] and distinct; dScratch: DenoiseScratchBytes bytes; enqueued on `stream`, no host wait.
+inline nrc_denoise_params DenoiseDefaults()
+{
+    nrc_denoise_params p;
+    nrc_denoise_params_default(&p);
+    return p;
+}
+inline size_t DenoiseScratchBytes(uint32_t width, uint32_t height, const nrc_denoise_params& params) { return nrc_denoise_scratch_bytes(width, height, &params); }
+inline void Denoise(const float* dRgba, const float* dAov, uint32_t width, uint32_t height, const nrc_denoise_params& params, float* dOut, void* dScratch,
+                    void* stream)
+{
+    nrc_check(nrc_denoise(dRgba, dAov, width, height, &params, dOut, dScratch, stream));
+}
 
 // en::Reference (src/Reference.cpp): the converged ground-truth image of a scene, seen from a fixed reference camera, and the
 // comparison of a renderer's frame with it -- Result{mse, refMean, ownMean, ownVar, validPixelCount} by the three passes of

@@ -98,6 +98,9 @@ ABI_SYMBOLS = [
     "nrc_camera_rays", "nrc_ortho_rays", "nrc_test_ray_aov_host",
     "nrc_renderer_deep_ray_aov", "nrc_mc_renderer_deep_ray_aov", "nrc_renderer_deep_view_aov", "nrc_mc_renderer_deep_view_aov",
     "nrc_renderer_deep_ortho_aov", "nrc_mc_renderer_deep_ortho_aov", "nrc_test_deep_ray_aov_host",
+    "nrc_denoise_params_default", "nrc_denoise_scratch_bytes", "nrc_denoise", "nrc_test_denoise_host",
+    "nrc_renderer_denoised_frame", "nrc_mc_renderer_denoised_frame", "nrc_renderer_set_path_denoise_target", "nrc_mc_renderer_set_path_denoise_target",
+    "nrc_renderer_export_exr_denoised", "nrc_mc_renderer_export_exr_denoised",
     "nrc_renderer_set_show_nrc", "nrc_renderer_set_frame_random", "nrc_renderer_framebuffer", "nrc_renderer_framebuffer_on",
     "nrc_renderer_export_exr",
     "nrc_renderer_frame_time_ms", "nrc_renderer_stage_stats", "nrc_renderer_frame_timeline", "nrc_set_wave_priority_raise", "nrc_renderer_destroy", "nrc_renderer_buffer", "nrc_renderer_count_fetches",
@@ -221,6 +224,20 @@ def load_library():
         for name in ("nrc_renderer_deep_ortho_aov", "nrc_mc_renderer_deep_ortho_aov"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nrc_test_deep_ray_aov_host.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "nrc_denoise"):      # (an older build loaded through NRC_HPM_LIB has no denoise filter)
+        L.nrc_denoise_params_default.restype = None
+        L.nrc_denoise_params_default.argtypes = [C.c_void_p]
+        L.nrc_denoise_scratch_bytes.restype = C.c_size_t
+        L.nrc_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
+        L.nrc_denoise.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nrc_test_denoise_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        for name in ("nrc_renderer_denoised_frame", "nrc_mc_renderer_denoised_frame"):
+            getattr(L, name).restype = C.c_void_p
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+        for name in ("nrc_renderer_set_path_denoise_target", "nrc_mc_renderer_set_path_denoise_target"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        for name in ("nrc_renderer_export_exr_denoised", "nrc_mc_renderer_export_exr_denoised"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     L.nrc_mc_renderer_frame_time_ms.restype = C.c_float
     if hasattr(L, "nrc_test_flight_select"):      # (an older build loaded through NRC_HPM_LIB has no such hook)
         L.nrc_test_flight_select.argtypes = [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -479,6 +496,64 @@ def _deep_flat(what, flat, shape):
     return _aov_out(what + ": flat", None if flat is True else flat, shape)
 
 
+class NrcDenoiseParams(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("sigma_alpha", C.c_float), ("sigma_depth", C.c_float), ("sigma_color", C.c_float),
+                ("color_decay", C.c_float)]
+
+
+def make_c_denoise_params(params=None):
+    """nrc_denoise_params: the library's defaults (nrc_denoise_params_default) overridden by `params` -- None, a dict with any of passes,
+    sigma_alpha, sigma_depth, sigma_color, color_decay (scene.denoise_params), or an NrcDenoiseParams.  The library checks the values."""
+    if isinstance(params, NrcDenoiseParams):
+        return params
+    p = NrcDenoiseParams()
+    load_library().nrc_denoise_params_default(C.byref(p))
+    for k, v in (params or {}).items():
+        if k not in ("passes", "sigma_alpha", "sigma_depth", "sigma_color", "color_decay"):
+            raise ValueError("denoise parameters: unknown key %r" % (k,))
+        setattr(p, k, int(v) if k == "passes" else float(v))
+    return p
+
+
+def Denoise(rgba, aov, params=None, out=None):
+    """nrc_denoise: the edge-avoiding a-trous filter (include/nrc_hpm.h, "Denoise") over whole images -- what a caller with a gathered frame
+    uses.  rgba and aov: contiguous float32 CUDA tensors [h][w][4] (a framebuffer and the view AOV of the same view); params as for
+    make_c_denoise_params.  Returns the filtered image [h][w][4] (`out`, or a new tensor; never one of the inputs).  Enqueued on torch's
+    current stream; no host wait."""
+    import torch
+    if not isinstance(rgba, torch.Tensor) or rgba.dim() != 3:
+        raise ValueError("Denoise: rgba must be a contiguous float32 CUDA tensor of shape (h, w, 4)")
+    shape = (int(rgba.shape[0]), int(rgba.shape[1]), 4)
+    _check_device_floats("Denoise: rgba", rgba, shape)
+    _check_device_floats("Denoise: aov", aov, shape)
+    out = _aov_out("Denoise", out, shape)
+    p = make_c_denoise_params(params)
+    L = load_library()
+    n = L.nrc_denoise_scratch_bytes(C.c_uint32(shape[1]), C.c_uint32(shape[0]), C.byref(p))
+    if n == 0:
+        raise RuntimeError(L.nrc_last_error().decode() or "denoise: refused")
+    scratch = torch.empty(n, device="cuda", dtype=torch.uint8)
+    stream = torch.cuda.current_stream()
+    _check(L.nrc_denoise(_dev_ptr(rgba), _dev_ptr(aov), C.c_uint32(shape[1]), C.c_uint32(shape[0]), C.byref(p), _dev_ptr(out), _dev_ptr(scratch),
+                         C.c_void_p(stream.cuda_stream)))
+    scratch.record_stream(stream)
+    return out
+
+
+def test_denoise_host(rgba, aov, params=None):
+    """nrc_test_denoise_host: the filter [h][w][4] (numpy) of the numpy images rgba and aov [h][w][4], computed on the CPU inside the library
+    by csrc/nrc_denoise.hpp's arithmetic"""
+    c = np.ascontiguousarray(rgba, np.float32)
+    g = np.ascontiguousarray(aov, np.float32)
+    if c.ndim != 3 or c.shape[2] != 4 or g.shape != c.shape:
+        raise ValueError("test_denoise_host: rgba and aov must both be [h][w][4]")
+    out = np.empty_like(c)
+    p = make_c_denoise_params(params)
+    _check(load_library().nrc_test_denoise_host(c.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), C.c_uint32(c.shape[1]),
+                                                C.c_uint32(c.shape[0]), C.byref(p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 class NrcOrthoView(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3), ("dir", C.c_float * 3)]
 
@@ -495,15 +570,18 @@ def make_c_ortho_view(view):
 
 
 def _times_keyword(plain):
-    """RenderPath(..., times=None, aov_out=None, aov_depths=None) of both renderers.  The keywords ride on the untimed method: its positional signature is
+    """RenderPath(..., times=None, aov_out=None, aov_depths=None, denoised_out=None, denoise_params=None) of both renderers.  The keywords ride
+    on the untimed method: its positional signature is
     a published one (callers and tests/test_camera_path_host.py name its parameters in order) and stays what inspect.signature reports; a
     call without times is `plain`'s own, a call with times goes to the renderer's _path with the same arguments.
     aov_out: a contiguous float32 CUDA tensor [len(cameras)][height][width][4] that receives every view's AOV ({alpha, tau, z_front,
     z_half} of that view's camera and medium: ViewAov, nrc_renderer_set_path_aov_target); frames, `out` and training are unchanged by it.
     aov_depths (with aov_out): a contiguous float32 CUDA tensor [len(cameras)][height][width]; view i's AOV is held out to aov_depths[i]
-    (ViewAovToDepth, nrc_renderer_set_path_aov_depths)."""
+    (ViewAovToDepth, nrc_renderer_set_path_aov_depths).
+    denoised_out (with aov_out, without aov_depths): a tensor of aov_out's shape that receives every view's final frame filtered with the
+    view's own AOV (DenoisedFrame, nrc_renderer_set_path_denoise_target); denoise_params as for make_c_denoise_params."""
     @functools.wraps(plain)
-    def RenderPath(self, *args, times=None, aov_out=None, aov_depths=None, **kw):
+    def RenderPath(self, *args, times=None, aov_out=None, aov_depths=None, denoised_out=None, denoise_params=None, **kw):
         bound = inspect.signature(plain).bind(self, *args, **kw)
         bound.apply_defaults()
         if aov_out is not None:
@@ -522,6 +600,18 @@ def _times_keyword(plain):
                 self.SetPathAovTarget(None)
                 raise
             self.SetPathAovDepths(aov_depths)
+        if denoised_out is not None:
+            try:
+                if aov_out is None:
+                    raise ValueError("RenderPath: denoised_out needs aov_out (a view's AOV is its guide)")
+                _check_device_floats("RenderPath: denoised_out", denoised_out, shape)
+                self.SetPathDenoiseTarget(denoised_out, denoise_params)
+            except Exception:
+                if aov_out is not None:
+                    self.SetPathAovTarget(None)
+                if aov_depths is not None:
+                    self.SetPathAovDepths(None)
+                raise
         try:
             if times is None:
                 return plain(self, *args, **kw)
@@ -531,6 +621,8 @@ def _times_keyword(plain):
                 self.SetPathAovTarget(None)
             if aov_depths is not None:
                 self.SetPathAovDepths(None)
+            if denoised_out is not None:
+                self.SetPathDenoiseTarget(None)
     return RenderPath
 
 
@@ -650,6 +742,34 @@ class _LiveMedium:
         """the deep AOV of an orthographic view (scene.light_view): a deep shadow map, planes [K][h][w] (nrc_renderer_deep_ortho_aov).
         flat as for DeepRayAov, [h][w][4]."""
         return self._aov("DeepOrthoAov", "ortho", (view, w, h), levels, out, flat)
+
+    def DenoisedFrame(self, params=None):
+        """the current framebuffer filtered with the current view AOV (include/nrc_hpm.h, "Denoise"; nrc_renderer_denoised_frame): a torch
+        CUDA tensor view [height, width, 4].  Opt-in and biased: for low frame counts and previews.  Enqueued behind the frames rendered
+        so far, no host wait; the stream given at construction is ordered behind it.  The tensor is the renderer's buffer: the next
+        DenoisedFrame() rewrites it.  A renderer that draws a strip of a sharded frame refuses."""
+        import torch
+        p = make_c_denoise_params(params)
+        ptr = self._medium("denoised_frame")(self.h, C.byref(p))
+        if not ptr:
+            raise RuntimeError(self.L.nrc_last_error().decode() or "denoised_frame failed")
+        return _wrap_device(ptr, self.width * self.height * 16, torch.float32, (self.height, self.width, 4))
+
+    def SetPathDenoiseTarget(self, denoised, params=None, views=None):
+        """nrc_renderer_set_path_denoise_target: the next RenderPath writes view i's filtered final frame to denoised[i] (a contiguous
+        float32 CUDA tensor [views][height][width][4]; None cancels).  Needs an AOV target in the same call and no AOV depths.
+        RenderPath(..., aov_out=, denoised_out=) makes this call itself."""
+        if denoised is None:
+            _check(self._medium("set_path_denoise_target")(self.h, None, C.c_uint32(0), None))
+        else:
+            p = make_c_denoise_params(params)
+            _check(self._medium("set_path_denoise_target")(self.h, _dev_ptr(denoised), C.c_uint32(int(denoised.shape[0]) if views is None else int(views)),
+                                                           C.byref(p)))
+
+    def ExportDenoisedImageToFile(self, filePath, params=None):
+        """ExportImageWithAovToFile with B, G, R taken from DenoisedFrame(params) (nrc_renderer_export_exr_denoised)"""
+        p = make_c_denoise_params(params)
+        _check(self._medium("export_exr_denoised")(self.h, filePath.encode(), C.byref(p)))
 
     def ExportImageWithAovToFile(self, filePath):
         """ExportOutputImageToFile with the view AOV beside the colours: a scan-line EXR with FLOAT channels A (alpha of the AOV), B, G, R,

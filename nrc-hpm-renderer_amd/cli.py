@@ -29,6 +29,8 @@ linear in-between -- with one RenderPath(..., times=...) call.  A --time-scale b
 With `--sparse-keys` the keys are held as brick lists (NrcHpmRenderer.SetVolumeKeyBricks): every file's leaves are read over the aligned
 union bbox as for `--bricks`, no dense array is made per file (only the first list is densified, for creation), and the run prints the
 dense and brick byte counts held.  `--animate --bricks` stays refused: `--bricks` means stepping with SetVolumeBricks.
+Denoise (new): `--denoise [PASSES]` with `--export` writes the frame filtered by the AOV-guided a-trous filter (include/nrc_hpm.h, "Denoise")
+instead of the raw one; with `--orbit` and a file per view every view's final frame is filtered with its own AOV inside the one RenderPath call.
 """
 import argparse
 import math
@@ -75,6 +77,21 @@ def check_aov_args(args):
         raise SystemExit("SkyRenderer ERROR: --aov adds channels to the files --export writes: give --export")
     if args.gpus > 1:
         raise SystemExit("SkyRenderer ERROR: --aov is not available with --gpus (a sharded renderer holds its own columns' AOV only)")
+
+
+def check_denoise_args(args):
+    """what --denoise can be combined with (raises SystemExit)"""
+    passes = getattr(args, "denoise", None)
+    if passes is None:
+        return
+    if not 1 <= passes <= 6:
+        raise SystemExit("SkyRenderer ERROR: --denoise takes 1 .. 6 passes")
+    if not args.export:
+        raise SystemExit("SkyRenderer ERROR: --denoise filters the image --export writes: give --export")
+    if args.gpus > 1:
+        raise SystemExit("SkyRenderer ERROR: --denoise is not available with --gpus (a sharded renderer's local image has no pixel neighbours)")
+    if getattr(args, "holdout_sphere", None) is not None:
+        raise SystemExit("SkyRenderer ERROR: --denoise and --holdout-sphere exclude each other (the filter's guide is the whole rays' AOV)")
 
 
 def aov_planes(rgba, aov):
@@ -195,6 +212,10 @@ def main(argv=None):
                     help="with --export: the files also carry the view AOV (exact opacity and depth per pixel) as FLOAT channels -- A = alpha "
                          "instead of the framebuffer's constant 1, Z = distance to the first non-empty voxel, Zhalf = distance to optical depth "
                          "ln 2, tau = optical depth -- for compositing; one GPU")
+    ap.add_argument("--denoise", type=int, nargs="?", const=3, default=None, metavar="PASSES",
+                    help="with --export: the exported R, G, B are the frame filtered by the edge-avoiding a-trous filter that the view AOV guides "
+                         "(include/nrc_hpm.h, \"Denoise\"; 1 .. 6 passes, default 3).  Biased: for low frame counts and previews.  Combines with "
+                         "--aov; one GPU; not with --holdout-sphere")
     ap.add_argument("--holdout-sphere", type=float, default=None, metavar="R",
                     help="with --aov: the AOV is held out to a sphere of radius R at the origin -- the medium in FRONT of the sphere, along each "
                          "camera ray up to the sphere's depth (include/nrc_hpm.h, nrc_renderer_view_aov_to_depth); pixels beside the sphere keep "
@@ -234,6 +255,7 @@ def main(argv=None):
     animate = check_animate_args(args)
     n_views = check_orbit_args(args)
     check_aov_args(args)
+    check_denoise_args(args)
     check_ray_aov_args(args)
     check_deep_args(args)
 
@@ -356,12 +378,15 @@ def main(argv=None):
                 nrc_renderer.SetVolumeKeys(np.ascontiguousarray(np.stack(sequence)))
             times = animate_times(n_views, nrc_renderer.VolumeKeyCount(), args.time_scale)
         # (--aov: every view's AOV, of its camera and its in-between medium, lands beside its image; the frames are the same frames)
-        aovs = torch.empty((n_views, H, lw, 4), device="cuda", dtype=torch.float32) if per_view and args.aov else None
+        # (--denoise: every view's final frame filtered with the view's own AOV, which the path then computes whether or not --aov exports it)
+        dn = sc.denoise_params(passes=args.denoise) if per_view and args.denoise is not None else None
+        aovs = torch.empty((n_views, H, lw, 4), device="cuda", dtype=torch.float32) if per_view and (args.aov or dn is not None) else None
+        denoised = torch.empty((n_views, H, lw, 4), device="cuda", dtype=torch.float32) if dn is not None else None
         depths = None
         if aovs is not None and args.holdout_sphere is not None:
             depths = torch.from_numpy(np.stack([sphere_depth(api.camera_rays(v, lw, H), args.holdout_sphere) for v in views])).cuda()
         images = nrc_renderer.RenderPath(views, args.frames, train=True, out=None if per_view else False, times=times, aov_out=aovs,
-                                         aov_depths=depths)
+                                         aov_depths=depths, denoised_out=denoised, denoise_params=dn)
         loss = nrc.GetLoss(wait=True)
         failed = (math.isnan(loss) or math.isinf(loss)) and not args.skip_nonfinite      # (the all-reduced loss: the same on every rank)
         if failed:
@@ -369,8 +394,8 @@ def main(argv=None):
         elif rank == 0:
             print("orbit: %d views x %d frames, loss %.5f" % (n_views, args.frames, loss))
         if per_view and not failed:
-            host = images.cpu().numpy()
-            host_aov = aovs.cpu().numpy() if aovs is not None else None
+            host = (denoised if denoised is not None else images).cpu().numpy()
+            host_aov = aovs.cpu().numpy() if aovs is not None and args.aov else None
             for i, (path, img) in enumerate(zip(export_paths(args.export, n_views), host)):
                 if host_aov is not None:
                     io_exr.write_exr_channels(path, aov_planes(img, host_aov[i]))
@@ -415,10 +440,12 @@ def main(argv=None):
         depth = None
         if args.aov and args.holdout_sphere is not None:
             depth = torch.from_numpy(sphere_depth(api.camera_rays(cam, lw, H), args.holdout_sphere)).cuda()
+        dn = sc.denoise_params(passes=args.denoise) if args.denoise is not None else None
+        colour = (lambda: nrc_renderer.DenoisedFrame(dn)) if dn is not None else nrc_renderer.GetImage
         if args.aov and args.deep:      # the flat AOV and the K depths of one walk (whole rays, or out to the sphere)
             levels = sc.deep_levels(args.deep, DEEP_TAU_MAX)
             z, held = nrc_renderer.DeepViewAov(levels, depth=depth, flat=True)
-            planes = aov_planes(nrc_renderer.GetImage().cpu().numpy(), held.cpu().numpy())
+            planes = aov_planes(colour().cpu().numpy(), held.cpu().numpy())
             planes.update(deep_planes(z.cpu().numpy()))
             io_exr.write_exr_channels(args.export, planes)
             if rank == 0:
@@ -426,8 +453,12 @@ def main(argv=None):
         elif depth is not None:
             held = nrc_renderer.ViewAovToDepth(depth)
             io_exr.write_exr_channels(args.export, aov_planes(nrc_renderer.GetImage().cpu().numpy(), held.cpu().numpy()))
+        elif args.aov and dn is not None:
+            nrc_renderer.ExportDenoisedImageToFile(args.export, dn)
         elif args.aov:
             nrc_renderer.ExportImageWithAovToFile(args.export)
+        elif dn is not None:
+            io_exr.write_exr(args.export, colour().cpu().numpy())
         else:
             nrc_renderer.ExportOutputImageToFile(None, args.export)      # sharded: collective, rank 0 writes the whole frame
     if args.shadow_map and not failed and rank == 0:      # (every rank holds the whole medium: rank 0's map is the map)

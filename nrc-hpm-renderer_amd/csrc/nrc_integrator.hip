@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <string>
 
+#include "nrc_denoise.hpp"
 #include "nrc_math.h"
 #include "nrc_view_aov.hpp"
 #include "nrc_volume_keys.hpp"
@@ -2499,6 +2500,45 @@ __global__ __launch_bounds__(256) void k_vol_brick_index(const int32_t* __restri
     atomicMax(&cell_brick[((size_t)((uint32_t)z0 >> 3) * gy + ((uint32_t)y0 >> 3)) * gx + ((uint32_t)x0 >> 3)], first + i + 1u);
 }
 
+// ------------------------------------------------------------------------------------------------ the denoise filter (nrc_denoise.hpp)
+// The guide's two floats {alpha, z_front} of every pixel, packed once per call: the passes read 8 bytes per tap instead of 16.
+__global__ __launch_bounds__(256) void k_denoise_pack(const float4* __restrict__ aov, float2* __restrict__ guide, uint32_t n)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = aov[i];
+    guide[i] = make_float2(a.x, a.z);
+}
+
+// One pass: a lane per pixel, a workgroup per 32 x 8 tile (a wave covers two rows of 32 pixels: a tap is two 512-byte row segments of
+// colour per wave).  Every tap inside the image is loaded straight from memory under the lane's own predicate -- nothing is read outside the
+// image, nothing is staged: the 25 taps of neighbouring lanes overlap and are served by the L1 / L2.  in and out never alias (launch_denoise).
+struct DenoiseDevImage {
+    const float4* __restrict__ c;
+    const float2* __restrict__ g;
+    uint32_t w;
+    __device__ DenoiseRgba colour(int x, int y) const
+    {
+        const float4 v = c[(size_t)y * w + (uint32_t)x];
+        return DenoiseRgba{v.x, v.y, v.z, v.w};
+    }
+    __device__ DenoiseGuide guide(int x, int y) const
+    {
+        const float2 v = g[(size_t)y * w + (uint32_t)x];
+        return DenoiseGuide{v.x, v.y};
+    }
+};
+__global__ __launch_bounds__(256) void k_denoise_pass(const float4* __restrict__ in, const float2* __restrict__ guide, float4* __restrict__ out,
+                                                     uint32_t w, uint32_t h, DenoisePass ps)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    const uint32_t x = blockIdx.x * 32u + (threadIdx.x & 31u), y = blockIdx.y * 8u + (threadIdx.x >> 5);
+    if (x >= w || y >= h) return;
+    const DenoiseRgba r = denoise_pixel(DenoiseDevImage{in, guide, w}, ps, (int)w, (int)h, (int)x, (int)y);
+    out[(size_t)y * w + x] = make_float4(r.r, r.g, r.b, r.a);
+}
+
 }  // namespace
 
 // ================================================================================================ launchers
@@ -2876,6 +2916,33 @@ void launch_assemble_columns(const float* gathered, uint32_t world, uint32_t blo
 {
     hipLaunchKernelGGL(k_assemble_columns, dim3(ceil_div(gw, 256), h), dim3(256), 0, s, (const float4*)gathered, world, block_log2, gw, h, max_lw,
                        (float4*)out);
+    NRC_HIP(hipGetLastError());
+}
+
+// ---- the denoise filter.  Scratch: [passes > 1: image][passes > 2: image][guide pairs]; 16-byte aligned.
+static size_t denoise_images(uint32_t passes) { return passes > 2u ? 2u : (passes > 1u ? 1u : 0u); }
+size_t denoise_scratch_bytes(uint32_t w, uint32_t h, uint32_t passes) { return (size_t)w * h * (16u * denoise_images(passes) + 8u); }
+void launch_denoise(const float* rgba, const float* aov, uint32_t w, uint32_t h, const DenoiseParams& p, float* out, void* scratch, hipStream_t s)
+{
+    if (const char* what = denoise_params_error(p)) fail(std::string("denoise: ") + what);
+    if (w == 0u || h == 0u || w > kDenoiseMaxSide || h > kDenoiseMaxSide || (uint64_t)w * h > 0x7fffffffull || ceil_div(h, 8) > 65535u)
+        fail("denoise: bad image size");
+    if ((((uintptr_t)rgba) | ((uintptr_t)aov) | ((uintptr_t)out) | ((uintptr_t)scratch)) & 15u) fail("denoise: the images and the scratch must be 16-byte aligned");
+    const size_t px = (size_t)w * h, img = px * 16u, need = denoise_scratch_bytes(w, h, p.passes);
+    const char *o0 = (const char*)out, *s0 = (const char*)scratch, *c0 = (const char*)rgba, *a0 = (const char*)aov;
+    auto overlap = [](const char* a, size_t na, const char* b, size_t nb) { return a < b + nb && b < a + na; };
+    if (overlap(o0, img, c0, img) || overlap(o0, img, a0, img) || overlap(o0, img, s0, need)) fail("denoise: d_out overlaps an input or the scratch (no in-place operation)");
+    if (overlap(s0, need, c0, img) || overlap(s0, need, a0, img)) fail("denoise: the scratch overlaps an input");
+    float4* ping = (float4*)scratch;
+    float4* pong = ping + px;
+    float2* guide = (float2*)(ping + px * denoise_images(p.passes));
+    hipLaunchKernelGGL(k_denoise_pack, dim3(ceil_div((uint32_t)px, 256)), dim3(256), 0, s, (const float4*)aov, guide, (uint32_t)px);
+    const float4* src = (const float4*)rgba;
+    for (uint32_t pass = 0; pass < p.passes; pass++) {      // the last pass writes the output
+        float4* dst = pass + 1u == p.passes ? (float4*)out : ((pass & 1u) ? pong : ping);
+        hipLaunchKernelGGL(k_denoise_pass, dim3(ceil_div(w, 32), ceil_div(h, 8)), dim3(256), 0, s, src, (const float2*)guide, dst, w, h, denoise_pass(p, pass));
+        src = dst;
+    }
     NRC_HIP(hipGetLastError());
 }
 

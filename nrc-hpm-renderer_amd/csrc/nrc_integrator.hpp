@@ -3,6 +3,7 @@
 // data/shader/mc/render.comp and data/shader/include/{random,volume,dir_gen,path_trace}.glsl.
 #pragma once
 #include "nrc_common.hpp"
+#include "nrc_denoise.hpp"
 #include "nrc_hot_tiles.hpp"
 #include "nrc_view_aov.hpp"
 
@@ -189,6 +190,12 @@ struct AovPlanes { uint32_t n_levels; const float* levels; float* z; };
 void launch_ray_aov_list(const DevScene& sc, const DevFrame& fr, size_t n, const float* rays, float* out, const AovPlanes* deep, hipStream_t s);
 void launch_ray_aov_view_depth(const DevScene& sc, const DevCamera& cam, const DevFrame& fr, const float* depth, float* out, const AovPlanes* deep, hipStream_t s);
 void launch_ray_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrthoView& view, uint32_t w, uint32_t h, float* out, const AovPlanes* deep, hipStream_t s);
+
+// the denoise filter (nrc_denoise.hpp): rgba [h][w][4] filtered with the guide aov [h][w][4] -> out [h][w][4], all device memory, 16-byte aligned.
+// One launch that packs the guide and one per pass, ping-ponging between the scratch's images (denoise_scratch_bytes); the last pass writes
+// out.  Refused before anything is enqueued: bad parameters, out overlapping an input or the scratch.
+size_t denoise_scratch_bytes(uint32_t w, uint32_t h, uint32_t passes);
+void launch_denoise(const float* rgba, const float* aov, uint32_t w, uint32_t h, const DenoiseParams& p, float* out, void* scratch, hipStream_t s);
 
 // ring: {uint head, uint tail, RayInfo[ring_size]}; scratch: uint32[2*T + 4]
 // start == nullptr: the whole of prep_train_rays.comp (scan, pop / trace / write, ring push).  start != nullptr (long train paths, the split

@@ -412,6 +412,25 @@ def deep_levels(k, tau_max):
     return levels
 
 
+def denoise_params(**kw):
+    """The parameters of the denoise filter (api.Denoise / DenoisedFrame / RenderPath(..., denoised_out=); include/nrc_hpm.h, "Denoise") as a
+    dict: the defaults -- passes 3, sigma_alpha 0.1, sigma_depth 4.0 (in the units of t), sigma_color +inf (the colour term off),
+    color_decay 0.5 -- overridden by the keywords, checked as the library checks them."""
+    p = dict(passes=3, sigma_alpha=0.1, sigma_depth=4.0, sigma_color=math.inf, color_decay=0.5)
+    for k, v in kw.items():
+        if k not in p:
+            raise ValueError("denoise_params: unknown parameter %r" % (k,))
+        p[k] = int(v) if k == "passes" else float(v)
+    if not 1 <= p["passes"] <= 6:
+        raise ValueError("denoise_params: passes must be 1 .. 6")
+    for k in ("sigma_alpha", "sigma_depth", "sigma_color"):
+        if not p[k] > 0.0:      # (NaN included)
+            raise ValueError("denoise_params: %s must be > 0 (+inf switches the term off)" % k)
+    if not 0.0 < p["color_decay"] <= 1.0:
+        raise ValueError("denoise_params: color_decay must lie in (0, 1]")
+    return p
+
+
 def deep_tau_bracket(levels, z, flat, depth):
     """What a deep AOV's samples say about the optical depth in front of `depth` -- what a compositor or a shadow look-up does with them.
     levels [K], z [K][...] (the planes), flat [...][4] (the flat result of the same call), depth [...] (an image or array, or a scalar).
