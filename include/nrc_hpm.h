@@ -504,7 +504,10 @@ int nrc_renderer_destroy(nrc_renderer_t* r);
  * 6 train input [T][5], 7 train target [T][3], 8 train ring {head, tail, RayInfo[ring]}; self-training (nrc_config.self_train) of the
  * latest TRAINING frame, one entry per (ray i, sample s) at i * spp + s: 9 tail queries [T*spp][5] (zeros where there is no tail),
  * 10 {light.rgb, factor} [T*spp][4] (factor 0: no tail), 11 tail inference outputs [T*spp][3] (defined where there is a tail) --
- * NRC_ERR_INVALID for a renderer without self-training.  Buffers 4 and 5 are handed out in the
+ * NRC_ERR_INVALID for a renderer without self-training; 12 the frame's list of scattered pixels as gen_rays wrote it, uint32 {count,
+ * indices[] in no particular order}, an index being ((y / 8) * ceil(w / 8) + x / 8) * 64 + (y % 8) * 8 + x % 8; the frame's compositing
+ * pass has cleared the count for the set's next frame, the entries (as many as buffer 1 holds ones) stay -- NRC_ERR_INVALID for a
+ * renderer that keeps no such list.  Buffers 4 and 5 are handed out in the
  * reference's order, query x*H+y (nrc/prep_infer_rays.comp:31), as a COPY made by this call: inside the renderer they are
  * tile-major (the 64 queries of an 8x8 pixel tile contiguous), and the cache's own API (nrc_cache_init / infer) speaks x*H+y
  * whatever its caller's order is.  Entries of pixels that did not scatter (info != 1) are zeros in both copies: the reference's zero-filled
@@ -578,6 +581,10 @@ int nrc_renderer_set_stage_events(nrc_renderer_t* r, int on);
 /* density look-ups executed by gen_rays (measurement: algorithmic bytes of the integrator).
  * Returns the count accumulated so far in *out (may be NULL), then enables/disables + zeroes the device counter. */
 int nrc_renderer_count_fetches(nrc_renderer_t* r, int enable, unsigned long long* out);
+/* Of the look-ups counted above, those that ratio tracking kept from memory because their walk's transmittance was already exactly 0
+ * and that the occupancy bits would have sent there: accumulated since count_fetches last zeroed the counters,
+ * read before the next count_fetches call. */
+int nrc_renderer_masked_fetches(nrc_renderer_t* r, unsigned long long* out);
 /* train grid chosen by CalcTrainSubset (src/NrcHpmRenderer.cu:612-642): {TW, TH, xDist, yDist, ringSize} */
 int nrc_renderer_train_grid(nrc_renderer_t* r, uint32_t out5[5]);
 

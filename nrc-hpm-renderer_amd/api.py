@@ -103,7 +103,7 @@ ABI_SYMBOLS = [
     "nrc_renderer_export_exr_denoised", "nrc_mc_renderer_export_exr_denoised",
     "nrc_renderer_set_show_nrc", "nrc_renderer_set_frame_random", "nrc_renderer_framebuffer", "nrc_renderer_framebuffer_on",
     "nrc_renderer_export_exr",
-    "nrc_renderer_frame_time_ms", "nrc_renderer_stage_stats", "nrc_renderer_frame_timeline", "nrc_set_wave_priority_raise", "nrc_renderer_destroy", "nrc_renderer_buffer", "nrc_renderer_count_fetches",
+    "nrc_renderer_frame_time_ms", "nrc_renderer_stage_stats", "nrc_renderer_frame_timeline", "nrc_set_wave_priority_raise", "nrc_renderer_destroy", "nrc_renderer_buffer", "nrc_renderer_count_fetches", "nrc_renderer_masked_fetches",
     "nrc_renderer_train_grid",
     "nrc_mc_renderer_create", "nrc_mc_renderer_render", "nrc_mc_renderer_set_camera", "nrc_mc_renderer_set_blend",
     "nrc_mc_renderer_set_frame_random", "nrc_mc_renderer_framebuffer", "nrc_mc_renderer_export_exr",
@@ -1168,7 +1168,7 @@ class NrcHpmRenderer(_LiveMedium):
     """en::NrcHpmRenderer (src/NrcHpmRenderer.cu).  `queue` arguments of the reference become the HIP stream."""
     _PREFIX = "nrc_renderer_"
     BUF = dict(primary=0, info=1, origin=2, dir=3, infer_input=4, infer_output=5, train_input=6, train_target=7, ring=8,
-               tail_query=9, tail_record=10, tail_output=11)
+               tail_query=9, tail_record=10, tail_output=11, live=12)
 
     def __init__(self, width, height, blend, camera, appConfig, hpmScene, nrc, tile=None, stream=None):
         self.L = load_library()
@@ -1365,7 +1365,7 @@ class NrcHpmRenderer(_LiveMedium):
         p = self.L.nrc_renderer_buffer(self.h, C.c_int(self.BUF[name]), C.byref(nbytes))
         if not p:
             _check(-1)
-        if name == "ring":
+        if name in ("ring", "live"):
             return _wrap_device(p, nbytes.value, torch.int32, (nbytes.value // 4,))
         inner = {"primary": 4, "info": 1, "origin": 4, "dir": 4, "infer_input": 5, "infer_output": 3,
                  "train_input": 5, "train_target": 3, "tail_query": 5, "tail_record": 4, "tail_output": 3}[name]
@@ -1379,6 +1379,12 @@ class NrcHpmRenderer(_LiveMedium):
     def CountFetches(self, enable=True):
         v = C.c_ulonglong(0)
         _check(self.L.nrc_renderer_count_fetches(self.h, C.c_int(int(enable)), C.byref(v)))
+        return v.value
+
+    def MaskedFetches(self):
+        """of the look-ups CountFetches has counted since it was last called, those a dead walk (transmittance exactly 0) kept from memory"""
+        v = C.c_ulonglong(0)
+        _check(self.L.nrc_renderer_masked_fetches(self.h, C.byref(v)))
         return v.value
 
     def Destroy(self):

@@ -153,6 +153,8 @@ struct CtxT {
     const DevScene& sc;
     float rng;              // randomState
     uint32_t fetches;
+    uint32_t masked = 0u;   // look-ups the dead-walk rule kept from memory (ratio_track), counted beside `fetches`: the WAVE's sum, uniform
+    static constexpr bool counting = COUNT;
     // raw buffer view of the volume: offsets >= the voxel count read 0, which is the sampler's black border
     __amdgpu_buffer_rsrc_t vol = __builtin_amdgcn_make_buffer_rsrc((void*)sc.density, 0, (int)(sc.nx * sc.ny * sc.nz), 0x00020000);
     const uint32_t* occ = nullptr;      // LDS copy of DevScene::occ_bits (load_occupancy), or nullptr
@@ -168,6 +170,10 @@ struct CtxT {
     __device__ __forceinline__ void count(uint32_t n)
     {
         if constexpr (COUNT) fetches += n;
+    }
+    __device__ __forceinline__ void count_masked(uint32_t n)
+    {
+        if constexpr (COUNT) masked += n;
     }
 };
 
@@ -304,6 +310,9 @@ __device__ __forceinline__ float get_density(C& c, V3 p)
 // chain does not depend on the fetched densities).  fetch2_addr computes both voxel indices (slots that are masked off or
 // outside the volume get offset 2^31: the raw buffer returns the sampler's black border without a memory access), fetch2_load
 // issues the two 1-byte gathers, fetch2_density turns the bytes into getDensity()'s value, volume.glsl:31-39.
+// `dead`: the lane's walk has a transmittance of exactly 0 (ratio_track): both slots get the border offset whatever they hold.
+// n_masked (counting builds): how many slots of the wave `dead` kept from memory, i.e. that the occupancy bits would have sent there
+// (a wave-uniform sum: a per-lane counter is a register the counting kernels do not have).
 struct Addr2 {
     uint32_t i0, i1;
 };
@@ -311,7 +320,8 @@ struct Fetch2 {
     uint32_t b0, b1;
 };
 template <class C>
-__device__ __forceinline__ Addr2 fetch2_addr(const C& c, V3 dir, V3 start, float t1, float t2, bool first, bool second)
+__device__ __forceinline__ Addr2 fetch2_addr(const C& c, V3 dir, V3 start, float t1, float t2, bool first, bool second, bool dead = false,
+                                             uint32_t* n_masked = nullptr)
 {
     const DevScene& s = c.sc;
     const f2 t = f2{t1, t2};
@@ -346,6 +356,9 @@ __device__ __forceinline__ Addr2 fetch2_addr(const C& c, V3 dir, V3 start, float
         in0 &= ((c.occ[c0 >> 5] >> (c0 & 31u)) & 1u) != 0u;
         in1 &= ((c.occ[c1 >> 5] >> (c1 & 31u)) & 1u) != 0u;
     }
+    if (n_masked != nullptr) *n_masked = (uint32_t)(__popcll(__ballot(dead & in0)) + __popcll(__ballot(dead & in1)));
+    in0 &= !dead;
+    in1 &= !dead;
     return Addr2{in0 ? idx0 : 0x80000000u, in1 ? idx1 : 0x80000000u};
 }
 template <class C>
@@ -441,6 +454,9 @@ __device__ __forceinline__ RatioTrip ratio_trip(float rng, float t, float t_max,
     r.second = !(r.t2 >= t_max);
     return r;
 }
+// a per-lane predicate as a wave-uniform 64-bit lane mask and back (why the loops carry masks: see ratio_track)
+__device__ __forceinline__ bool lane_bool(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+__device__ __forceinline__ unsigned long long lane_mask(bool b) { return __builtin_amdgcn_ballot_w64(b); }
 // ---- thin trips: two lanes per surviving walk ---------------------------------------------------------------------------------
 // A tracking loop runs until its last walk ends: the trips issued with at most 32 of the 64 lanes still walking cost 28 % of the
 // launch (round 2's cut-tail build, docs/MEASUREMENT_LOG.md).  When a loop is down to 32 walks or fewer they are handed to lane PAIRS (lane p and p + 32, state pushed
@@ -489,6 +505,7 @@ __device__ __forceinline__ void ratio_pairs(C& c, unsigned long long am, bool al
     const V3 st = v3(y[5], y[6], y[7]), dr = v3(y[8], y[9], y[10]);
     bool act = (lane & 31u) < k;
     float rf = R0;
+    unsigned long long deadm = lane_mask(T == 0.0f);      // pairs whose product is exactly 0 and stays so: see ratio_track
     for (;;) {
         const unsigned long long actm = __ballot(act);
         if (actm == 0ull) break;
@@ -507,10 +524,12 @@ __device__ __forceinline__ void ratio_pairs(C& c, unsigned long long am, bool al
         const bool d4 = go & (nn + 4u <= 128u); rf = d4 ? R4 : rf; const bool p4 = d4 & !(t4 >= tm); go = p4;
         // look-ups: collisions 1, 2 on the lower lane, 3, 4 on the upper one
         const bool ma = is_b ? p3 : p1, mb = is_b ? p4 : p2;
-        const Addr2 ad = fetch2_addr(c, dr, st, is_b ? t3 : t1, is_b ? t4 : t2, ma, mb);
+        uint32_t n_masked = 0u;
+        const Addr2 ad = fetch2_addr(c, dr, st, is_b ? t3 : t1, is_b ? t4 : t2, ma, mb, lane_bool(deadm), C::counting ? &n_masked : nullptr);
         const Fetch2 fa = fetch2_load(c, ad);
         const f2 dens = fetch2_density(c.sc, fa);
         c.count((ma ? 1u : 0u) + (mb ? 1u : 0u));
+        c.count_masked(n_masked);
         float f1, f2_, f3, f4;
         pair_both(nrc_fmaf_(-dens.x, inv, 1.0f), &f1, &f3);
         pair_both(nrc_fmaf_(-dens.y, inv, 1.0f), &f2_, &f4);
@@ -518,6 +537,7 @@ __device__ __forceinline__ void ratio_pairs(C& c, unsigned long long am, bool al
         T = p2 ? T * f2_ : T;
         T = p3 ? T * f3 : T;
         T = p4 ? T * f4 : T;
+        deadm = lane_mask(T == 0.0f);
         act = p4 & (nn + 4u < 128u);
         nn += 4u;
         R0 = R4;
@@ -541,8 +561,6 @@ __device__ __forceinline__ void ratio_pairs(C& c, unsigned long long am, bool al
 // 30 of them in front of every delta trip) -- and a scalar instruction costs a SIMD as much issue time as a vector one here
 // (tools/issue_mix.hip: at five waves per SIMD a v_fma_f32 1.6 clocks, a v_fma_f32 + s_and_b64 pair 3.6).  A uniform mask is an
 // ordinary 64-bit value: its phi is a copy.  lane_bool() hands it to v_cndmask as the select mask (no instruction).
-__device__ __forceinline__ bool lane_bool(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
-__device__ __forceinline__ unsigned long long lane_mask(bool b) { return __builtin_amdgcn_ballot_w64(b); }
 
 // Round 5 measured the next step of that idea and took it out again (commit 4f700df has the code; DESIGN.md section 4 "Lane groups"): every
 // surviving walk on a GROUP of L = 2^floor(log2(64 / walks alive)) lanes, chunks of 2 Lc collisions per iteration, the walk's serial
@@ -559,6 +577,12 @@ __device__ __forceinline__ float ratio_track(C& c, V3 start, V3 end, bool valid 
     float tr = 1.0f;
     float rng = c.rng;
     unsigned long long alive_m = lane_mask(valid);
+    // Dead walks: only tr leaves the walk, every factor is finite, so a tr of exactly +-0 stays +-0 and what its
+    // lane would still fetch is never used.  Such a lane's look-ups get the border offset (one trip late: trip j + 1 is located before
+    // trip j is consumed -- a look-up too many, never one too few).  c.count() keeps counting the algorithm's collisions.  (A reduced
+    // trip for waves whose walking lanes are all dead -- the chain alone -- was measured and did not move the frame: section 4.4.)
+    unsigned long long dead_m = 0ull;
+    uint32_t pend = 0u;                        // (counting builds) the wave's masked look-ups of the located trip that would have gone to memory
     RatioTrip a = ratio_trip(rng, 0.0f, t_max, inv);
     unsigned long long live1_m = lane_mask(a.live1), second_m = lane_mask(a.second);
     Addr2 ia = fetch2_addr(c, dir, start, a.t1, a.t2, a.live1, a.live1 & a.second);
@@ -583,12 +607,17 @@ __device__ __forceinline__ float ratio_track(C& c, V3 start, V3 end, bool valid 
         const unsigned long long more_m = last ? 0ull : two_m;
         const bool more = lane_bool(more_m);
         const RatioTrip b = ratio_trip(a.s2, a.t2, t_max, inv);      // ... fly while the next trip is located
-        const Addr2 ib = fetch2_addr(c, dir, start, b.t1, b.t2, more & b.live1, more & b.live1 & b.second);
+        uint32_t pend_b = 0u;
+        const Addr2 ib = fetch2_addr(c, dir, start, b.t1, b.t2, more & b.live1, more & b.live1 & b.second, lane_bool(dead_m),
+                                     C::counting ? &pend_b : nullptr);
         __builtin_amdgcn_sched_barrier(0);
         const f2 dens = fetch2_density(c.sc, fa);
         c.count(alive ? (lane_bool(second_m) ? 2u : 1u) : 0u);
+        c.count_masked(pend);
+        pend = pend_b;
         tr = alive ? tr * nrc_fmaf_(-dens.x, inv, 1.0f) : tr;
         tr = lane_bool(two_m) ? tr * nrc_fmaf_(-dens.y, inv, 1.0f) : tr;
+        dead_m = lane_mask(tr == 0.0f);
         rng = lane_bool(alive_m & ~more_m) ? a.s2 : rng;              // ends after collision 1 / after the 128th collision
         alive_m = more_m;
         live1_m = lane_mask(b.live1);
@@ -1379,7 +1408,10 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK, NRC_GEN_WAVES_PER_SIMD
     // per-pixel look-up count in the w component of the origin image (tools/lane_model.py)
     if (inside && full_vertex_images != 0) reinterpret_cast<float*>(origin)[4 * ((size_t)y * fr.w + lx) + 3] = (float)c.fetches;
 #endif
-    if constexpr (COUNT) count_fetches(fetch_counter, c.fetches);
+    if constexpr (COUNT) {      // [0] the algorithm's look-ups, [1] those of them the dead-walk rule kept from memory
+        count_fetches(fetch_counter, c.fetches);
+        if (fetch_counter != nullptr && (threadIdx.x & 63u) == 0u && c.masked != 0u) atomicAdd(fetch_counter + 1, (unsigned long long)c.masked);
+    }
     // what this tile cost (shader cycles): next frames launch the costliest tiles first (k_tile_order).  (Not for a hot wave: what
     // it measured is this frame's one pixel in a capped state, not the tile.)
     if (fr.tile_cost != nullptr && !hot_wave && (threadIdx.x & 63u) == 0) store_tile_cost(fr, slot, __builtin_amdgcn_s_memtime() - t_start);
@@ -1447,7 +1479,10 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK, NRC_CAMERA_WAVES_PER_S
                                     blend_factor * col.z + ib * prev.z, blend_factor * a + ib * prev.w);
         if (info) info[pix] = a;
     }
-    if constexpr (COUNT) count_fetches(fetch_counter, c.fetches);
+    if constexpr (COUNT) {      // [0] the algorithm's look-ups, [1] those of them the dead-walk rule kept from memory
+        count_fetches(fetch_counter, c.fetches);
+        if (fetch_counter != nullptr && (threadIdx.x & 63u) == 0u && c.masked != 0u) atomicAdd(fetch_counter + 1, (unsigned long long)c.masked);
+    }
     if (fr.tile_cost != nullptr && !hot_wave && (threadIdx.x & 63u) == 0)      // see k_gen_rays / k_tile_order (a longer walk: 8 192-cycle classes)
         store_tile_cost(fr, slot, (__builtin_amdgcn_s_memtime() - t_start) >> 4);
 }
