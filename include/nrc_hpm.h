@@ -341,6 +341,10 @@ int nrc_renderer_render_path(nrc_renderer_t* r, uint32_t n_cameras, const nrc_ca
  * (ceil(tiles / 32) bit words, tile ty * ceil(w / 8) + tx at bit id % 32 of word id / 32, + the trailing "mask off for this camera"
  * word); 0 words when the frame uses no mask (empty skip off, no perspective camera, a medium too dense for it) */
 size_t nrc_renderer_tile_mask(nrc_renderer_t* r, uint32_t* host_out, size_t capacity);
+/* diagnostics: the far bounds built with that mask, one float per tile (index ty * ceil(w / 8) + tx): an upper bound of the distance from
+ * the camera position behind which no camera ray of the tile meets density again (DESIGN.md section 4.4 "Far cut"; 0: no occupancy box
+ * touches the tile).  Same calling pattern; 0 floats when the frame uses no mask. */
+size_t nrc_renderer_tile_far(nrc_renderer_t* r, float* host_out, size_t capacity);
 int nrc_renderer_set_blend(nrc_renderer_t* r, int blend);
 /* The uniform-buffer half of the scene -- DirLight / PointLight / VolumeData / HdrEnvMap strength (src/DirLight.cpp:31-49,
  * src/HpmScene.cpp:56-76 `HpmScene::Update`, the ImGui light editors): takes effect with the next Render and does not reset
@@ -585,6 +589,10 @@ int nrc_renderer_count_fetches(nrc_renderer_t* r, int enable, unsigned long long
  * and that the occupancy bits would have sent there: accumulated since count_fetches last zeroed the counters,
  * read before the next count_fetches call. */
 int nrc_renderer_masked_fetches(nrc_renderer_t* r, unsigned long long* out);
+/* The far cut's proof on the device, counted beside the look-ups (the counting launches walk every camera ray whole):
+ * out[0] the camera walk's collisions at or behind the lane's cut in waves the cut applies to, out[1] those of them that met density (a
+ * non-zero byte or an acceptance) -- 0 on every frame when the cut is sound.  Accumulated and read like masked_fetches. */
+int nrc_renderer_cut_fetches(nrc_renderer_t* r, unsigned long long out[2]);
 /* train grid chosen by CalcTrainSubset (src/NrcHpmRenderer.cu:612-642): {TW, TH, xDist, yDist, ringSize} */
 int nrc_renderer_train_grid(nrc_renderer_t* r, uint32_t out5[5]);
 
@@ -608,6 +616,7 @@ int nrc_mc_renderer_set_scene_params(nrc_mc_renderer_t* r, const nrc_scene* scen
 int nrc_mc_renderer_render_path(nrc_mc_renderer_t* r, uint32_t n_cameras, const nrc_camera* cameras, uint32_t frames_per_camera,
                                 const float* frame_randoms, float* d_frames);
 size_t nrc_mc_renderer_tile_mask(nrc_mc_renderer_t* r, uint32_t* host_out, size_t capacity);
+size_t nrc_mc_renderer_tile_far(nrc_mc_renderer_t* r, float* host_out, size_t capacity);   /* see nrc_renderer_tile_far */
 /* see nrc_renderer_set_volume / nrc_renderer_volume_buffer (one stream: the volume is rewritten in stream order behind the frames) */
 int nrc_mc_renderer_set_volume(nrc_mc_renderer_t* r, const void* density, uint32_t nx, uint32_t ny, uint32_t nz, int format, int on_device);
 /* see nrc_renderer_set_volume_bricks */

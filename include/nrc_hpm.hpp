@@ -538,6 +538,13 @@ public:
         if (!m.empty() && nrc_renderer_tile_mask(h_, m.data(), m.size()) != m.size()) nrc_check(NRC_ERR_STATE);
         return m;
     }
+    // ... and the far bounds built with it, one float per 8x8 tile -- nrc_renderer_tile_far
+    std::vector<float> TileFar() const
+    {
+        std::vector<float> m(nrc_renderer_tile_far(h_, nullptr, 0));
+        if (!m.empty() && nrc_renderer_tile_far(h_, m.data(), m.size()) != m.size()) nrc_check(NRC_ERR_STATE);
+        return m;
+    }
     void SetBlend(bool blend) { nrc_check(nrc_renderer_set_blend(h_, blend ? 1 : 0)); }
     void SetSceneParams(const nrc_scene& scene) { nrc_check(nrc_renderer_set_scene_params(h_, &scene)); }   // HpmScene::Update
     void SetSceneParams(const HpmScene& scene) { SetSceneParams(scene.Scene()); }

@@ -91,6 +91,7 @@ ABI_SYMBOLS = [
     "nrc_renderer_set_volume_key_bricks", "nrc_mc_renderer_set_volume_key_bricks", "nrc_renderer_volume_key_bytes", "nrc_mc_renderer_volume_key_bytes",
     "nrc_renderer_set_volume_time", "nrc_mc_renderer_set_volume_time", "nrc_renderer_render_path_timed", "nrc_mc_renderer_render_path_timed",
     "nrc_renderer_render_path", "nrc_mc_renderer_render_path", "nrc_renderer_tile_mask", "nrc_mc_renderer_tile_mask",
+    "nrc_renderer_tile_far", "nrc_mc_renderer_tile_far", "nrc_renderer_cut_fetches",
     "nrc_renderer_view_aov", "nrc_mc_renderer_view_aov", "nrc_renderer_set_path_aov_target", "nrc_mc_renderer_set_path_aov_target",
     "nrc_renderer_export_exr_aov", "nrc_mc_renderer_export_exr_aov", "nrc_test_view_aov_host",
     "nrc_renderer_ray_aov", "nrc_mc_renderer_ray_aov", "nrc_renderer_view_aov_to_depth", "nrc_mc_renderer_view_aov_to_depth",
@@ -172,7 +173,7 @@ def load_library():
         if hasattr(L, name):
             getattr(L, name).restype = C.c_void_p
             getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
-    for name in ("nrc_renderer_tile_mask", "nrc_mc_renderer_tile_mask"):
+    for name in ("nrc_renderer_tile_mask", "nrc_mc_renderer_tile_mask", "nrc_renderer_tile_far", "nrc_mc_renderer_tile_far"):
         if hasattr(L, name):      # (an older build loaded through NRC_HPM_LIB has no camera paths)
             getattr(L, name).restype = C.c_size_t
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -642,6 +643,16 @@ class _LiveMedium:
         out = np.zeros(n, np.uint32)
         if n and fn(self.h, out.ctypes.data_as(C.c_void_p), C.c_size_t(n)) != n:
             raise RuntimeError(self.L.nrc_last_error().decode() or "tile_mask failed")
+        return out
+
+    def TileFar(self):
+        """the far bounds built with that mask (numpy float32, one per 8x8 tile, row-major; empty: no mask in use): see
+        nrc_renderer_tile_far; synchronises the renderer"""
+        fn = self._medium("tile_far")
+        n = fn(self.h, None, C.c_size_t(0))
+        out = np.zeros(n, np.float32)
+        if n and fn(self.h, out.ctypes.data_as(C.c_void_p), C.c_size_t(n)) != n:
+            raise RuntimeError(self.L.nrc_last_error().decode() or "tile_far failed")
         return out
 
     def ViewAov(self):
@@ -1386,6 +1397,13 @@ class NrcHpmRenderer(_LiveMedium):
         v = C.c_ulonglong(0)
         _check(self.L.nrc_renderer_masked_fetches(self.h, C.byref(v)))
         return v.value
+
+    def CutFetches(self):
+        """the far cut's proof since CountFetches was last called: (the camera walk's collisions at or behind the cut in waves it applies
+        to, those of them that met density -- 0 when the cut is sound)"""
+        v = (C.c_ulonglong * 2)()
+        _check(self.L.nrc_renderer_cut_fetches(self.h, v))
+        return int(v[0]), int(v[1])
 
     def Destroy(self):
         if self.h:

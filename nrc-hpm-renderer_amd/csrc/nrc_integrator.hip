@@ -175,6 +175,12 @@ struct CtxT {
     {
         if constexpr (COUNT) masked += n;
     }
+    // the far cut's proof (delta_track): the camera walk's collisions at or behind the cut, and those of them that met density; the WAVE's sums
+    uint32_t cut_n = 0u, cut_met = 0u;
+    __device__ __forceinline__ void count_cut(unsigned long long behind, unsigned long long met)
+    {
+        if constexpr (COUNT) { cut_n += (uint32_t)__popcll(behind); cut_met += (uint32_t)__popcll(behind & met); }
+    }
 };
 
 // The integrator is bound by the rate at which a CU gets scattered bytes out of the L2 (tools/gather_rate.hip: 2.3 cycles per
@@ -213,6 +219,15 @@ __device__ __forceinline__ uint32_t scalar_load(const uint32_t* p)
     uint32_t r;
     asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(r) : "s"(p) : "memory");
     return r;
+}
+__device__ __forceinline__ void scalar_load3(const uint32_t* p, const uint32_t* q, const uint32_t* r, uint32_t* a, uint32_t* b, uint32_t* c)
+{
+    uint32_t r0, r1, r2;
+    asm volatile("s_load_dword %0, %3, 0x0\n\ts_load_dword %1, %4, 0x0\n\ts_load_dword %2, %5, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(r0), "=&s"(r1), "=&s"(r2) : "s"(p), "s"(q), "s"(r) : "memory");
+    *a = r0;
+    *b = r1;
+    *c = r2;
 }
 __device__ __forceinline__ void scalar_load2(const uint32_t* p, const uint32_t* q, uint32_t* a, uint32_t* b)
 {
@@ -743,8 +758,14 @@ __device__ __forceinline__ DeltaTrip delta_trip(float rng, float t, float t_max,
     r.second = !(r.t2 >= t_max);
     return r;
 }
-template <bool UNI = false, class C>
-__device__ __forceinline__ V3 delta_track(C& c, V3 ro, V3 rd, bool* volume_exit, bool valid = true)
+// CUT, `cut` (the first walk of a camera path, DESIGN.md section 4.4 "Far cut"): behind t = cut the ray is in empty space for good and the
+// lane's RNG state is not a capped one, so every further collision would be rejected and the walk would leave the volume before the cap --
+// it leaves at the cut instead: t_max becomes min(t_max, cut).  Hits lie in front of the cut and are the whole walk's; what a leaving lane
+// returns (a point of the shorter segment) and its RNG state are never read.  +inf: no cut.  The counting instantiations walk whole, so
+// that c.count() stays the algorithm's number, and count the collisions at or behind the cut and those of them that met density
+// (a non-zero byte, or an acceptance): the second number is 0 when the cut is sound.
+template <bool UNI = false, bool CUT = false, class C>
+__device__ __forceinline__ V3 delta_track(C& c, V3 ro, V3 rd, bool* volume_exit, bool valid = true, float cut = __builtin_huge_valf())
 {
     V3 en, ex;
     if constexpr (UNI) {      // lanes without a walk march a harmless ray (from the centre along +z): the march must end for them too
@@ -752,7 +773,8 @@ __device__ __forceinline__ V3 delta_track(C& c, V3 ro, V3 rd, bool* volume_exit,
     } else {
         find_entry_exit(c, ro, rd, &en, &ex);
     }
-    const float t_max = length(sub(ex, ro));
+    float t_max = length(sub(ex, ro));
+    if constexpr (CUT && !C::counting) t_max = fminf(t_max, cut);
     const float inv = c.sc.inv_max_density;
     float rng = c.rng;
     // loop-carried predicates as uniform lane masks (see ratio_track)
@@ -786,6 +808,10 @@ __device__ __forceinline__ V3 delta_track(C& c, V3 ro, V3 rd, bool* volume_exit,
         const unsigned long long alive3_m = alive2_m & second_m;
         c.count(lane_bool(alive3_m) ? 1u : 0u);
         const unsigned long long acc2_m = alive3_m & lane_mask(dens.y > a.a2);
+        if constexpr (CUT && C::counting) {
+            c.count_cut(alive_m & lane_mask(a.t1 >= cut), acc1_m | lane_mask(fa.b0 != 0u));
+            c.count_cut(alive3_m & lane_mask(a.t2 >= cut), acc2_m | lane_mask(fa.b1 != 0u));
+        }
         hit_m |= acc1_m | acc2_m;
         t_hit = lane_bool(acc1_m) ? a.t1 : (lane_bool(acc2_m) ? a.t2 : t_hit);
         vexit_m |= out2_m;
@@ -953,6 +979,36 @@ __device__ __forceinline__ bool tile_is_empty(const DevFrame& fr, uint32_t lx, u
 {
     return tile_mask_clear(fr, lx, y) && !tile_has_capped_state(fr, inside, rng0);
 }
+// Far cut: the same argument for the TAIL of a camera ray.  DevFrame::tile_far bounds the distance from the camera
+// position to the farthest point of every mask box the tile's rays can pass through; a collision farther out reads density 0, and so does
+// every later one.  tile_mask_look is tile_mask_clear for the camera kernels: the tile's bound comes with the mask word, in the same
+// round trip through the scalar cache (*far_bits; +inf where there is no mask in force or a box behind the eye switches it off).
+// tile_far_cut: the bound the wave may use -- +inf as well when a pixel of the tile is in a capped state (such a walk may end at the cap,
+// not outside).  Wave-uniform.
+__device__ __forceinline__ bool tile_mask_look(const DevFrame& fr, uint32_t lx, uint32_t y, uint32_t* far_bits)
+{
+    *far_bits = 0x7f800000u;
+    if (fr.tile_mask == nullptr || fr.flight_mode == 0u) return false;
+    const uint32_t tiles_x = (fr.w + 7u) >> 3, tiles_y = (fr.h + 7u) >> 3;
+    const uint32_t id = __builtin_amdgcn_readfirstlane((y >> 3) * tiles_x + (lx >> 3));      // wave-uniform: one tile per wave
+    const uint32_t n_words = (tiles_x * tiles_y + 31u) >> 5;
+    uint32_t word, ignore, far;
+    const uint32_t* farp = fr.tile_far != nullptr ? reinterpret_cast<const uint32_t*>(fr.tile_far) + id : fr.tile_mask + n_words;
+    scalar_load3(fr.tile_mask + (id >> 5), fr.tile_mask + n_words, farp, &word, &ignore, &far);
+    if (ignore == 0u && fr.tile_far != nullptr) *far_bits = far;
+    return ignore == 0u && ((word >> (id & 31u)) & 1u) == 0u;
+}
+__device__ __forceinline__ float tile_far_cut(const DevFrame& fr, uint32_t far_bits, bool inside, float rng0)
+{
+    if (far_bits == 0x7f800000u || tile_has_capped_state(fr, inside, rng0)) return __builtin_huge_valf();
+    return nrc_u2f(far_bits);
+}
+// a lane's cut for the walk that starts at `entry`: the walk's t counts from there, and entry = eye + s * rd with s = dot(entry - eye, rd)
+// (signed: an eye inside the box has s <= 0).  The rounding of s and of the difference is inside tile_far_bound's margin.
+__device__ __forceinline__ float camera_far_cut(float far, const DevCamera& cam, V3 entry, V3 rd)
+{
+    return far - dot(sub(entry, v3(cam.pos[0], cam.pos[1], cam.pos[2])), rd);
+}
 
 // optical distance (in units of 1 / sigma_max) covered by the 128 free flights of a delta walk that starts in RNG state
 // float_construct(m) and rejects every tentative collision: draws alternate flight, acceptance (path_trace.glsl:163-170)
@@ -1043,6 +1099,14 @@ __device__ __forceinline__ void store_tile_cost(const DevFrame& fr, uint32_t slo
     fr.tile_cost[slot] = c;
 }
 
+// [2], [3]: the far cut's proof (CtxT::count_cut)
+template <class C>
+__device__ __forceinline__ void count_cut_fetches(unsigned long long* counter, const C& c)
+{
+    if (counter == nullptr || (threadIdx.x & 63u) != 0u) return;
+    if (c.cut_n != 0u) atomicAdd(counter + 2, (unsigned long long)c.cut_n);
+    if (c.cut_met != 0u) atomicAdd(counter + 3, (unsigned long long)c.cut_met);
+}
 __device__ __forceinline__ void count_fetches(unsigned long long* counter, uint32_t n)
 {
     if (counter == nullptr) return;
@@ -1315,11 +1379,14 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK, NRC_GEN_WAVES_PER_SIMD
         }
     }
     c.occ = load_occupancy_per_wave(sc, s_occ);
+    uint32_t far_bits;
+    tile_mask_look(fr, lx, y, &far_bits);      // (the tile's far bound: a wave that walks pays a second trip through the scalar cache for it)
     // Wave-uniform control flow with per-lane predicates from here to the stores: a lane whose path has ended (or that has none)
     // stays in the instruction stream, so that the tracking loops can hand the last walks to lane pairs (ratio_pairs).
     V3 ro, rd;
     camera_ray(cam, u, v, &ro, &rd);
     c.rng = random2(seed_uv, random4(fr.random));      // init_random
+    const float far = tile_far_cut(fr, far_bits, inside, c.rng);
     const bool enter = inside;
     V3 entry = ro, ex;
     {
@@ -1347,7 +1414,10 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK, NRC_GEN_WAVES_PER_SIMD
     for (int i = 0;; i++) {
         if (__ballot(walking) == 0ull) break;
         bool vexit = false;
-        const V3 nc = delta_track<true>(c, cur, dir, &vexit, walking);
+        // the far cut ends the FIRST walk only: the later ones start from RNG states nobody has classified, and the second vertex's exit
+        // point is read (the query)
+        const float cut = camera_far_cut(i == 0 ? far : __builtin_huge_valf(), cam, cur, dir);
+        const V3 nc = delta_track<true, true>(c, cur, dir, &vexit, walking, cut);
         cur = sel(walking, nc, cur);
         walking &= !vexit;
         did_scatter |= walking;
@@ -1374,7 +1444,9 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK, NRC_GEN_WAVES_PER_SIMD
                 const uint32_t qx = tg.x_dist ? lx / tg.x_dist : 0u, qy = tg.y_dist ? y / tg.y_dist : 0u;
                 on_grid = (qx * tg.x_dist == lx) & (qy * tg.y_dist == y) & (qx < tg.tw) & (qy < tg.th);
             }
-            if (on_grid) {
+            // (scattered pixels only: prep_train_rays reads the images where info == 1, and an unscattered pixel's point is where its walk
+            // left -- with the far cut no longer the reference's exit point)
+            if (on_grid && did_scatter) {
                 origin[pix] = make_float4(cur.x, cur.y, cur.z, 0.0f);
                 dirs[pix] = make_float4(dir.x, dir.y, dir.z, 0.0f);
             }
@@ -1411,6 +1483,7 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK, NRC_GEN_WAVES_PER_SIMD
     if constexpr (COUNT) {      // [0] the algorithm's look-ups, [1] those of them the dead-walk rule kept from memory
         count_fetches(fetch_counter, c.fetches);
         if (fetch_counter != nullptr && (threadIdx.x & 63u) == 0u && c.masked != 0u) atomicAdd(fetch_counter + 1, (unsigned long long)c.masked);
+        count_cut_fetches(fetch_counter, c);
     }
     // what this tile cost (shader cycles): next frames launch the costliest tiles first (k_tile_order).  (Not for a hot wave: what
     // it measured is this frame's one pixel in a capped state, not the tile.)
@@ -1444,7 +1517,12 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK, NRC_CAMERA_WAVES_PER_S
     V3 ro, rd;
     camera_ray(cam, u, v, &ro, &rd);
     init_random(c, u, v, fr.random);
-    const bool empty = tile_is_empty(fr, lx, y, inside, c.rng);      // wave-uniform, see tile_is_empty
+    // (the capped states are looked up only where the mask is in force: without it there is no selection -- flight_bits is null)
+    uint32_t far_bits;
+    const bool clear = tile_mask_look(fr, lx, y, &far_bits);
+    const bool capped = (clear || far_bits != 0x7f800000u) && tile_has_capped_state(fr, inside, c.rng);
+    const bool empty = clear && !capped;      // wave-uniform, see tile_is_empty
+    const float far = capped ? __builtin_huge_valf() : nrc_u2f(far_bits);
     const bool enter = inside & !empty;
     V3 entry = ro, ex;
     if (__ballot(enter) != 0ull) find_entry_exit(c, sel(enter, ro, v3(0.0f, 0.0f, 0.0f)), sel(enter, rd, v3(0.0f, 0.0f, 1.0f)), &entry, &ex);
@@ -1456,7 +1534,8 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK, NRC_CAMERA_WAVES_PER_S
     for (uint32_t i = 0; i < path_length; i++) {
         if (__ballot(walking) == 0ull) break;
         bool vexit = false;
-        const V3 nc = delta_track<true>(c, cur, dir, &vexit, walking);
+        const float cut = camera_far_cut(i == 0u ? far : __builtin_huge_valf(), cam, cur, dir);      // the first walk only, as in k_gen_rays
+        const V3 nc = delta_track<true, true>(c, cur, dir, &vexit, walking, cut);
         cur = sel(walking, nc, cur);
         walking &= !vexit;
         did_scatter |= walking;
@@ -1482,6 +1561,7 @@ __global__ __launch_bounds__(64 * CAMERA_WAVES_PER_BLOCK, NRC_CAMERA_WAVES_PER_S
     if constexpr (COUNT) {      // [0] the algorithm's look-ups, [1] those of them the dead-walk rule kept from memory
         count_fetches(fetch_counter, c.fetches);
         if (fetch_counter != nullptr && (threadIdx.x & 63u) == 0u && c.masked != 0u) atomicAdd(fetch_counter + 1, (unsigned long long)c.masked);
+        count_cut_fetches(fetch_counter, c);
     }
     if (fr.tile_cost != nullptr && !hot_wave && (threadIdx.x & 63u) == 0)      // see k_gen_rays / k_tile_order (a longer walk: 8 192-cycle classes)
         store_tile_cost(fr, slot, (__builtin_amdgcn_s_memtime() - t_start) >> 4);
@@ -1564,13 +1644,27 @@ __global__ __launch_bounds__(1024) void k_tile_order_xcd(uint32_t* __restrict__ 
 // and one off screen are two sentinels whose row range ty0 > ty1 is empty.  One body, so that the two builds agree to the last bit.
 constexpr unsigned long long kTileRectOff = 0x0000ffff00000000ull | 0xfffeull;        // ty0 = 0xffff > ty1 = 0, tx0 = 0xfffe: behind
 constexpr unsigned long long kTileRectNone = 0x0000ffff00000000ull | 0xffffull;       // ... tx0 = 0xffff: off screen
-template <bool kRects = false>
-__device__ __forceinline__ void tile_mask_box(const float* __restrict__ boxes, uint32_t i, const DevProjView& pv, const DevFrame& fr,
-                                              uint32_t* __restrict__ mask, unsigned long long* __restrict__ rect = nullptr)
+// The far cut's bound (DevFrame::tile_far, DESIGN.md section 4.4 "Far cut"): both builds also raise, for every tile the box's rectangle
+// touches, the tile's float to tile_far_bound of the box -- the distance from the camera position to the box's farthest point (a corner: the
+// distance to a point is convex, and a convex function on a box is largest at a vertex), rounded up and grown.  The values are positive
+// floats, whose order is the order of their bit patterns: an atomic max on the bits is the maximum, whatever the order of the boxes.
+// The margin: the boxes already stand one voxel off every non-empty voxel; on top of that far_margin (a voxel diagonal, from the host) and
+// 2^-16 of the distance itself, some hundred times the rounding error of the three products, two sums and the square root here and of
+// the lane's own dot product and subtraction in camera_far_cut.
+__device__ __forceinline__ float tile_far_bound(const float* b, const DevProjView& pv)
 {
-    const uint32_t tiles_x = (fr.w + 7u) >> 3, tiles_y = (fr.h + 7u) >> 3;
-    const uint32_t n_words = (tiles_x * tiles_y + 31u) >> 5;
-    const float* b = boxes + 6u * (size_t)i;
+    float d2 = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const float x = b[(k & 1) ? 3 : 0] - pv.eye[0], y = b[(k & 2) ? 4 : 1] - pv.eye[1], z = b[(k & 4) ? 5 : 2] - pv.eye[2];
+        d2 = fmaxf(d2, x * x + y * y + z * z);
+    }
+    const float d = sqrtf(d2);
+    return d + (d * 0x1p-16f + pv.far_margin);
+}
+// the tile rectangle of box b = {lo xyz, hi xyz}: t = {tx0, tx1, ty0, ty1}.  0: on screen; 1: a corner at or behind the eye plane; 2: off screen
+__device__ __forceinline__ int tile_rect_of(const float* b, const DevProjView& pv, const DevFrame& fr, uint32_t* t)
+{
     float xmin = 3.0e38f, xmax = -3.0e38f, ymin = 3.0e38f, ymax = -3.0e38f;
     bool behind = false;
 #pragma unroll
@@ -1584,11 +1678,7 @@ __device__ __forceinline__ void tile_mask_box(const float* __restrict__ boxes, u
         xmin = fminf(xmin, nx); xmax = fmaxf(xmax, nx);
         ymin = fminf(ymin, ny); ymax = fmaxf(ymax, ny);
     }
-    if (behind || !(xmin <= xmax) || !(ymin <= ymax)) {      // NaN-safe
-        if constexpr (kRects) *rect = kTileRectOff;
-        else atomicOr(&mask[n_words], 1u);
-        return;
-    }
+    if (behind || !(xmin <= xmax) || !(ymin <= ymax)) return 1;      // NaN-safe
     // pixel (gx, y) looks along ndc = (2 gx / gw - 1, 2 y / gh - 1): gx = (ndc.x + 1) / 2 * gw
     const float gw = 1.0f / fr.inv_gw, gh = 1.0f / fr.inv_gh;
     float gx0 = floorf((xmin + 1.0f) * 0.5f * gw) - 1.0f, gx1 = ceilf((xmax + 1.0f) * 0.5f * gw) + 1.0f;
@@ -1603,32 +1693,71 @@ __device__ __forceinline__ void tile_mask_box(const float* __restrict__ boxes, u
     float lx1 = (floorf((floorf(gx1 / blk) - (float)fr.x_offset) / (float)fr.x_stride) + 1.0f) * blk - 1.0f;
     lx0 = fmaxf(lx0, 0.0f); gy0 = fmaxf(gy0, 0.0f);
     lx1 = fminf(lx1, (float)(fr.w - 1u)); gy1 = fminf(gy1, (float)(fr.h - 1u));
-    if (!(lx0 <= lx1) || !(gy0 <= gy1)) {                    // off screen
+    if (!(lx0 <= lx1) || !(gy0 <= gy1)) return 2;
+    t[0] = (uint32_t)lx0 >> 3; t[1] = (uint32_t)lx1 >> 3; t[2] = (uint32_t)gy0 >> 3; t[3] = (uint32_t)gy1 >> 3;
+    return 0;
+}
+template <bool kRects = false>
+__device__ __forceinline__ void tile_mask_box(const float* __restrict__ boxes, uint32_t i, const DevProjView& pv, const DevFrame& fr,
+                                              uint32_t* __restrict__ mask, float* __restrict__ far, unsigned long long* __restrict__ rect = nullptr)
+{
+    const uint32_t tiles_x = (fr.w + 7u) >> 3, tiles_y = (fr.h + 7u) >> 3;
+    const uint32_t n_words = (tiles_x * tiles_y + 31u) >> 5;
+    const float* b = boxes + 6u * (size_t)i;
+    uint32_t t[4];
+    const int st = tile_rect_of(b, pv, fr, t);
+    if (st == 1) {
+        if constexpr (kRects) *rect = kTileRectOff;
+        else atomicOr(&mask[n_words], 1u);
+        return;
+    }
+    if (st == 2) {                    // off screen
         if constexpr (kRects) *rect = kTileRectNone;
         return;
     }
-    const uint32_t tx0 = (uint32_t)lx0 >> 3, tx1 = (uint32_t)lx1 >> 3, ty0 = (uint32_t)gy0 >> 3, ty1 = (uint32_t)gy1 >> 3;
     if constexpr (kRects) {
-        *rect = (unsigned long long)tx0 | ((unsigned long long)tx1 << 16) | ((unsigned long long)ty0 << 32) | ((unsigned long long)ty1 << 48);
-        return;
+        *rect = (unsigned long long)t[0] | ((unsigned long long)t[1] << 16) | ((unsigned long long)t[2] << 32) | ((unsigned long long)t[3] << 48);
+    } else {
+        for (uint32_t ty = t[2]; ty <= t[3]; ty++)
+            for (uint32_t tx = t[0]; tx <= t[1]; tx++) {
+                const uint32_t id = ty * tiles_x + tx;
+                const uint32_t bit = 1u << (id & 31u);
+                if ((mask[id >> 5] & bit) == 0u) atomicOr(&mask[id >> 5], bit);
+            }
     }
-    for (uint32_t ty = ty0; ty <= ty1; ty++)
-        for (uint32_t tx = tx0; tx <= tx1; tx++) {
-            const uint32_t id = ty * tiles_x + tx;
-            const uint32_t bit = 1u << (id & 31u);
-            if ((mask[id >> 5] & bit) == 0u) atomicOr(&mask[id >> 5], bit);
-        }
+    // The far bounds, piece by piece: a box is a run of cells along x, up to the volume's width long, and its farthest corner says little
+    // about a tile that sees its near end.  The run is cut into pieces of pv.far_piece (a cell's length) -- consecutive, the same expression
+    // for a shared boundary, the last one ending at the box's end: together they are the box.  A ray that passes through the box meets
+    // density only inside pieces whose rectangle holds its pixel, so every piece raises the tiles of its OWN rectangle to its own bound.
+    // (A piece the projection cannot place -- it cannot be behind the eye when the box is not, but the test is made in fp32 -- raises the
+    // box's whole rectangle.)
+    uint32_t* far_u = reinterpret_cast<uint32_t*>(far);
+    for (uint32_t k = 0; k < 4096u; k++) {
+        const float x0 = b[0] + (float)k * pv.far_piece, x1 = fminf(b[0] + (float)(k + 1u) * pv.far_piece, b[3]);
+        if (!(x0 < b[3])) break;
+        const float piece[6] = {x0, b[1], b[2], k + 1u == 4096u ? b[3] : x1, b[4], b[5]};
+        uint32_t q[4];
+        const int sp = tile_rect_of(piece, pv, fr, q);
+        if (sp == 2) continue;
+        if (sp == 1) { q[0] = t[0]; q[1] = t[1]; q[2] = t[2]; q[3] = t[3]; }
+        const uint32_t far_bits = nrc_f2u(tile_far_bound(piece, pv));
+        for (uint32_t ty = q[2]; ty <= q[3]; ty++)
+            for (uint32_t tx = q[0]; tx <= q[1]; tx++) {
+                const uint32_t id = ty * tiles_x + tx;
+                if (far_u[id] < far_bits) atomicMax(&far_u[id], far_bits);
+            }
+    }
 }
 
 // n = *n_dev when the count lives in device memory (a volume rebuilt on the device, k_vol_rows; the grid covers the capacity), else n_host
 __global__ __launch_bounds__(256) void k_tile_mask(const float* __restrict__ boxes, uint32_t n_host, const uint32_t* __restrict__ n_dev, DevProjView pv,
-                                                  DevFrame fr, uint32_t* __restrict__ mask)
+                                                  DevFrame fr, uint32_t* __restrict__ mask, float* __restrict__ far)
 {
     NRC_RAISE_WAVE_PRIORITY(16);
     const uint32_t n = n_dev != nullptr ? *n_dev : n_host;
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    tile_mask_box(boxes, i, pv, fr, mask);
+    tile_mask_box(boxes, i, pv, fr, mask, far);
 }
 
 // ---- the same mask, built in parallel over its words (nrc_renderer_render_path: a mask per view, beside the previous view's frames).
@@ -1640,13 +1769,13 @@ __global__ __launch_bounds__(256) void k_tile_mask(const float* __restrict__ box
 constexpr uint32_t kTileRectChunk = 1024u;
 
 __global__ __launch_bounds__(256) void k_tile_rects(const float* __restrict__ boxes, uint32_t n_host, const uint32_t* __restrict__ n_dev, DevProjView pv,
-                                                   DevFrame fr, unsigned long long* __restrict__ rects)
+                                                   DevFrame fr, unsigned long long* __restrict__ rects, float* __restrict__ far)
 {
     NRC_RAISE_WAVE_PRIORITY(16);
     const uint32_t n = n_dev != nullptr ? *n_dev : n_host;
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    tile_mask_box<true>(boxes, i, pv, fr, nullptr, rects + i);
+    tile_mask_box<true>(boxes, i, pv, fr, nullptr, far, rects + i);
 }
 
 __global__ __launch_bounds__(256) void k_tile_mask_words(const unsigned long long* __restrict__ rects, uint32_t n_host, const uint32_t* __restrict__ n_dev,
@@ -2686,18 +2815,21 @@ void launch_tile_order(const uint32_t* cost, uint32_t n_slots, uint32_t* order, 
 
 uint32_t tile_mask_words(uint32_t w, uint32_t h) { return (ceil_div(w, 8) * ceil_div(h, 8) + 31u) / 32u + 1u; }
 
-void launch_tile_mask(const BoxList& b, const DevProjView& pv, const DevFrame& fr, uint32_t* mask, hipStream_t s)
+void launch_tile_mask(const BoxList& b, const DevProjView& pv, const DevFrame& fr, uint32_t* mask, float* far, hipStream_t s)
 {
     NRC_HIP(hipMemsetAsync(mask, 0, (size_t)tile_mask_words(fr.w, fr.h) * 4, s));
+    NRC_HIP(hipMemsetAsync(far, 0, (size_t)ceil_div(fr.w, 8) * ceil_div(fr.h, 8) * 4, s));
     if (b.grid == 0) return;
-    hipLaunchKernelGGL(k_tile_mask, dim3(ceil_div(b.grid, 256)), dim3(256), 0, s, b.boxes, b.n_host, b.n_dev, pv, fr, mask);
+    hipLaunchKernelGGL(k_tile_mask, dim3(ceil_div(b.grid, 256)), dim3(256), 0, s, b.boxes, b.n_host, b.n_dev, pv, fr, mask, far);
     NRC_HIP(hipGetLastError());
 }
 
-void launch_tile_mask_tiles(const BoxList& b, const DevProjView& pv, const DevFrame& fr, void* rects, uint32_t* mask, hipStream_t s)
+void launch_tile_mask_tiles(const BoxList& b, const DevProjView& pv, const DevFrame& fr, void* rects, uint32_t* mask, float* far, hipStream_t s)
 {
+    NRC_HIP(hipMemsetAsync(far, 0, (size_t)ceil_div(fr.w, 8) * ceil_div(fr.h, 8) * 4, s));      // (the far bounds are a maximum: they start from 0)
     if (b.grid > 0) {      // (no box: k_tile_mask_words alone writes an all-clear mask)
-        hipLaunchKernelGGL(k_tile_rects, dim3(ceil_div(b.grid, 256)), dim3(256), 0, s, b.boxes, b.n_host, b.n_dev, pv, fr, (unsigned long long*)rects);
+        hipLaunchKernelGGL(k_tile_rects, dim3(ceil_div(b.grid, 256)), dim3(256), 0, s, b.boxes, b.n_host, b.n_dev, pv, fr, (unsigned long long*)rects,
+                           far);
         NRC_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_tile_mask_words, dim3(ceil_div(tile_mask_words(fr.w, fr.h), 4)), dim3(256), 0, s, (const unsigned long long*)rects,

@@ -45,6 +45,10 @@ struct DevFrame {
     // one bit per 8x8 pixel tile (index ty * ceil(w/8) + tx), set when a camera ray of the tile can meet a non-empty voxel; the
     // word behind the last tile word is non-zero when the mask must be ignored.  nullptr: no mask (every tile is traced).
     const uint32_t* tile_mask;
+    // the far cut, built with the mask: one float per tile, an upper bound of the distance from the camera position
+    // to the farthest point of any mask box whose rectangle touches the tile (0: none does).  Behind it a camera ray of the tile is in
+    // empty space for good.  nullptr: no cut.
+    const float* tile_far;
     // the mask may only be applied to a pixel whose delta walk through empty space provably leaves the volume before DeltaTrack's
     // cap of 128 collisions -- a property of the pixel's RNG state (2^23 of them) and of the scene's largest optical depth.  The
     // states that can reach the cap ("capped") are handed over as a list when there are at most kFlightListMax of them (one state,
@@ -88,8 +92,13 @@ struct DevFrame {
 constexpr uint32_t kOrderSlotMask = 0x00ffffffu;      // (most tiles a launch order can address)
 
 // forward camera transform for the tile mask: clip = m * (x, y, z, 1), column-major like DevCamera::m
+// eye: the camera position the far cut's distances are measured from; far_margin: what a box's farthest-corner distance is grown by
+// (tile_far_bound)
 struct DevProjView {
     float m[16];
+    float eye[3];
+    float far_margin;
+    float far_piece;              // the length along x of the pieces a box is cut into for its far bounds (a cell's; > 0)
 };
 
 struct TrainGrid {
@@ -109,18 +118,19 @@ uint32_t query_count(uint32_t w, uint32_t h);      // queries in tile-major orde
 // {lo.xyz, hi.xyz} that together cover every non-empty voxel with a margin of one voxel.  mask: ceil(tiles/32) + 1 words, zeroed here.
 // The boxes of the active volume: n_host of them, or *n_dev (<= grid, the capacity) when the count lives in device memory, as
 // launch_volume_rebuild leaves it (n_dev not null); grid: the boxes a launch has to cover, 0: none
+// far: DevFrame::tile_far of the same boxes (one float per tile, zeroed here), by both builds
 struct BoxList {
     const float* boxes;
     uint32_t n_host;
     const uint32_t* n_dev;
     uint32_t grid;
 };
-void launch_tile_mask(const BoxList& b, const DevProjView& pv, const DevFrame& fr, uint32_t* mask, hipStream_t s);
+void launch_tile_mask(const BoxList& b, const DevProjView& pv, const DevFrame& fr, uint32_t* mask, float* far, hipStream_t s);
 uint32_t tile_mask_words(uint32_t w, uint32_t h);
 // the same words (the trailing "off" word included) from a build that runs in parallel over the mask instead of over the boxes, without
 // atomics and without a clear of `mask` (nrc_renderer_render_path: one mask per view).  rects: 8 bytes per box (b.grid), scratch between
 // the two launches.
-void launch_tile_mask_tiles(const BoxList& b, const DevProjView& pv, const DevFrame& fr, void* rects, uint32_t* mask, hipStream_t s);
+void launch_tile_mask_tiles(const BoxList& b, const DevProjView& pv, const DevFrame& fr, void* rects, uint32_t* mask, float* far, hipStream_t s);
 
 // ---- device-side volume rebuild (nrc_renderer_set_volume): from a density volume in device memory (NRC_VOLUME_U8 / NRC_VOLUME_F32,
 // index i + nx*(j + ny*k)) the R8 density, the exact occupancy bits (DevScene::occ_bits) and the dilated 8^3-cell boxes of the tile mask,

@@ -391,7 +391,7 @@ struct Medium : SceneDev {
         return {slot[active].boxes, 0u, slot[active].n_boxes, volume_box_capacity(d.nx, d.ny, d.nz)};
     }
     // the empty-space tile mask from them
-    void launch_mask(const DevProjView& pv, const DevFrame& fr, uint32_t* mask, hipStream_t s) const { launch_tile_mask(box_list(), pv, fr, mask, s); }
+    void launch_mask(const DevProjView& pv, const DevFrame& fr, uint32_t* mask, float* far, hipStream_t s) const { launch_tile_mask(box_list(), pv, fr, mask, far, s); }
     // the same words from the tile-parallel build (launch_tile_mask_tiles; render_path's views)
     DevBuf<void> d_rects;         // its scratch: a packed rectangle per box, allocated by the first camera path
     void ensure_rects()
@@ -400,9 +400,9 @@ struct Medium : SceneDev {
         const size_t n = std::max<size_t>(std::max(n_boxes, volume_box_capacity(d.nx, d.ny, d.nz)), 1);
         d_rects.alloc(n * 8, "tile mask rectangles");
     }
-    void launch_mask_tiles(const DevProjView& pv, const DevFrame& fr, uint32_t* mask, hipStream_t s) const
+    void launch_mask_tiles(const DevProjView& pv, const DevFrame& fr, uint32_t* mask, float* far, hipStream_t s) const
     {
-        launch_tile_mask_tiles(box_list(), pv, fr, d_rects, mask, s);
+        launch_tile_mask_tiles(box_list(), pv, fr, d_rects, mask, far, s);
     }
     // nrc_renderer_volume_buffer (the caller has synchronised): 0 density, 1 occupancy bits, 2 boxes
     const void* buffer(int which, size_t* bytes) const
