@@ -861,6 +861,75 @@ int nrc_mc_renderer_set_path_denoise_target(nrc_mc_renderer_t* r, float* d_denoi
 int nrc_mc_renderer_export_exr_denoised(nrc_mc_renderer_t* r, const char* path, const nrc_denoise_params* params);
 int nrc_test_denoise_host(const float* rgba, const float* aov, uint32_t w, uint32_t h, const nrc_denoise_params* params, float* out);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Reproject: history reuse by reprojection (both renderers; the renderer call has an nrc_mc_renderer_ twin).  The frame accumulated over
+ * the views before this one is carried into the current view and blended with the current view's frames by effective frame counts, so a
+ * turntable or fly-through of a few frames per view shows more samples per pixel than it renders per view.  What reprojection needs is the
+ * depth of a pixel, and the view AOV has it exact and noise-free: z_half, the distance at which the camera ray reaches optical depth ln 2,
+ * or z_front where the medium is thinner than that.  No motion vectors, no G-buffer.  It is a deterministic function of its images and
+ * cameras, opt-in, and BIASED (DESIGN.md section 4.20 has the measured gains and the bias).
+ *   Inputs.   History, all or none: colour hist_rgba [h][w][4], count hist_count [h][w] (the effective number of frames behind each pixel),
+ *             the history view's AOV hist_aov [h][w][4] and its camera.  Current: colour rgba [h][w][4], the scalar frames > 0 (finite: the
+ *             frames blended into it), its AOV aov [h][w][4] and its camera.  Outputs out [h][w][4], out_count [h][w].  Device memory, the
+ *             images 16-byte aligned.  d_hist_rgba == NULL means no history: then all four history arguments must be NULL, out = rgba bit
+ *             for bit and out_count = frames.  A NULL here and a pointer there: NRC_ERR_INVALID.
+ *   Params.   nrc_reproject_params: max_history (64; > 0, finite: a cap on the frames history may count for), sigma_alpha (0.1),
+ *             sigma_depth (4.0, in the units of t) -- the denoiser's defaults.  Every sigma must be > 0, +inf allowed (the term is then
+ *             exactly 0), and large enough that 1 / sigma is finite in fp32.  NaN and anything out of range: NRC_ERR_INVALID.
+ *   Setup.    Once per call, on the host, in double, from the history camera's fp32 inv_proj_view m and pos:  A_k = m[k] - pos_k m[3],
+ *             B_k = m[4 + k] - pos_k m[7],  C_k = m[12 + k] - pos_k m[15]  (k = 0, 1, 2) -- a history pixel's ray direction is
+ *             ~ sx A + sy B + C.  N = [A B C]^-1, rounded to fp32.  A determinant of 0 or a non-finite N: NRC_ERR_INVALID.
+ *   Pixel.    P = (x, y), in fp32, in this order (csrc/nrc_reproject.hpp is the one statement; its head is this list's fine print):
+ *             1. alpha_P == 0, a non-finite R, G or B of rgba(P), or no history: out = rgba(P) bit for bit, out_count = frames.
+ *             2. z = finite(z_half_P) ? z_half_P : z_front_P.
+ *             3. the view AOV's camera ray of the pixel (u = x (1.0f / w), v = y (1.0f / h): no half-pixel offset); X = fma(z, rd, ro).
+ *             4. D = X - pos_hist;  q_k = fma(N[3k + 2], D_2, fma(N[3k + 1], D_1, N[3k] D_0));  sx = q_0 / q_2, sy = q_1 / q_2;
+ *                ww = fma(m[7], sy, fma(m[3], sx, m[15])); the pixel passes through unless q_2 ww > 0 (X in front of the history
+ *                camera);  dist = |D|.
+ *             5. fx = ((sx + 1) 0.5) w, fy likewise with h; the pixel passes through unless -1 <= fx < w and -1 <= fy < h;
+ *                x0 = floor(fx), tx = fx - x0, and likewise for y.
+ *             6. the taps Q = (x0 + i, y0 + j), j = 0, 1 outside, i = 0, 1 inside, skipping a tap outside the image, with alpha_Q == 0,
+ *                or with a non-finite R, G or B in hist_rgba.  z_Q as in 2.  b = (i ? tx : 1 - tx) (j ? ty : 1 - ty);
+ *                  d = |alpha_Q - alpha_P| inv_sa;  d = fma(|z_Q - dist|, inv_sz, d);  wgt = b (1.0f - nrc_expm1_negf(d))
+ *                  acc_c = fma(wgt, c_Q - c_P, acc_c) for R, G, B;  acc_w += wgt;  acc_n = fma(wgt, n_Q, acc_n)
+ *                The depth term is the disocclusion test: the history pixel must have seen the medium at the distance X has from the
+ *                history camera.  The mean is formed around the centre: a constant colour comes back bit for bit.
+ *             7. acc_w == 0: the pixel passes through.  Otherwise n_h = min(acc_n, max_history), a = n_h / (n_h + frames),
+ *                out = fma(a, acc_c / acc_w, c_P) for R, G, B, out_count = n_h + frames.
+ *             acc_n is not normalised: the bilinear weights and exp(-d) shrink it, so poorly matched history counts for little, without a
+ *             threshold.  The rule is continuous in (fx, fy).
+ *   Alpha.    The output's alpha channel is the current colour's bits in every case.
+ * The fp32 arithmetic is defined once, in csrc/nrc_reproject.hpp, which the kernel and the host (nrc_test_reproject_host) both run: the same
+ * bits.  No in-place operation: an output that overlaps any input, or the other output, returns NRC_ERR_INVALID before anything is enqueued.
+ * nrc_reproject: the free function over whole images; one launch on `stream`, no host wait, nothing allocated.
+ * nrc_renderer_set_path_reproject_target: view i of the next nrc_renderer_render_path / _render_path_timed call writes
+ *     accum[i], counts[i] = reproject(history: accum[i - 1], counts[i - 1], aovs[i - 1], cameras[i - 1];
+ *                                     current: the view's final framebuffer, frames_per_camera, aovs[i], cameras[i])
+ *   to d_accum + i * h * w * 4 and d_counts + i * h * w (device memory for n_views views); view 0 has no history.  It is enqueued behind
+ *   the view's last blend and in front of the next view's clear, behind view i - 1's reprojection.  It needs an AOV target in the same
+ *   call (nrc_renderer_set_path_aov_target): the caller's d_aovs[i - 1] and d_aovs[i] are the guides.  A path call without an AOV target,
+ *   with AOV depths, with another n_views, with frames_per_camera == 0 or with a singular camera fails with NRC_ERR_INVALID, enqueues
+ *   nothing and drops every target.  Consumed by that call; d_accum == NULL cancels.  With a denoise target in the same call view i's
+ *   filter reads accum[i] instead of the framebuffer, behind the reprojection: accumulate, then filter.  With a timed path the medium
+ *   may change between views: history is validated by the guides alone, whose depth and alpha then differ where the medium moved.  When the
+ *   path call returns the creation stream is ordered behind the last reprojection.  The renderer allocates nothing for this: every buffer
+ *   is the caller's.  Frames, d_frames, AOVs and training state are bit for bit what they are without the target.
+ * A renderer that draws one rank's column strips of a sharded frame refuses the renderer call with NRC_ERR_INVALID.
+ * nrc_test_reproject_host (test hook): the header's arithmetic on the CPU inside the library; host memory, no device. */
+typedef struct nrc_reproject_params {
+    float max_history, sigma_alpha, sigma_depth;
+} nrc_reproject_params;
+void nrc_reproject_params_default(nrc_reproject_params* p);
+int nrc_reproject(const float* d_hist_rgba, const float* d_hist_count, const float* d_hist_aov, const nrc_camera* hist_camera, const float* d_rgba,
+                  float frames, const float* d_aov, const nrc_camera* camera, uint32_t w, uint32_t h, const nrc_reproject_params* params, float* d_out,
+                  float* d_out_count, void* stream);
+int nrc_test_reproject_host(const float* hist_rgba, const float* hist_count, const float* hist_aov, const nrc_camera* hist_camera, const float* rgba,
+                            float frames, const float* aov, const nrc_camera* camera, uint32_t w, uint32_t h, const nrc_reproject_params* params,
+                            float* out, float* out_count);
+int nrc_renderer_set_path_reproject_target(nrc_renderer_t* r, float* d_accum, float* d_counts, uint32_t n_views, const nrc_reproject_params* params);
+int nrc_mc_renderer_set_path_reproject_target(nrc_mc_renderer_t* r, float* d_accum, float* d_counts, uint32_t n_views,
+                                              const nrc_reproject_params* params);
+
 /* THE environment switch of the library: NRC_DEBUG="name[=value],..." -- diagnostic and test switches only, none changes a result
  * (the list and what each does: csrc/nrc_common.hpp, debug_switch).
  * diagnostics (read when the library first allocates): NRC_DEBUG=poison_alloc fills every device allocation with 0xFF

@@ -531,6 +531,13 @@ public:
     {
         nrc_check(nrc_renderer_export_exr_denoised(h_, filePath.c_str(), &params));
     }
+    // Reprojection (include/nrc_hpm.h, "Reproject"; en::Reproject below is the free function): with SetPathAovTarget and without depths, the
+    // next RenderPath writes view i's frame accumulated over the views before it to dAccum + i * height * width * 4 and its effective frame
+    // counts to dCounts + i * height * width (dAccum == nullptr cancels).  Opt-in and biased; every buffer is the caller's.
+    void SetPathReprojectTarget(float* dAccum, float* dCounts, uint32_t nViews, const nrc_reproject_params* params)
+    {
+        nrc_check(nrc_renderer_set_path_reproject_target(h_, dAccum, dCounts, nViews, params));
+    }
     // diagnostics: the empty-space tile mask in use (synchronises; empty: the frame uses none) -- nrc_renderer_tile_mask
     std::vector<uint32_t> TileMask() const
     {
@@ -666,6 +673,11 @@ public:
     {
         nrc_check(nrc_mc_renderer_export_exr_denoised(h_, filePath.c_str(), &params));
     }
+    // see NrcHpmRenderer::SetPathReprojectTarget
+    void SetPathReprojectTarget(float* dAccum, float* dCounts, uint32_t nViews, const nrc_reproject_params* params)
+    {
+        nrc_check(nrc_mc_renderer_set_path_reproject_target(h_, dAccum, dCounts, nViews, params));
+    }
     std::vector<uint32_t> TileMask() const
     {
         std::vector<uint32_t> m(nrc_mc_renderer_tile_mask(h_, nullptr, 0));
@@ -718,6 +730,22 @@ inline void Denoise(const float* dRgba, const float* dAov, uint32_t width, uint3
                     void* stream)
 {
     nrc_check(nrc_denoise(dRgba, dAov, width, height, &params, dOut, dScratch, stream));
+}
+
+// History reuse by reprojection over whole device images (include/nrc_hpm.h, "Reproject": nrc_reproject).  The history {dHistRgba, dHistCount,
+// dHistAov, histCamera} is all given or all nullptr (no history: dOut = dRgba, dOutCount = frames); the outputs overlap no input; enqueued on
+// `stream`, no host wait.
+inline nrc_reproject_params ReprojectDefaults()
+{
+    nrc_reproject_params p;
+    nrc_reproject_params_default(&p);
+    return p;
+}
+inline void Reproject(const float* dHistRgba, const float* dHistCount, const float* dHistAov, const nrc_camera* histCamera, const float* dRgba, float frames,
+                      const float* dAov, const nrc_camera& camera, uint32_t width, uint32_t height, const nrc_reproject_params& params, float* dOut,
+                      float* dOutCount, void* stream)
+{
+    nrc_check(nrc_reproject(dHistRgba, dHistCount, dHistAov, histCamera, dRgba, frames, dAov, &camera, width, height, &params, dOut, dOutCount, stream));
 }
 
 // en::Reference (src/Reference.cpp): the converged ground-truth image of a scene, seen from a fixed reference camera, and the

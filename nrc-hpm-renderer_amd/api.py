@@ -102,6 +102,8 @@ ABI_SYMBOLS = [
     "nrc_denoise_params_default", "nrc_denoise_scratch_bytes", "nrc_denoise", "nrc_test_denoise_host",
     "nrc_renderer_denoised_frame", "nrc_mc_renderer_denoised_frame", "nrc_renderer_set_path_denoise_target", "nrc_mc_renderer_set_path_denoise_target",
     "nrc_renderer_export_exr_denoised", "nrc_mc_renderer_export_exr_denoised",
+    "nrc_reproject_params_default", "nrc_reproject", "nrc_test_reproject_host",
+    "nrc_renderer_set_path_reproject_target", "nrc_mc_renderer_set_path_reproject_target",
     "nrc_renderer_set_show_nrc", "nrc_renderer_set_frame_random", "nrc_renderer_framebuffer", "nrc_renderer_framebuffer_on",
     "nrc_renderer_export_exr",
     "nrc_renderer_frame_time_ms", "nrc_renderer_stage_stats", "nrc_renderer_frame_timeline", "nrc_set_wave_priority_raise", "nrc_renderer_destroy", "nrc_renderer_buffer", "nrc_renderer_count_fetches", "nrc_renderer_masked_fetches",
@@ -239,6 +241,14 @@ def load_library():
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         for name in ("nrc_renderer_export_exr_denoised", "nrc_mc_renderer_export_exr_denoised"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
+    if hasattr(L, "nrc_reproject"):      # (an older build loaded through NRC_HPM_LIB has no reprojection)
+        L.nrc_reproject_params_default.restype = None
+        L.nrc_reproject_params_default.argtypes = [C.c_void_p]
+        L.nrc_reproject.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nrc_test_reproject_host.argtypes = L.nrc_reproject.argtypes[:-1]
+        for name in ("nrc_renderer_set_path_reproject_target", "nrc_mc_renderer_set_path_reproject_target"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.nrc_mc_renderer_frame_time_ms.restype = C.c_float
     if hasattr(L, "nrc_test_flight_select"):      # (an older build loaded through NRC_HPM_LIB has no such hook)
         L.nrc_test_flight_select.argtypes = [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -555,6 +565,87 @@ def test_denoise_host(rgba, aov, params=None):
     return out
 
 
+class NrcReprojectParams(C.Structure):
+    _fields_ = [("max_history", C.c_float), ("sigma_alpha", C.c_float), ("sigma_depth", C.c_float)]
+
+
+def make_c_reproject_params(params=None):
+    """nrc_reproject_params: the library's defaults (nrc_reproject_params_default) overridden by `params` -- None, a dict with any of
+    max_history, sigma_alpha, sigma_depth (scene.reproject_params), or an NrcReprojectParams.  The library checks the values."""
+    if isinstance(params, NrcReprojectParams):
+        return params
+    p = NrcReprojectParams()
+    load_library().nrc_reproject_params_default(C.byref(p))
+    for k, v in (params or {}).items():
+        if k not in ("max_history", "sigma_alpha", "sigma_depth"):
+            raise ValueError("reproject parameters: unknown key %r" % (k,))
+        setattr(p, k, float(v))
+    return p
+
+
+def _reproject_history(what, hist):
+    """`hist` of Reproject / test_reproject_host: None, or the four of (rgba, count, aov, camera)"""
+    if hist is None:
+        return None
+    if not isinstance(hist, (tuple, list)) or len(hist) != 4:
+        raise ValueError("%s: hist must be None or (rgba, count, aov, camera)" % what)
+    return tuple(hist)
+
+
+def Reproject(hist, rgba, frames, aov, camera, params=None, out=None, out_count=None):
+    """nrc_reproject: history reuse by reprojection (include/nrc_hpm.h, "Reproject") over whole images.  hist: None (no history: the result
+    is rgba and frames) or (rgba, count, aov, camera) of the history view -- contiguous float32 CUDA tensors [h][w][4], [h][w], [h][w][4]
+    and a camera (scene.make_camera); rgba, aov: the current view's frame and view AOV, `frames` the number of frames blended into rgba,
+    camera its camera; params as for make_c_reproject_params.  Returns (out [h][w][4], count [h][w]) -- `out` / `out_count`, or new tensors;
+    never an input.  Opt-in and biased.  Enqueued on torch's current stream; no host wait."""
+    import torch
+    if not isinstance(rgba, torch.Tensor) or rgba.dim() != 3:
+        raise ValueError("Reproject: rgba must be a contiguous float32 CUDA tensor of shape (h, w, 4)")
+    shape = (int(rgba.shape[0]), int(rgba.shape[1]), 4)
+    _check_device_floats("Reproject: rgba", rgba, shape)
+    _check_device_floats("Reproject: aov", aov, shape)
+    hist = _reproject_history("Reproject", hist)
+    hp = [None, None, None, None]
+    if hist is not None:
+        _check_device_floats("Reproject: hist rgba", hist[0], shape)
+        _check_device_floats("Reproject: hist count", hist[1], shape[:2])
+        _check_device_floats("Reproject: hist aov", hist[2], shape)
+        hcam = make_c_camera(hist[3])
+        hp = [_dev_ptr(hist[0]), _dev_ptr(hist[1]), _dev_ptr(hist[2]), C.byref(hcam)]
+    out = _aov_out("Reproject", out, shape)
+    out_count = _aov_out("Reproject: count", out_count, shape[:2])
+    p = make_c_reproject_params(params)
+    cam = make_c_camera(camera)
+    _check(load_library().nrc_reproject(hp[0], hp[1], hp[2], hp[3], _dev_ptr(rgba), C.c_float(frames), _dev_ptr(aov), C.byref(cam), C.c_uint32(shape[1]),
+                                        C.c_uint32(shape[0]), C.byref(p), _dev_ptr(out), _dev_ptr(out_count),
+                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out, out_count
+
+
+def test_reproject_host(hist, rgba, frames, aov, camera, params=None):
+    """nrc_test_reproject_host: (out [h][w][4], count [h][w]) (numpy) of Reproject's arguments as numpy arrays, computed on the CPU inside the
+    library by csrc/nrc_reproject.hpp's arithmetic"""
+    c = np.ascontiguousarray(rgba, np.float32)
+    g = np.ascontiguousarray(aov, np.float32)
+    if c.ndim != 3 or c.shape[2] != 4 or g.shape != c.shape:
+        raise ValueError("test_reproject_host: rgba and aov must both be [h][w][4]")
+    hist = _reproject_history("test_reproject_host", hist)
+    hp = [None, None, None, None]
+    if hist is not None:
+        hc, hn, hg = np.ascontiguousarray(hist[0], np.float32), np.ascontiguousarray(hist[1], np.float32), np.ascontiguousarray(hist[2], np.float32)
+        if hc.shape != c.shape or hg.shape != c.shape or hn.shape != c.shape[:2]:
+            raise ValueError("test_reproject_host: the history must be [h][w][4], [h][w], [h][w][4]")
+        hcam = make_c_camera(hist[3])
+        hp = [hc.ctypes.data_as(C.c_void_p), hn.ctypes.data_as(C.c_void_p), hg.ctypes.data_as(C.c_void_p), C.byref(hcam)]
+    out, count = np.empty_like(c), np.empty(c.shape[:2], np.float32)
+    p = make_c_reproject_params(params)
+    cam = make_c_camera(camera)
+    _check(load_library().nrc_test_reproject_host(hp[0], hp[1], hp[2], hp[3], c.ctypes.data_as(C.c_void_p), C.c_float(frames), g.ctypes.data_as(C.c_void_p),
+                                                  C.byref(cam), C.c_uint32(c.shape[1]), C.c_uint32(c.shape[0]), C.byref(p),
+                                                  out.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p)))
+    return out, count
+
+
 class NrcOrthoView(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3), ("dir", C.c_float * 3)]
 
@@ -571,8 +662,8 @@ def make_c_ortho_view(view):
 
 
 def _times_keyword(plain):
-    """RenderPath(..., times=None, aov_out=None, aov_depths=None, denoised_out=None, denoise_params=None) of both renderers.  The keywords ride
-    on the untimed method: its positional signature is
+    """RenderPath(..., times=None, aov_out=None, aov_depths=None, denoised_out=None, denoise_params=None, accumulated_out=None,
+    accumulated_counts=None, reproject_params=None) of both renderers.  The keywords ride on the untimed method: its positional signature is
     a published one (callers and tests/test_camera_path_host.py name its parameters in order) and stays what inspect.signature reports; a
     call without times is `plain`'s own, a call with times goes to the renderer's _path with the same arguments.
     aov_out: a contiguous float32 CUDA tensor [len(cameras)][height][width][4] that receives every view's AOV ({alpha, tau, z_front,
@@ -580,11 +671,18 @@ def _times_keyword(plain):
     aov_depths (with aov_out): a contiguous float32 CUDA tensor [len(cameras)][height][width]; view i's AOV is held out to aov_depths[i]
     (ViewAovToDepth, nrc_renderer_set_path_aov_depths).
     denoised_out (with aov_out, without aov_depths): a tensor of aov_out's shape that receives every view's final frame filtered with the
-    view's own AOV (DenoisedFrame, nrc_renderer_set_path_denoise_target); denoise_params as for make_c_denoise_params."""
+    view's own AOV (DenoisedFrame, nrc_renderer_set_path_denoise_target); denoise_params as for make_c_denoise_params.
+    accumulated_out (with aov_out, without aov_depths): a tensor of aov_out's shape that receives every view's frame accumulated over the
+    views before it by reprojection (Reproject, nrc_renderer_set_path_reproject_target); accumulated_counts: a tensor
+    [len(cameras)][height][width] for the effective frame counts (None: one is made and dropped); reproject_params as for
+    make_c_reproject_params.  With denoised_out too, the filter reads the accumulated frames."""
     @functools.wraps(plain)
-    def RenderPath(self, *args, times=None, aov_out=None, aov_depths=None, denoised_out=None, denoise_params=None, **kw):
+    def RenderPath(self, *args, times=None, aov_out=None, aov_depths=None, denoised_out=None, denoise_params=None, accumulated_out=None,
+                   accumulated_counts=None, reproject_params=None, **kw):
         bound = inspect.signature(plain).bind(self, *args, **kw)
         bound.apply_defaults()
+        if accumulated_counts is not None and accumulated_out is None:      # (before any target is set)
+            raise ValueError("RenderPath: accumulated_counts needs accumulated_out")
         if aov_out is not None:
             import torch
             shape = (len(list(bound.arguments["cameras"])), self.height, self.width, 4)
@@ -613,6 +711,24 @@ def _times_keyword(plain):
                 if aov_depths is not None:
                     self.SetPathAovDepths(None)
                 raise
+        if accumulated_out is not None:
+            try:
+                if aov_out is None:
+                    raise ValueError("RenderPath: accumulated_out needs aov_out (the views' AOVs are the guides)")
+                _check_device_floats("RenderPath: accumulated_out", accumulated_out, shape)
+                if accumulated_counts is None:
+                    import torch
+                    accumulated_counts = torch.empty(shape[:3], device="cuda", dtype=torch.float32)
+                _check_device_floats("RenderPath: accumulated_counts", accumulated_counts, shape[:3])
+                self.SetPathReprojectTarget(accumulated_out, accumulated_counts, reproject_params)
+            except Exception:
+                if aov_out is not None:
+                    self.SetPathAovTarget(None)
+                if aov_depths is not None:
+                    self.SetPathAovDepths(None)
+                if denoised_out is not None:
+                    self.SetPathDenoiseTarget(None)
+                raise
         try:
             if times is None:
                 return plain(self, *args, **kw)
@@ -624,6 +740,8 @@ def _times_keyword(plain):
                 self.SetPathAovDepths(None)
             if denoised_out is not None:
                 self.SetPathDenoiseTarget(None)
+            if accumulated_out is not None:
+                self.SetPathReprojectTarget(None, None)
     return RenderPath
 
 
@@ -776,6 +894,18 @@ class _LiveMedium:
             p = make_c_denoise_params(params)
             _check(self._medium("set_path_denoise_target")(self.h, _dev_ptr(denoised), C.c_uint32(int(denoised.shape[0]) if views is None else int(views)),
                                                            C.byref(p)))
+
+    def SetPathReprojectTarget(self, accum, counts, params=None, views=None):
+        """nrc_renderer_set_path_reproject_target: the next RenderPath writes view i's frame, accumulated over the views before it by
+        reprojection, to accum[i] and its effective frame counts to counts[i] (contiguous float32 CUDA tensors [views][height][width][4]
+        and [views][height][width]; accum None cancels).  Needs an AOV target in the same call and no AOV depths.
+        RenderPath(..., aov_out=, accumulated_out=) makes this call itself."""
+        if accum is None:
+            _check(self._medium("set_path_reproject_target")(self.h, None, None, C.c_uint32(0), None))
+        else:
+            p = make_c_reproject_params(params)
+            _check(self._medium("set_path_reproject_target")(self.h, _dev_ptr(accum), _dev_ptr(counts) if counts is not None else None,
+                                                             C.c_uint32(int(accum.shape[0]) if views is None else int(views)), C.byref(p)))
 
     def ExportDenoisedImageToFile(self, filePath, params=None):
         """ExportImageWithAovToFile with B, G, R taken from DenoisedFrame(params) (nrc_renderer_export_exr_denoised)"""

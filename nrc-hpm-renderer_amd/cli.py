@@ -31,6 +31,8 @@ union bbox as for `--bricks`, no dense array is made per file (only the first li
 dense and brick byte counts held.  `--animate --bricks` stays refused: `--bricks` means stepping with SetVolumeBricks.
 Denoise (new): `--denoise [PASSES]` with `--export` writes the frame filtered by the AOV-guided a-trous filter (include/nrc_hpm.h, "Denoise")
 instead of the raw one; with `--orbit` and a file per view every view's final frame is filtered with its own AOV inside the one RenderPath call.
+Reproject (new): `--reproject [MAX_HISTORY]` with `--orbit` and a file per view (`--export` with a `%d` pattern) writes every view's frame
+accumulated over the views before it by reprojection (include/nrc_hpm.h, "Reproject"); with `--denoise` the accumulated frames are filtered.
 """
 import argparse
 import math
@@ -92,6 +94,23 @@ def check_denoise_args(args):
         raise SystemExit("SkyRenderer ERROR: --denoise is not available with --gpus (a sharded renderer's local image has no pixel neighbours)")
     if getattr(args, "holdout_sphere", None) is not None:
         raise SystemExit("SkyRenderer ERROR: --denoise and --holdout-sphere exclude each other (the filter's guide is the whole rays' AOV)")
+
+
+def check_reproject_args(args):
+    """what --reproject can be combined with (raises SystemExit)"""
+    cap = getattr(args, "reproject", None)
+    if cap is None:
+        return
+    if not 0.0 < cap < math.inf:      # (NaN included)
+        raise SystemExit("SkyRenderer ERROR: --reproject takes a MAX_HISTORY > 0")
+    if getattr(args, "orbit", None) is None:
+        raise SystemExit("SkyRenderer ERROR: --reproject carries frames from view to view: give --orbit")
+    if not args.export or "%" not in args.export:
+        raise SystemExit("SkyRenderer ERROR: --reproject writes every view's accumulated frame: give --export with a %d pattern")
+    if args.gpus > 1:
+        raise SystemExit("SkyRenderer ERROR: --reproject is not available with --gpus (a sharded renderer's local image has no pixel neighbours)")
+    if getattr(args, "holdout_sphere", None) is not None:
+        raise SystemExit("SkyRenderer ERROR: --reproject and --holdout-sphere exclude each other (the guides are the whole rays' AOVs)")
 
 
 def aov_planes(rgba, aov):
@@ -216,6 +235,10 @@ def main(argv=None):
                     help="with --export: the exported R, G, B are the frame filtered by the edge-avoiding a-trous filter that the view AOV guides "
                          "(include/nrc_hpm.h, \"Denoise\"; 1 .. 6 passes, default 3).  Biased: for low frame counts and previews.  Combines with "
                          "--aov; one GPU; not with --holdout-sphere")
+    ap.add_argument("--reproject", type=float, nargs="?", const=64.0, default=None, metavar="MAX_HISTORY",
+                    help="with --orbit and --export with a %%d pattern: the exported frames are accumulated from view to view by reprojection through "
+                         "the view AOV's exact depth (include/nrc_hpm.h, \"Reproject\"; MAX_HISTORY caps the frames history counts for, default "
+                         "64).  Biased.  With --denoise the accumulated frames are filtered; one GPU; not with --holdout-sphere")
     ap.add_argument("--holdout-sphere", type=float, default=None, metavar="R",
                     help="with --aov: the AOV is held out to a sphere of radius R at the origin -- the medium in FRONT of the sphere, along each "
                          "camera ray up to the sphere's depth (include/nrc_hpm.h, nrc_renderer_view_aov_to_depth); pixels beside the sphere keep "
@@ -256,6 +279,7 @@ def main(argv=None):
     n_views = check_orbit_args(args)
     check_aov_args(args)
     check_denoise_args(args)
+    check_reproject_args(args)
     check_ray_aov_args(args)
     check_deep_args(args)
 
@@ -380,13 +404,16 @@ def main(argv=None):
         # (--aov: every view's AOV, of its camera and its in-between medium, lands beside its image; the frames are the same frames)
         # (--denoise: every view's final frame filtered with the view's own AOV, which the path then computes whether or not --aov exports it)
         dn = sc.denoise_params(passes=args.denoise) if per_view and args.denoise is not None else None
-        aovs = torch.empty((n_views, H, lw, 4), device="cuda", dtype=torch.float32) if per_view and (args.aov or dn is not None) else None
+        # (--reproject: every view's frame accumulated over the views before it; --denoise then filters the accumulated frames)
+        rp = sc.reproject_params(max_history=args.reproject) if per_view and args.reproject is not None else None
+        aovs = torch.empty((n_views, H, lw, 4), device="cuda", dtype=torch.float32) if per_view and (args.aov or dn is not None or rp is not None) else None
+        accumulated = torch.empty((n_views, H, lw, 4), device="cuda", dtype=torch.float32) if rp is not None else None
         denoised = torch.empty((n_views, H, lw, 4), device="cuda", dtype=torch.float32) if dn is not None else None
         depths = None
         if aovs is not None and args.holdout_sphere is not None:
             depths = torch.from_numpy(np.stack([sphere_depth(api.camera_rays(v, lw, H), args.holdout_sphere) for v in views])).cuda()
         images = nrc_renderer.RenderPath(views, args.frames, train=True, out=None if per_view else False, times=times, aov_out=aovs,
-                                         aov_depths=depths, denoised_out=denoised, denoise_params=dn)
+                                         aov_depths=depths, denoised_out=denoised, denoise_params=dn, accumulated_out=accumulated, reproject_params=rp)
         loss = nrc.GetLoss(wait=True)
         failed = (math.isnan(loss) or math.isinf(loss)) and not args.skip_nonfinite      # (the all-reduced loss: the same on every rank)
         if failed:
@@ -394,7 +421,7 @@ def main(argv=None):
         elif rank == 0:
             print("orbit: %d views x %d frames, loss %.5f" % (n_views, args.frames, loss))
         if per_view and not failed:
-            host = (denoised if denoised is not None else images).cpu().numpy()
+            host = (denoised if denoised is not None else accumulated if accumulated is not None else images).cpu().numpy()
             host_aov = aovs.cpu().numpy() if aovs is not None and args.aov else None
             for i, (path, img) in enumerate(zip(export_paths(args.export, n_views), host)):
                 if host_aov is not None:

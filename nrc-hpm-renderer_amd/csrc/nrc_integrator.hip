@@ -20,6 +20,7 @@
 
 #include "nrc_denoise.hpp"
 #include "nrc_math.h"
+#include "nrc_reproject.hpp"
 #include "nrc_view_aov.hpp"
 #include "nrc_volume_keys.hpp"
 
@@ -2703,6 +2704,53 @@ __global__ __launch_bounds__(256) void k_denoise_pass(const float4* __restrict__
     out[(size_t)y * w + x] = make_float4(r.r, r.g, r.b, r.a);
 }
 
+// ------------------------------------------------------------------------------------------------ reprojection (nrc_reproject.hpp)
+// A lane per pixel of the current view, a workgroup per 32 x 8 tile, as k_denoise_pass.  The lane streams its own colour and AOV and gathers
+// the up to four history taps its point projects onto -- neighbours, so a wave's gathers of colour, AOV and count fall into a few cache
+// lines.  Every tap is loaded straight from memory under the lane's own predicate: nothing is read outside the images, nothing is staged.
+// The outputs never alias an input (launch_reproject).  The history guide is read as the AOV's own float4: it is not packed.
+struct ReprojectDevImage {
+    const float4* __restrict__ c;
+    const float4* __restrict__ g;
+    const float4* __restrict__ hc;
+    const float4* __restrict__ hg;
+    const float* __restrict__ hn;
+    uint32_t w;
+    __device__ size_t at(int x, int y) const { return (size_t)y * w + (uint32_t)x; }
+    __device__ ReprojectRgba colour(int x, int y) const
+    {
+        const float4 v = c[at(x, y)];
+        return ReprojectRgba{v.x, v.y, v.z, v.w};
+    }
+    __device__ ReprojectGuide guide(int x, int y) const
+    {
+        const float4 v = g[at(x, y)];
+        return ReprojectGuide{v.x, v.z, v.w};
+    }
+    __device__ ReprojectRgba hist_colour(int x, int y) const
+    {
+        const float4 v = hc[at(x, y)];
+        return ReprojectRgba{v.x, v.y, v.z, v.w};
+    }
+    __device__ ReprojectGuide hist_guide(int x, int y) const
+    {
+        const float4 v = hg[at(x, y)];
+        return ReprojectGuide{v.x, v.z, v.w};
+    }
+    __device__ float hist_count(int x, int y) const { return hn[at(x, y)]; }
+};
+__global__ __launch_bounds__(256) void k_reproject(const float4* __restrict__ hist_rgba, const float* __restrict__ hist_n, const float4* __restrict__ hist_aov,
+                                                  const float4* __restrict__ rgba, const float4* __restrict__ aov, float4* __restrict__ out,
+                                                  float* __restrict__ out_n, uint32_t w, uint32_t h, ReprojectView view)
+{
+    NRC_RAISE_WAVE_PRIORITY(16);
+    const uint32_t x = blockIdx.x * 32u + (threadIdx.x & 31u), y = blockIdx.y * 8u + (threadIdx.x >> 5);
+    if (x >= w || y >= h) return;
+    const ReprojectOut r = reproject_pixel(ReprojectDevImage{rgba, aov, hist_rgba, hist_aov, hist_n, w}, view, (int)w, (int)h, (int)x, (int)y);
+    out[(size_t)y * w + x] = make_float4(r.c.r, r.c.g, r.c.b, r.c.a);
+    out_n[(size_t)y * w + x] = r.n;
+}
+
 }  // namespace
 
 // ================================================================================================ launchers
@@ -3110,6 +3158,29 @@ void launch_denoise(const float* rgba, const float* aov, uint32_t w, uint32_t h,
         hipLaunchKernelGGL(k_denoise_pass, dim3(ceil_div(w, 32), ceil_div(h, 8)), dim3(256), 0, s, src, (const float2*)guide, dst, w, h, denoise_pass(p, pass));
         src = dst;
     }
+    NRC_HIP(hipGetLastError());
+}
+
+// ---- reprojection.  view comes from reproject_setup: the parameters, the frame count and the history camera have been checked.
+void launch_reproject(const float* hist_rgba, const float* hist_n, const float* hist_aov, const float* rgba, const float* aov, uint32_t w, uint32_t h,
+                      const ReprojectView& view, float* out, float* out_n, hipStream_t s)
+{
+    if (w == 0u || h == 0u || (uint64_t)w * h > kReprojectMaxPixels || ceil_div(h, 8) > 65535u) fail("reproject: bad image size");
+    const bool hist = view.has_history != 0;
+    if (hist != (hist_rgba != nullptr) || hist != (hist_n != nullptr) || hist != (hist_aov != nullptr)) fail("reproject: the history is all or none");
+    if (rgba == nullptr || aov == nullptr || out == nullptr || out_n == nullptr) fail("reproject: null image");
+    if ((((uintptr_t)rgba) | ((uintptr_t)aov) | ((uintptr_t)out) | ((uintptr_t)hist_rgba) | ((uintptr_t)hist_aov)) & 15u) fail("reproject: the images must be 16-byte aligned");
+    if ((((uintptr_t)out_n) | ((uintptr_t)hist_n)) & 3u) fail("reproject: the counts must be 4-byte aligned");
+    const size_t px = (size_t)w * h, img = px * 16u, cnt = px * 4u;
+    auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+        return b != nullptr && (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
+    };
+    auto hits_input = [&](const void* o, size_t no) {
+        return overlap(o, no, rgba, img) || overlap(o, no, aov, img) || overlap(o, no, hist_rgba, img) || overlap(o, no, hist_aov, img) || overlap(o, no, hist_n, cnt);
+    };
+    if (hits_input(out, img) || hits_input(out_n, cnt) || overlap(out, img, out_n, cnt)) fail("reproject: an output overlaps an input or the other output (no in-place operation)");
+    hipLaunchKernelGGL(k_reproject, dim3(ceil_div(w, 32), ceil_div(h, 8)), dim3(256), 0, s, (const float4*)hist_rgba, hist_n, (const float4*)hist_aov,
+                       (const float4*)rgba, (const float4*)aov, (float4*)out, out_n, w, h, view);
     NRC_HIP(hipGetLastError());
 }
 

@@ -5,6 +5,7 @@
 #include "nrc_common.hpp"
 #include "nrc_denoise.hpp"
 #include "nrc_hot_tiles.hpp"
+#include "nrc_reproject.hpp"
 #include "nrc_view_aov.hpp"
 
 namespace nrc {
@@ -206,6 +207,12 @@ void launch_ray_aov_ortho(const DevScene& sc, const DevFrame& fr, const AovOrtho
 // out.  Refused before anything is enqueued: bad parameters, out overlapping an input or the scratch.
 size_t denoise_scratch_bytes(uint32_t w, uint32_t h, uint32_t passes);
 void launch_denoise(const float* rgba, const float* aov, uint32_t w, uint32_t h, const DenoiseParams& p, float* out, void* scratch, hipStream_t s);
+
+// reprojection (nrc_reproject.hpp): the history {hist_rgba [h][w][4], hist_n [h][w], hist_aov [h][w][4]} -- all three or, with a view made
+// without history, none -- carried into the current view {rgba, aov} -> out [h][w][4], out_n [h][w]; all device memory, the images 16-byte
+// aligned.  One launch.  Refused before anything is enqueued: an output that overlaps an input or the other output, a half-given history.
+void launch_reproject(const float* hist_rgba, const float* hist_n, const float* hist_aov, const float* rgba, const float* aov, uint32_t w, uint32_t h,
+                      const ReprojectView& view, float* out, float* out_n, hipStream_t s);
 
 // ring: {uint head, uint tail, RayInfo[ring_size]}; scratch: uint32[2*T + 4]
 // start == nullptr: the whole of prep_train_rays.comp (scan, pop / trace / write, ring push).  start != nullptr (long train paths, the split

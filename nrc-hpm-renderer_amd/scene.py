@@ -431,6 +431,23 @@ def denoise_params(**kw):
     return p
 
 
+def reproject_params(**kw):
+    """The parameters of reprojection (api.Reproject / RenderPath(..., accumulated_out=); include/nrc_hpm.h, "Reproject") as a dict: the
+    defaults -- max_history 64 (the cap on the frames history may count for), sigma_alpha 0.1, sigma_depth 4.0 (in the units of t) --
+    overridden by the keywords, checked as the library checks them."""
+    p = dict(max_history=64.0, sigma_alpha=0.1, sigma_depth=4.0)
+    for k, v in kw.items():
+        if k not in p:
+            raise ValueError("reproject_params: unknown parameter %r" % (k,))
+        p[k] = float(v)
+    if not 0.0 < p["max_history"] < math.inf:      # (NaN included)
+        raise ValueError("reproject_params: max_history must be > 0 and finite")
+    for k in ("sigma_alpha", "sigma_depth"):
+        if not p[k] > 0.0:
+            raise ValueError("reproject_params: %s must be > 0 (+inf switches the term off)" % k)
+    return p
+
+
 def deep_tau_bracket(levels, z, flat, depth):
     """What a deep AOV's samples say about the optical depth in front of `depth` -- what a compositor or a shadow look-up does with them.
     levels [K], z [K][...] (the planes), flat [...][4] (the flat result of the same call), depth [...] (an image or array, or a scalar).
