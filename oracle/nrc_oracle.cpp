@@ -582,13 +582,17 @@ void orc_nrc_prep_train(const orc_scene* sc, uint32_t W, uint32_t H, uint32_t TW
                 train_target[3 * (size_t)i + 0] = fminf(8.0f, target.x);
                 train_target[3 * (size_t)i + 1] = fminf(8.0f, target.y);
                 train_target[3 * (size_t)i + 2] = fminf(8.0f, target.z);
-                if (scat[i]) {
-                    float* r = ring + 6 * (size_t)((head + push_idx[i]) % ring_size);
-                    r[0] = ro.x; r[1] = ro.y; r[2] = ro.z; r[3] = rdir.x; r[4] = rdir.y; r[5] = rdir.z;
-                }
             }
         }
     });
+    /* pushes, serially in linear train-index order: a frame that pushes more than ring_size entries writes a slot more than
+     * once, and the last push in that order wins (rows of the loop above run in any order) */
+    for (uint32_t i = 0; i < T && ring_size > 0; i++) {
+        if (!scat[i]) continue;
+        size_t p = (size_t)((i / TW) * y_dist) * W + (i % TW) * x_dist;
+        float* r = ring + 6 * (size_t)((head + push_idx[i]) % ring_size);
+        for (int k = 0; k < 3; k++) { r[k] = nrc_origin[4 * p + k]; r[3 + k] = nrc_dir[4 * p + k]; }
+    }
     if (ring_size > 0) {
         ring_head_tail[0] = head + n_push;     /* atomicAdd leaves the un-wrapped counters; clear.comp wraps next frame */
         ring_head_tail[1] = tail + n_pop;

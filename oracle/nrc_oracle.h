@@ -83,7 +83,9 @@ void orc_nrc_walk_lengths(const orc_scene* sc, const orc_camera* cam, uint32_t W
                           uint32_t primary_ray_length, float primary_ray_prob, const float frame_random[4], float* primary_rgba,
                           float* info, float* nrc_origin, float* nrc_dir, int n_threads, uint16_t* walk_lengths, uint32_t walks_per_pixel);
 
-/* nrc/clear.comp + nrc/prep_train_rays.comp, deterministic two-phase ring semantics. */
+/* nrc/clear.comp + nrc/prep_train_rays.comp, deterministic two-phase ring semantics: pops read the ring as it was at
+ * frame start; pushes are then applied in linear train-index order, slot (head + rank) % ring_size, and where a frame pushes more
+ * than ring_size entries the last push in that order wins.  No result depends on n_threads. */
 void orc_nrc_prep_train(const orc_scene* sc, uint32_t W, uint32_t H, uint32_t TW, uint32_t TH,
                         uint32_t x_dist, uint32_t y_dist, uint32_t train_spp, uint32_t train_ray_length,
                         uint32_t ring_size, const float frame_random[4],

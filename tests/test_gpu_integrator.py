@@ -373,8 +373,10 @@ def test_prep_train_spp_ray_length_and_small_ring(api, orc, sc, cloud16, torch_g
         ren.SetFrameRandom(frs[f])
         ren.Render(None, False)
         o = orc.nrc_gen_rays(scene, cam, W, H, 1, 0.0, frs[f], threads=8)
+        head_before = int(head_tail[0]) % tg["ring_size"]
         tin, tgt = orc.nrc_prep_train(scene, W, H, tg["tw"], tg["th"], tg["x_dist"], tg["y_dist"], 3, 4, tg["ring_size"],
                                       frs[f], o["info"], o["origin"], o["dir"], head_tail, ring, threads=8)
+        assert int(head_tail[0]) - head_before > tg["ring_size"]      # the frame pushes more than the ring holds: slots are written twice
         assert same_bits(ren.Buffer("train_input").cpu().numpy(), tin)
         assert same_bits(ren.Buffer("train_target").cpu().numpy(), tgt)
         rb = ren.Buffer("ring").cpu().numpy()
