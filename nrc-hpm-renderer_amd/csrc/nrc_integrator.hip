@@ -299,6 +299,17 @@ __device__ __forceinline__ uint32_t index24(uint32_t z, uint32_t ny, uint32_t y,
     asm("s_nop 1\n\tv_mad_u32_u24 %0, %1, %2, %3\n\tv_mad_u32_u24 %0, %0, %4, %5" : "=&v"(r) : "v"(z), "s"(ny), "v"(y), "s"(nx), "v"(x));
     return r;
 }
+// Two indices with the same ny, nx (the two collisions of a trip) behind ONE pad: the hazard can only come from an instruction in front of
+// the statement -- inside it nothing writes a scalar register, and the pad's two wait states plus every mad issued since only add distance.
+__device__ __forceinline__ void index24x2(uint32_t ny, uint32_t nx, uint32_t z0, uint32_t y0, uint32_t x0, uint32_t z1, uint32_t y1, uint32_t x1,
+                                          uint32_t* i0, uint32_t* i1)
+{
+    uint32_t r0, r1;
+    asm("s_nop 1\n\tv_mad_u32_u24 %0, %2, %3, %4\n\tv_mad_u32_u24 %1, %7, %3, %8\n\tv_mad_u32_u24 %0, %0, %5, %6\n\tv_mad_u32_u24 %1, %1, %5, %9"
+        : "=&v"(r0), "=&v"(r1) : "v"(z0), "s"(ny), "v"(y0), "s"(nx), "v"(x0), "v"(z1), "v"(y1), "v"(x1));
+    *i0 = r0;
+    *i1 = r1;
+}
 
 // volume.glsl:31-39; sampler: R8 UNORM, NEAREST, CLAMP_TO_BORDER black (src/Texture3D.cpp:79-81,221).
 // One byte per voxel, fetched with a 32-bit voxel index (24-bit mads); the per-axis border test is branch-free and
@@ -353,20 +364,22 @@ __device__ __forceinline__ Addr2 fetch2_addr(const C& c, V3 dir, V3 start, float
     bool in1 = (max(max(nrc_f2u(u.y), nrc_f2u(v.y)), nrc_f2u(w.y)) < 0x3f800000u) & second;
     const uint32_t x0 = (uint32_t)fx.x, y0 = (uint32_t)fy.x, z0 = (uint32_t)fz.x;
     const uint32_t x1 = (uint32_t)fx.y, y1 = (uint32_t)fy.y, z1 = (uint32_t)fz.y;
-    const uint32_t idx0 = index24(z0, s.ny, y0, s.nx, x0);
-    const uint32_t idx1 = index24(z1, s.ny, y1, s.nx, x1);
+    uint32_t idx0, idx1;
+    index24x2(s.ny, s.nx, z0, y0, x0, z1, y1, x1, &idx0, &idx1);
     // The LDS occupancy bits are tested behind a wave-uniform test for the table, as in round 3.  Round 4 measured both: without the test
     // k_gen_rays is 1 % faster alone (0.2092 against 0.2117 ms: one branch and four mask merges fewer per trip) and 12 % faster inside the
     // configs[4] frame (0.283 against 0.318 ms) -- and the FRAMES are slower, 7 730 against 7 850 Msamples/s on the default preset and 4 160
     // against 4 810 on configs[4]: a camera kernel that issues more densely leaves the inference / training kernels beside it fewer issue
     // slots (train stage 0.18 -> 0.23 ms, configs[4] train rays 0.53 -> 0.98 ms), and those set the frame rate wherever they are the
-    // longer chain.  (tools/ab_config.sh, same box, lib / lib_o0 / lib_m0o0 / round 3's.)
+    // longer chain.  (tools/ab_config.sh, same box, lib / lib_o0 / lib_m0o0 / round 3's.)  Measured again with the masks and pads of DESIGN.md
+    // section 4.4 "Trip overhead" in place: 11 / 8 instructions fewer per delta / ratio trip without the test, two registers fewer -- and the
+    // default frame at 9 385-9 413 Msamples/s against 9 467-9 534 with the test (the parent: 9 408-9 427).  The test stays.
     if (c.occ != nullptr) {
         // occupancy bit of the voxel's cell from LDS: an empty cell's byte is 0 without asking memory.  (The table always exists --
         // Scene::build_occupancy_bits.)
         const uint32_t sh = s.occ_shift;
-        uint32_t c0 = index24(z0 >> sh, s.occ_gy, y0 >> sh, s.occ_gx, x0 >> sh);
-        uint32_t c1 = index24(z1 >> sh, s.occ_gy, y1 >> sh, s.occ_gx, x1 >> sh);
+        uint32_t c0, c1;
+        index24x2(s.occ_gy, s.occ_gx, z0 >> sh, y0 >> sh, x0 >> sh, z1 >> sh, y1 >> sh, x1 >> sh, &c0, &c1);
         c0 = in0 ? c0 : 0u;
         c1 = in1 ? c1 : 0u;
         in0 &= ((c.occ[c0 >> 5] >> (c0 & 31u)) & 1u) != 0u;
@@ -448,15 +461,21 @@ __device__ __forceinline__ V3 new_ray_dir(C& c, V3 old_dir, bool phase_sampling)
     return nd;
 }
 
+// a per-lane predicate as a wave-uniform 64-bit lane mask and back (why the loops carry masks: see ratio_track)
+__device__ __forceinline__ bool lane_bool(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+__device__ __forceinline__ unsigned long long lane_mask(bool b) { return __builtin_amdgcn_ballot_w64(b); }
 // ---- include/path_trace.glsl
 // RatioTrack, path_trace.glsl:24-43.  Two collisions per trip: nothing in a step depends on the previous fetch, so both free-
 // flight logs share packed math.  The loop is software-pipelined: a trip's two gathers are issued at the top of the loop body,
 // the NEXT trip is located (hash chain, logs, positions, voxel indices -- about 80 instructions that do not depend on any
 // density) while they are in flight, and only then are the densities used.  A lane that ends on a collision keeps the RNG state
 // of that draw, exactly as the one-step loop would; the trip located ahead of it is dropped.
+// The two predicates of a located trip leave it as lane masks, formed where the compare is (the compare writes the mask: no instruction).
+// Handed on as bools and turned into masks at the bottom of the loop -- another basic block -- each cost a v_cndmask 0/1 and a v_cmp_ne.
+// ("Trip overhead": what each of these rewrites took out of a trip, and the ones that were measured and dropped.)
 struct RatioTrip {
     float s1, s2, t1, t2;
-    bool live1, second;       // collision 1 / collision 2 lie inside the segment
+    unsigned long long live1_m, second_m;       // collision 1 / collision 2 lie inside the segment
 };
 __device__ __forceinline__ RatioTrip ratio_trip(float rng, float t, float t_max, float inv)
 {
@@ -466,13 +485,20 @@ __device__ __forceinline__ RatioTrip ratio_trip(float rng, float t, float t_max,
     const f2 l = logf2(f2{1.0f - r.s1, 1.0f - r.s2});
     r.t1 = nrc_fmaf_(-l.x, inv, t);
     r.t2 = nrc_fmaf_(-l.y, inv, r.t1);
-    r.live1 = !(r.t1 >= t_max);
-    r.second = !(r.t2 >= t_max);
+    r.live1_m = lane_mask(!(r.t1 >= t_max));
+    r.second_m = lane_mask(!(r.t2 >= t_max));
     return r;
 }
-// a per-lane predicate as a wave-uniform 64-bit lane mask and back (why the loops carry masks: see ratio_track)
-__device__ __forceinline__ bool lane_bool(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
-__device__ __forceinline__ unsigned long long lane_mask(bool b) { return __builtin_amdgcn_ballot_w64(b); }
+// The cap of 128 collisions as a lane mask: all ones in the trips that start at collisions 0 .. 124, 0 in the 64th.  An ordinary 64-bit value
+// that the loops AND into their masks; written as `last ? 0 : m` at every use, the compiler turns each use into its own compare-and-select
+// chain through SCC (twelve scalar instructions in a delta trip).  The empty asm keeps it from folding the mask back into selects.
+// (delta_track only: ratio_track's single use costs no more as a select, and a uniform `break` behind the 64th trip made both loops longer.)
+__device__ __forceinline__ unsigned long long cap_mask(uint32_t i)
+{
+    unsigned long long m = (unsigned long long)((long long)((int)i - 126) >> 63);
+    asm("" : "+s"(m));
+    return m;
+}
 // ---- thin trips: two lanes per surviving walk ---------------------------------------------------------------------------------
 // A tracking loop runs until its last walk ends: the trips issued with at most 32 of the 64 lanes still walking cost 28 % of the
 // launch (round 2's cut-tail build, docs/MEASUREMENT_LOG.md).  When a loop is down to 32 walks or fewer they are handed to lane PAIRS (lane p and p + 32, state pushed
@@ -600,8 +626,8 @@ __device__ __forceinline__ float ratio_track(C& c, V3 start, V3 end, bool valid 
     unsigned long long dead_m = 0ull;
     uint32_t pend = 0u;                        // (counting builds) the wave's masked look-ups of the located trip that would have gone to memory
     RatioTrip a = ratio_trip(rng, 0.0f, t_max, inv);
-    unsigned long long live1_m = lane_mask(a.live1), second_m = lane_mask(a.second);
-    Addr2 ia = fetch2_addr(c, dir, start, a.t1, a.t2, a.live1, a.live1 & a.second);
+    unsigned long long live1_m = a.live1_m, second_m = a.second_m;
+    Addr2 ia = fetch2_addr(c, dir, start, a.t1, a.t2, lane_bool(a.live1_m), lane_bool(a.live1_m & a.second_m));
     float bs = rng, bt = 0.0f;                 // base of the located trip `a`: chain value and position before its first draw
     for (uint32_t i = 0;; i += 2) {            // i counts collisions: at most 128 (path_trace.glsl:34)
         rng = lane_bool(alive_m & ~live1_m) ? a.s1 : rng;             // collision 1 beyond the segment: the walk ends on this draw
@@ -621,10 +647,10 @@ __device__ __forceinline__ float ratio_track(C& c, V3 start, V3 end, bool valid 
         const bool last = i + 2 >= 128;
         const unsigned long long two_m = alive_m & second_m;
         const unsigned long long more_m = last ? 0ull : two_m;
-        const bool more = lane_bool(more_m);
         const RatioTrip b = ratio_trip(a.s2, a.t2, t_max, inv);      // ... fly while the next trip is located
         uint32_t pend_b = 0u;
-        const Addr2 ib = fetch2_addr(c, dir, start, b.t1, b.t2, more & b.live1, more & b.live1 & b.second, lane_bool(dead_m),
+        const unsigned long long go1_m = more_m & b.live1_m;
+        const Addr2 ib = fetch2_addr(c, dir, start, b.t1, b.t2, lane_bool(go1_m), lane_bool(go1_m & b.second_m), lane_bool(dead_m),
                                      C::counting ? &pend_b : nullptr);
         __builtin_amdgcn_sched_barrier(0);
         const f2 dens = fetch2_density(c.sc, fa);
@@ -636,8 +662,8 @@ __device__ __forceinline__ float ratio_track(C& c, V3 start, V3 end, bool valid 
         dead_m = lane_mask(tr == 0.0f);
         rng = lane_bool(alive_m & ~more_m) ? a.s2 : rng;              // ends after collision 1 / after the 128th collision
         alive_m = more_m;
-        live1_m = lane_mask(b.live1);
-        second_m = lane_mask(b.second);
+        live1_m = b.live1_m;
+        second_m = b.second_m;
         bs = a.s2;
         bt = a.t2;
         a.s1 = b.s1; a.s2 = b.s2; a.t1 = b.t1; a.t2 = b.t2;
@@ -743,7 +769,7 @@ __device__ __forceinline__ V3 trace_scene(C& c, V3 pos, V3 dir, bool valid = tru
 // accept 2 -- ends the walk with the RNG state the one-step loop would have, and the trip located ahead is dropped
 struct DeltaTrip {
     float s1, a1, s2, a2, t1, t2;
-    bool live1, second;
+    unsigned long long live1_m, second_m;       // as RatioTrip's
 };
 __device__ __forceinline__ DeltaTrip delta_trip(float rng, float t, float t_max, float inv)
 {
@@ -755,8 +781,8 @@ __device__ __forceinline__ DeltaTrip delta_trip(float rng, float t, float t_max,
     const f2 l = logf2(f2{1.0f - r.s1, 1.0f - r.s2});
     r.t1 = nrc_fmaf_(-l.x, inv, t);
     r.t2 = nrc_fmaf_(-l.y, inv, r.t1);
-    r.live1 = !(r.t1 >= t_max);
-    r.second = !(r.t2 >= t_max);
+    r.live1_m = lane_mask(!(r.t1 >= t_max));
+    r.second_m = lane_mask(!(r.t2 >= t_max));
     return r;
 }
 // CUT, `cut` (the first walk of a camera path, DESIGN.md section 4.4 "Far cut"): behind t = cut the ray is in empty space for good and the
@@ -782,8 +808,8 @@ __device__ __forceinline__ V3 delta_track(C& c, V3 ro, V3 rd, bool* volume_exit,
     unsigned long long alive_m = lane_mask(valid), hit_m = 0ull, vexit_m = 0ull;
     float t_hit = 0.0f;
     DeltaTrip a = delta_trip(rng, 0.0f, t_max, inv);
-    unsigned long long live1_m = lane_mask(a.live1), second_m = lane_mask(a.second);
-    Addr2 ia = fetch2_addr(c, rd, ro, a.t1, a.t2, a.live1, a.live1 & a.second);
+    unsigned long long live1_m = a.live1_m, second_m = a.second_m;
+    Addr2 ia = fetch2_addr(c, rd, ro, a.t1, a.t2, lane_bool(a.live1_m), lane_bool(a.live1_m & a.second_m));
     float bs = rng, bt = 0.0f;                 // base of the located trip `a`
     for (uint32_t i = 0;; i += 2) {            // i counts collisions: at most 128 (path_trace.glsl:161); predicated like ratio_track
         const unsigned long long out1_m = alive_m & ~live1_m;        // collision 1 beyond the exit point
@@ -796,10 +822,10 @@ __device__ __forceinline__ V3 delta_track(C& c, V3 ro, V3 rd, bool* volume_exit,
         NRC_PROF_LIVE(2, alive_m);
         const Fetch2 fa = fetch2_load(c, ia);
         __builtin_amdgcn_sched_barrier(0);
-        const bool last = i + 2 >= 128;
         const DeltaTrip b = delta_trip(a.a2, a.t2, t_max, inv);      // located ahead; used only if this trip accepts nothing
-        const bool maybe = lane_bool(last ? 0ull : (alive_m & second_m));
-        const Addr2 ib = fetch2_addr(c, rd, ro, b.t1, b.t2, maybe & b.live1, maybe & b.live1 & b.second);
+        const unsigned long long cap_m = cap_mask(i);
+        const unsigned long long go1_m = alive_m & second_m & cap_m & b.live1_m;
+        const Addr2 ib = fetch2_addr(c, rd, ro, b.t1, b.t2, lane_bool(go1_m), lane_bool(go1_m & b.second_m));
         __builtin_amdgcn_sched_barrier(0);
         const f2 dens = fetch2_density(c.sc, fa) * splat(inv);
         c.count(alive ? 1u : 0u);
@@ -814,15 +840,16 @@ __device__ __forceinline__ V3 delta_track(C& c, V3 ro, V3 rd, bool* volume_exit,
             c.count_cut(alive3_m & lane_mask(a.t2 >= cut), acc2_m | lane_mask(fa.b1 != 0u));
         }
         hit_m |= acc1_m | acc2_m;
-        t_hit = lane_bool(acc1_m) ? a.t1 : (lane_bool(acc2_m) ? a.t2 : t_hit);
+        t_hit = lane_bool(acc2_m) ? a.t2 : t_hit;                    // (two plain selects: the masks are disjoint)
+        t_hit = lane_bool(acc1_m) ? a.t1 : t_hit;
         vexit_m |= out2_m;
         // RNG state of the event that ended the walk: accept 1 -> a1, exit 2 -> s2, accept 2 or the 128-collision cap -> a2
         rng = lane_bool(acc1_m) ? a.a1 : rng;
         rng = lane_bool(out2_m) ? a.s2 : rng;
-        rng = lane_bool(last ? alive3_m : acc2_m) ? a.a2 : rng;
-        alive_m = last ? 0ull : (alive3_m & ~acc2_m);
-        live1_m = lane_mask(b.live1);
-        second_m = lane_mask(b.second);
+        rng = lane_bool(acc2_m | (alive3_m & ~cap_m)) ? a.a2 : rng;
+        alive_m = alive3_m & ~acc2_m & cap_m;
+        live1_m = b.live1_m;
+        second_m = b.second_m;
         bs = a.a2;
         bt = a.t2;
         a.s1 = b.s1; a.a1 = b.a1; a.s2 = b.s2; a.a2 = b.a2; a.t1 = b.t1; a.t2 = b.t2;
