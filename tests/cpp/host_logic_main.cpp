@@ -1,4 +1,4 @@
-// host_logic_main.cpp -- the library's device-free host logic (csrc/nrc_schedule.hpp, nrc_checkpoint.hpp, nrc_occupancy.hpp, nrc_owned.hpp) driven on
+// host_logic_main.cpp -- the library's device-free host logic (csrc/nrc_schedule.hpp, nrc_checkpoint.hpp, nrc_occupancy.hpp, nrc_owned.hpp, nrc_frame_state.hpp) driven on
 // the CPU; tests/test_host_logic_asan.py builds this with AddressSanitizer + UndefinedBehaviorSanitizer and runs it.
 //   host_logic_main <scratch directory> <path of nrc-hpm-renderer_amd/schedules.txt>
 // Every CHECK compares a value; the last line printed is "host_logic: <n> cases, <m> checks" (exit status 1 if any check failed).
@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../nrc-hpm-renderer_amd/csrc/nrc_checkpoint.hpp"
+#include "../../nrc-hpm-renderer_amd/csrc/nrc_frame_state.hpp"
 #include "../../nrc-hpm-renderer_amd/csrc/nrc_occupancy.hpp"
 #include "../../nrc-hpm-renderer_amd/csrc/nrc_owned.hpp"
 #include "../../nrc-hpm-renderer_amd/csrc/nrc_schedule.hpp"
@@ -702,6 +703,177 @@ static void owned_cases()
     }
 }
 
+// ======================================================================================== 7. frame bookkeeping (nrc_frame_state.hpp)
+// One frame of a script: the caller pins numbers (index into caller_numbers; -1: none), announces the next frame's (hint; -1: none), and
+// the frame promotes hot tiles or not.  Driven the way Renderer::render drives the type: pin / hint, take, was_predicted, announce_next.
+struct RandomStep { int pin, hint; bool promote; };
+static void caller_numbers(int k, float* r4) { for (int c = 0; c < 4; c++) r4[c] = (float)(16 * k + c + 1) / 1024.0f; }
+static void model_draw(std::mt19937& rng, float* r4, int* draws)
+{
+    std::uniform_real_distribution<float> u(0.0f, 1.0f);
+    for (int c = 0; c < 4; c++) r4[c] = u(rng);
+    (*draws)++;
+}
+// The straight-line model: ONE generator; a frame gets its pinned numbers, else the numbers drawn ahead, else a draw; a promoting frame
+// makes the next frame's numbers known -- the hint, else the numbers drawn ahead (drawn now when there are none).  Returns the draws.
+static int frame_randoms_equal_model(const std::vector<RandomStep>& script, const std::vector<int>& want_predicted, int zero_draws_through)
+{
+    const uint32_t seed = 20250917u;
+    FrameRandoms fr(seed);
+    std::mt19937 rng(seed);
+    int draws = 0;
+    float ahead[4], known[4];
+    bool have_ahead = false, next_known = false;
+    CHECK(want_predicted.size() == script.size());
+    for (size_t f = 0; f < script.size(); f++) {
+        const RandomStep& s = script[f];
+        float pin[4], hint[4], want[4], got[4] = {-1, -1, -1, -1};
+        if (s.pin >= 0) { caller_numbers(s.pin, pin); fr.pin(pin); }
+        if (s.hint >= 0) { caller_numbers(s.hint, hint); fr.hint(hint); }
+        if (s.pin >= 0) std::memcpy(want, pin, 16);
+        else if (have_ahead) { std::memcpy(want, ahead, 16); have_ahead = false; }
+        else model_draw(rng, want, &draws);
+        fr.take(got);
+        CHECK(std::memcmp(got, want, 16) == 0);
+        const bool predicted = next_known && std::memcmp(known, want, 16) == 0;
+        CHECK(fr.was_predicted(got) == predicted);
+        CHECK(predicted == (want_predicted[f] != 0));
+        if (s.promote) {
+            if (s.hint >= 0) std::memcpy(known, hint, 16);
+            else {
+                if (!have_ahead) { model_draw(rng, ahead, &draws); have_ahead = true; }
+                std::memcpy(known, ahead, 16);
+            }
+        }
+        next_known = s.promote;
+        fr.announce_next(s.promote);
+        CHECK(fr.generator() == rng);      // as many draws as the model, after every frame
+        if ((int)f <= zero_draws_through) CHECK(fr.generator() == std::mt19937(seed));
+    }
+    return draws;
+}
+static void frame_randoms_cases()
+{
+    begin_case("frame randoms: free, pinned and hinted frames, promotion on and off");
+    {
+        const std::vector<RandomStep> a = {
+            {-1, -1, true}, {-1, -1, true},      // free: a draw and a draw ahead; free: the numbers drawn ahead
+            {2, -1, true}, {-1, -1, true},       // pinned while numbers drawn ahead wait: they wait on; the free frame behind it takes them
+            {4, 5, true}, {5, -1, true},         // pinned + hint; the frame that uses the hint
+            {-1, -1, true},
+            {7, 8, true}, {9, -1, true},         // pinned + hint; a pinned frame that does not use it
+            {-1, -1, false}, {-1, -1, false},    // no promotion: nothing drawn ahead, a fresh draw
+            {-1, -1, true},
+            {-1, 3, false}, {3, -1, true},       // a hint without promotion lapses
+        };
+        CHECK(frame_randoms_equal_model(a, {0, 1, 0, 1, 0, 1, 1, 0, 0, 1, 0, 0, 1, 0}, -1) == 9);
+        const std::vector<RandomStep> b = {
+            {0, 1, true}, {1, 2, true}, {2, 3, true}, {3, -1, true},      // four frames of one render_frames call: no draw before the last
+            {-1, -1, true},
+            {4, 5, false}, {5, -1, true},        // the hint of a frame that does not promote is not known to the next
+            {-1, -1, true},
+            {6, 7, true}, {-1, -1, true},        // hinted, then free after all: the numbers drawn ahead, not the hint
+            {-1, -1, false}, {-1, -1, true},
+        };
+        CHECK(frame_randoms_equal_model(b, {0, 1, 1, 1, 1, 0, 0, 1, 0, 0, 1, 0}, 2) == 6);
+    }
+    begin_case("frame randoms: pin and take alone");
+    {
+        // a renderer that never announces (McRenderer): the unpinned frames' numbers are the generator's sequence, a pinned frame takes none
+        FrameRandoms fr(1337u);
+        std::mt19937 rng(1337u);
+        int draws = 0;
+        for (int f = 0; f < 12; f++) {
+            float pin[4], want[4], got[4];
+            if (f % 3 == 1) { caller_numbers(f, pin); fr.pin(pin); std::memcpy(want, pin, 16); }
+            else model_draw(rng, want, &draws);
+            fr.take(got);
+            CHECK(std::memcmp(got, want, 16) == 0 && fr.generator() == rng);
+        }
+        CHECK(draws == 8);
+    }
+}
+
+// Renderer::render's cost-order conditions as they read before TileOrderClock, on plain variables
+struct OrderTranscript {
+    bool cost_order = true, order_pending = false, order_resample = false;
+    int order_cur = 0;
+    uint64_t order_pending_frame = 0;
+    bool flipped = false, sample_cost = false;
+    void frame(uint64_t frame_index, int lag)
+    {
+        flipped = false;
+        if (cost_order && order_pending && frame_index >= order_pending_frame + (uint64_t)lag) {
+            order_cur ^= 1;
+            order_pending = false;
+            flipped = true;
+        }
+        sample_cost = cost_order && !order_pending && (frame_index % 4 == 0 || order_resample);
+        if (sample_cost) order_resample = false;
+        if (sample_cost) {
+            order_pending = true;
+            order_pending_frame = frame_index;
+        }
+    }
+};
+// 40 frames of both; medium_at: frames in front of which the medium changes; off_from / on_from: cost order off in [off_from, on_from).
+// The frames that sampled and that flipped, as bit masks.
+static void order_clock_equals_transcript(int lag, const std::vector<uint64_t>& medium_at, uint64_t* sampled, uint64_t* flipped,
+                                          uint64_t off_from = 99, uint64_t on_from = 99)
+{
+    TileOrderClock clock;
+    OrderTranscript was;
+    *sampled = *flipped = 0;
+    for (uint64_t n = 0; n < 40; n++) {
+        for (uint64_t m : medium_at) if (m == n) { clock.medium_changed(); was.order_resample = true; }
+        if (n == off_from) clock.on = was.cost_order = false;
+        if (n == on_from) clock.on = was.cost_order = true;
+        // (what tile_order() reads back in front of the frame: the buffer the frame will launch in, whether cost order is on or not)
+        CHECK(clock.due(n, lag) == (was.order_pending && n >= was.order_pending_frame + (uint64_t)lag));
+        was.frame(n, lag);
+        const bool flip = clock.take_effect(n, lag);
+        const bool sample = clock.samples(n);
+        if (sample) { CHECK(clock.other() == (clock.current() ^ 1)); clock.sort_enqueued(n); }
+        CHECK(flip == was.flipped && sample == was.sample_cost);
+        CHECK(clock.current() == was.order_cur && clock.sort_pending() == was.order_pending);
+        if (sample) *sampled |= 1ull << n;
+        if (flip) *flipped |= 1ull << n;
+    }
+}
+static uint64_t frames(std::initializer_list<int> list) { uint64_t m = 0; for (int n : list) m |= 1ull << n; return m; }
+static void tile_order_clock_cases()
+{
+    uint64_t sampled = 0, flipped = 0;
+    begin_case("tile order clock: 40 frames at lag 2, 3 and 5");
+    {
+        order_clock_equals_transcript(2, {}, &sampled, &flipped);
+        CHECK(sampled == frames({0, 4, 8, 12, 16, 20, 24, 28, 32, 36}) && flipped == frames({2, 6, 10, 14, 18, 22, 26, 30, 34, 38}));
+        order_clock_equals_transcript(3, {}, &sampled, &flipped);
+        CHECK(sampled == frames({0, 4, 8, 12, 16, 20, 24, 28, 32, 36}) && flipped == frames({3, 7, 11, 15, 19, 23, 27, 31, 35, 39}));
+        // a lag beyond the sampling interval: frame 4 finds the sort of frame 0 still waiting and does not sample
+        order_clock_equals_transcript(5, {}, &sampled, &flipped);
+        CHECK(sampled == frames({0, 8, 16, 24, 32}) && flipped == frames({5, 13, 21, 29, 37}));
+    }
+    begin_case("tile order clock: a medium change forces the next free frame to sample");
+    {
+        // in front of frame 1 a sort is waiting: no sample before frame 2, where it takes effect; in front of frame 23 none is: frame 23
+        // samples, and frame 24 finds that sort waiting
+        order_clock_equals_transcript(2, {1, 23}, &sampled, &flipped);
+        CHECK(sampled == frames({0, 2, 4, 8, 12, 16, 20, 23, 28, 32, 36}) && flipped == frames({2, 4, 6, 10, 14, 18, 22, 25, 30, 34, 38}));
+        // lag 3: frame 23 is also where the sort of frame 20 takes effect -- it flips, then samples
+        order_clock_equals_transcript(3, {1, 23}, &sampled, &flipped);
+        CHECK(sampled == frames({0, 3, 8, 12, 16, 20, 23, 28, 32, 36}) && flipped == frames({3, 6, 11, 15, 19, 23, 26, 31, 35, 39}));
+    }
+    begin_case("tile order clock: cost order off");
+    {
+        order_clock_equals_transcript(2, {5, 6}, &sampled, &flipped, 0);
+        CHECK(sampled == 0 && flipped == 0);
+        // switched off with a sort waiting: it takes effect with the first frame after cost order is back on
+        order_clock_equals_transcript(2, {}, &sampled, &flipped, 9, 14);
+        CHECK(sampled == frames({0, 4, 8, 16, 20, 24, 28, 32, 36}) && flipped == frames({2, 6, 14, 18, 22, 26, 30, 34, 38}));
+    }
+}
+
 int main(int argc, char** argv)
 {
     if (argc != 3) { std::printf("usage: host_logic_main <scratch directory> <schedules.txt>\n"); return 2; }
@@ -712,6 +884,8 @@ int main(int argc, char** argv)
     tuner_cases();
     key_cases(argv[2]);
     owned_cases();
+    frame_randoms_cases();
+    tile_order_clock_cases();
     std::printf("host_logic: %d cases, %d checks%s\n", g_cases, g_checks, g_failed ? ", FAILED" : "");
     return g_failed ? 1 : 0;
 }

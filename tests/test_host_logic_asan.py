@@ -1,8 +1,10 @@
 """Sanitizer run of the library's device-free host logic (VERDICT.md weak point 15): the schedule-cache text parser, the schedule key, the
 event-pool bookkeeping and the schedule tuner (csrc/nrc_schedule.hpp), the checkpoint file reader / writer (nrc_checkpoint.hpp) and the
-occupancy builders (nrc_occupancy.hpp) and the move-only owners of handles and device memory (nrc_owned.hpp) are plain C++17 that
+occupancy builders (nrc_occupancy.hpp), the move-only owners of handles and device memory (nrc_owned.hpp) and the renderers' frame
+bookkeeping (nrc_frame_state.hpp: which random numbers a frame uses, when a sorted tile order takes effect) are plain C++17 that
 nrc_api.hip includes; tests/cpp/host_logic_main.cpp drives them on the CPU under ASan + UBSan (no recovery) -- the tuner against a
-scripted clock, reset in mid-trial and event-pool wrap included; the owners against an allocator of the program's own."""
+scripted clock, reset in mid-trial and event-pool wrap included; the owners against an allocator of the program's own; the frame
+bookkeeping against the conditions Renderer::render held before, frame by frame."""
 import os
 import re
 import subprocess
@@ -10,14 +12,16 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "nrc-hpm-renderer_amd", "csrc")
 HOST_HEADERS = ["nrc_fail.hpp", "nrc_owned.hpp", "nrc_schedule.hpp", "nrc_checkpoint.hpp", "nrc_occupancy.hpp"]
-CASES = 27      # begin_case calls of host_logic_main.cpp
+FRAME_HEADERS = ["nrc_frame_state.hpp"]
+CASES = 32      # begin_case calls of host_logic_main.cpp
 
 
 def test_host_headers_compile_without_rocm():
     """each on its own, warnings as errors, include/ the only include path; no HIP / RCCL identifier outside comments"""
     makefile = open(os.path.join(CSRC, "Makefile")).read()
     assert re.search(r"^HOST_HDRS = " + " ".join(HOST_HEADERS) + "$", makefile, re.M), "HOST_HEADERS here and HOST_HDRS of csrc/Makefile differ"
-    for h in HOST_HEADERS:
+    assert re.search(r"^FRAME_HDRS = " + " ".join(FRAME_HEADERS) + "$", makefile, re.M), "FRAME_HEADERS here and FRAME_HDRS of csrc/Makefile differ"
+    for h in HOST_HEADERS + FRAME_HEADERS:
         r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"),
                             "-include", h, "-x", "c++", os.devnull], capture_output=True, text=True, cwd=CSRC)
         assert r.returncode == 0, r.stderr[-4000:]
