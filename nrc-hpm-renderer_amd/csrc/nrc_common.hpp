@@ -154,31 +154,6 @@ inline PinnedCell make_pinned_cell()
     return PinnedCell(p);
 }
 
-// O'Neill's pcg32 (XSH-RR) as tiny-cuda-nn vendors it (pcg32.h): its Trainer seeds pcg32{1337}, i.e. stream initseq = 1
-struct Pcg32 {
-    uint64_t state = 0, inc = 1;
-    void seed(uint64_t init_state, uint64_t init_seq = 1u)
-    {
-        state = 0; inc = (init_seq << 1) | 1u; next(); state += init_state; next();
-    }
-    uint32_t next()
-    {
-        uint64_t old = state;
-        state = old * 6364136223846793005ULL + inc;
-        uint32_t xs = (uint32_t)(((old >> 18u) ^ old) >> 27u);
-        uint32_t rot = (uint32_t)(old >> 59u);
-        return (xs >> rot) | (xs << ((32u - rot) & 31u));
-    }
-    // pcg32::next_float: a float in [1, 2) from the top 23 bits (the MTGP trick), minus 1
-    float nextf()
-    {
-        const uint32_t u = (next() >> 9) | 0x3f800000u;
-        float f;
-        __builtin_memcpy(&f, &u, 4);
-        return f - 1.0f;
-    }
-};
-
 }  // namespace nrc
 
 // Every kernel of the library that can share a SIMD with k_gen_rays raises its waves to the SAME user wave priority, the highest

@@ -40,18 +40,7 @@ constexpr int KS0 = ENC / 16;    // k-steps of layer 0
 constexpr int KSH = WIDTH / 16;  // k-steps of a hidden layer
 constexpr int MT = WIDTH / 32;   // 32-row M tiles per layer
 
-// canonical feature index held by (k-step s, lane half h, element j) of the layer-0 B operand.
-// s<4: natural order 16s+8h+j = four (sin,cos) pairs of one (dim, frequency quad);
-// s=4: both lane halves get two (sin,cos) pairs of dim 2 and the four OneBlob bins of ONE direction dim,
-//      so the two halves of a wave execute the same instruction stream.
-__host__ __device__ inline int fmap80(int s, int h, int j)
-{
-    if (s < 4) return 16 * s + 8 * h + j;
-    if (j < 4) return 64 + 4 * h + j;
-    return 72 + 4 * h + (j - 4);
-}
-// neuron index held by (k-step s, lane half h, element j) when a 32x32 accumulator pair is re-used as B operand
-__host__ __device__ inline int kperm(int s, int h, int j) { return 16 * s + 8 * (j >> 2) + 4 * h + (j & 3); }
+// (fmap80, kperm: the k-orders of the layer-0 and hidden-layer B operands, nrc_mlp_plan.hpp)
 
 __device__ __forceinline__ half8 ld_frag(const uint4* lw, int frag, int lane)
 {
@@ -461,8 +450,7 @@ __global__ __launch_bounds__(THREADS, THREADS == 512 && NT == 2 ? 4 : 1) void k_
 // set the kernels' time).  Now the wave turns each 16-row x 32-sample block through 1.25 KB of its own LDS (8 ds_write_b16, one
 // ds_read_b128 per lane; rows padded to 40 halves so that the two lane halves hit different banks) and stores 16 bytes per lane.
 // PERM: the half8's rows are 8(j>>2) + 4h + (j&3) (an accumulator pair re-used as operand, kperm), else 8h + j (natural order).
-constexpr int KG_ROW = 40;                          // halves per scratch row
-constexpr int KG_SCRATCH = 16 * KG_ROW * 2;         // bytes per wave
+// (KG_ROW halves per scratch row, KG_SCRATCH bytes per wave: nrc_mlp_plan.hpp, beside the LDS sizes they enter)
 template <bool PERM>
 __device__ __forceinline__ void store_kgroups(half_t* scratch, const half8& v, int lane, half_t* dst_row0, uint32_t rows)
 {
@@ -765,11 +753,7 @@ static void launch_encode(uint32_t pos_id, uint32_t dir_id, hipStream_t s, const
 // level, base resolution 16, per-level scale 2).  tiny-cuda-nn v1.6 grid semantics (PARITY UNPINNED):
 // pos = fma(scale, x, 0.5), trilinear weights over the 8 corners, dense index while res^3 fits the level else the coherent
 // prime hash, index % level size.  The table is trainable: fp32 master + EMA in the parameter vector, fp16 (half2 per
-// entry) copies for the gathers.
-constexpr uint32_t HG_LEVELS = 16;
-struct HashLevels {
-    uint32_t off[HG_LEVELS + 1];      // per-level entry offsets
-};
+// entry) copies for the gathers.  (HG_LEVELS, HashLevels: nrc_mlp_plan.hpp)
 
 #pragma clang fp contract(off)
 __device__ __forceinline__ void hg_corners(const HashLevels& lv, uint32_t level, const float (&x)[3], uint32_t (&idx)[8], float (&w8)[8])
@@ -1009,17 +993,10 @@ __global__ __launch_bounds__(256) void k_encode_hash_list(const float* __restric
 // gather pass folds it into the entries it finishes and clears it), and every entry is rounded ONCE, from its exact sum, to the fp16 pair
 // the optimizer and the list exchange read (round 4 summed in fp32 in arrival order; tiny-cuda-nn's atomics round every partial sum).
 // A list holds twice the pairs the level sends a bin on average (a dense coarse level's bins are crowded: 16 384 pairs each for 32^3).
-#ifndef NRC_GB_BIN_LOG2
-#define NRC_GB_BIN_LOG2 11
-#endif
+// (GB_BIN and the other GB_ constants, GridBins, LooseRanges and the plan that fills them: nrc_mlp_plan.hpp)
 #ifndef NRC_GB_GATHER_THREADS
 #define NRC_GB_GATHER_THREADS 512
 #endif
-constexpr uint32_t GB_BIN_LOG2 = NRC_GB_BIN_LOG2, GB_BIN = 1u << GB_BIN_LOG2, GB_MAX_BINS = 1u << (20 - NRC_GB_BIN_LOG2), GB_MIN_BINS = 8;
-struct GridBins {
-    uint32_t first[HG_LEVELS], count[HG_LEVELS];      // per level: index of its first bin, number of bins (0: no lists, the level adds into the shadow)
-    uint32_t cap[HG_LEVELS], list0[HG_LEVELS];        // pairs a bin's list holds; pair offset of the level's first list
-};
 // fp16 bits -> value * 2^24 (exact; inf / nan read as 2^15 * 2^25: deterministic, and the loss is not finite then anyway)
 __device__ __forceinline__ long long half_to_fix(uint32_t h)
 {
@@ -1114,9 +1091,6 @@ __global__ __launch_bounds__(256) void k_grid_scatter(const float* __restrict__ 
 // pass 2.  Workgroups 0 .. n_bins - 1: one bin each -- bin_info[b] = {table entry of the bin's first slot, pair offset of its list, the list's
 // capacity, 0}; resets the bin's counter for the next step.  The workgroups behind them walk the entries of the levels WITHOUT bins
 // (loose[k] = {first entry, count}, n_loose ranges, GB_BIN entries per workgroup) and turn their shadow sums into the gradient.
-struct LooseRanges {
-    uint32_t first[HG_LEVELS], count[HG_LEVELS], n;
-};
 __global__ __launch_bounds__(NRC_GB_GATHER_THREADS) void k_grid_gather(uint32_t* __restrict__ grad16, const uint4* __restrict__ bin_info, uint32_t n_bins,
                                                     uint32_t* __restrict__ counters, const uint2* __restrict__ lists, long long* __restrict__ fix,
                                                     LooseRanges loose)
@@ -1974,14 +1948,11 @@ __global__ __launch_bounds__(256, NRC_TRAIN_GEN2_MIN_WAVES) void k_train_gen2(Tr
 // ------------------------------------------------------------------------------------------------ training: weight gradients
 // dW_l = delta_l (rows: out neurons, k: samples) * a_{l-1}^T.  One workgroup per K-chunk of samples, one 32x32
 // output tile per wave iteration, partial result to this chunk's slab (fixed-order reduction afterwards).
-struct WgradTile {
-    uint32_t a_row0, b_row0, m_valid, n_valid, param_off, in_dim;
-};
+// (WgradTile, WGRAD_CHUNK: nrc_mlp_plan.hpp)
 #ifndef NRC_WGRAD_WAVES
 #define NRC_WGRAD_WAVES 7
 #endif
 constexpr int WGRAD_WAVES = NRC_WGRAD_WAVES;
-constexpr uint32_t WGRAD_CHUNK = 128;
 
 __global__ __launch_bounds__(WGRAD_WAVES * 64) void k_wgrad(const half_t* __restrict__ deltas,
                                                            const half_t* __restrict__ acts, uint32_t n,
@@ -2029,17 +2000,10 @@ __global__ __launch_bounds__(WGRAD_WAVES * 64) void k_wgrad(const half_t* __rest
 // samples) is chosen by the host so that the launch is ~2 workgroups per CU; the partial sums go to the chunk's slab and are added
 // in the fixed order of k_reduce_grads as before (bitwise reproducible; for a 6x64 net the chunk is the old 128 samples and the
 // gradient is bit-identical to k_wgrad's).
-struct WgradTask {
-    uint32_t a_row0, b_row0, m_valid, n_tiles, n_valid_last, param_off, in_dim, pad;
-};
-#ifndef NRC_WGRAD2_NTL
-#define NRC_WGRAD2_NTL 4            // 32-column blocks (accumulators) per task, at most 4
-#endif
+// (WgradTask, WGRAD2_WAVES, WGRAD2_NTL: nrc_mlp_plan.hpp)
 #ifndef NRC_WGRAD2_U
 #define NRC_WGRAD2_U 2              // k-steps per pipeline stage
 #endif
-constexpr int WGRAD2_WAVES = 4;
-constexpr int WGRAD2_NTL = NRC_WGRAD2_NTL;
 constexpr int WGRAD2_U = NRC_WGRAD2_U;
 template <int NTL>
 __device__ __forceinline__ void wgrad_task(const WgradTask& T, const half_t* __restrict__ deltas, const half_t* __restrict__ acts, uint32_t k0,
@@ -2404,210 +2368,71 @@ __global__ void k_pack(const float* __restrict__ w, const float* __restrict__ em
 }  // namespace
 
 // ================================================================================================ host
-static uint32_t pos_enc_dims(uint32_t id) { return id == 0 ? 32u : id == 1 ? 3u : id == 2 ? 36u : id == 3 ? 72u : 0u; }
-static uint32_t dir_enc_dims(uint32_t id) { return id == 0 ? 8u : id == 1 ? 2u : id == 2 ? 8u : ~0u; }
-
-Mlp::Mlp(const nrc_config& cfg) : cfg_(cfg)
+template <class T>
+static void upload(DevBuf<T>& d, const void* host, size_t bytes, const char* name)
 {
-    width_ = cfg.nn_width;
-    depth_ = cfg.nn_depth;
-    if (pos_enc_dims(cfg.pos_id) == 0 || dir_enc_dims(cfg.dir_id) == ~0u) fail("NNEncodingConfig posID/dirID is invalid");
-    if (width_ != 16 && width_ != 32 && width_ != 64 && width_ != 128)
-        fail("nnWidth must be 16, 32, 64 or 128 -- tiny-cuda-nn's FullyFusedMLP widths (got " + std::to_string(width_) + ")");
-    // a 16-wide network runs on the 32-row MFMA tiles of the 32-wide kernels: neurons 16..31 of every hidden layer have all-zero
-    // fragment entries, so they stay exactly 0 through ReLU and contribute exactly 0 downstream; the parameter vector, gradients
-    // and optimizer see the true 16-wide shapes (half of the MFMA work is padding: the model is 10x cheaper than 6x64 anyway)
-    kw_ = width_ < 32 ? 32 : width_;
+    d.alloc(bytes, name);
+    NRC_HIP(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
+}
+// kernels that ask for more dynamic LDS than the default limit (per instance = per device: the attribute belongs to the device's code object)
+template <class... K>
+static void allow_dynamic_lds(int bytes, K... kernels)
+{
+    for (const void* k : {reinterpret_cast<const void*>(kernels)...}) NRC_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+}
+
+// plan (nrc_mlp_plan.hpp), allocate, upload, repack
+Mlp::Mlp(const nrc_config& cfg) : cfg_(cfg), plan_(make_mlp_plan(cfg))
+{
+    const MlpPlan& p = plan_;
     xcd8_ = device_xcds() == 8;
-    if (depth_ < 1 || depth_ > 16) fail("nnDepth must be in 1..16 (got " + std::to_string(depth_) + ")");
-    if (std::strcmp(cfg.optimizer, "Adam") == 0) sgd_ = false;
-    else if (std::strcmp(cfg.optimizer, "SGD") == 0) sgd_ = true;
-    else fail(std::string("unsupported optimizer ") + cfg.optimizer + " (Adam and SGD are built; both run inside the EMA wrapper)");
-    if (std::strcmp(cfg.loss_fn, "RelativeL2Luminance") == 0) loss_id_ = 0;
-    else if (std::strcmp(cfg.loss_fn, "L2") == 0) loss_id_ = 1;
-    else if (std::strcmp(cfg.loss_fn, "RelativeL2") == 0) loss_id_ = 2;
-    else if (std::strcmp(cfg.loss_fn, "L1") == 0) loss_id_ = 3;
-    else if (std::strcmp(cfg.loss_fn, "Mape") == 0) loss_id_ = 4;
-    else if (std::strcmp(cfg.loss_fn, "Smape") == 0) loss_id_ = 5;
-    else if (std::strcmp(cfg.loss_fn, "LogL1") == 0) loss_id_ = 6;
-    else
-        fail(std::string("unsupported loss ") + cfg.loss_fn +
-             " (built: RelativeL2Luminance, L2, RelativeL2, L1, Mape, Smape, LogL1; tiny-cuda-nn's CrossEntropy and Variance need a "
-             "sample pdf the NRC path does not have)");
-    // encoded width, padded to a multiple of 16 with 1.0 (tiny-cuda-nn); the fused kernels cover the north-star model
-    enc_dims_ = (pos_enc_dims(cfg.pos_id) + dir_enc_dims(cfg.dir_id) + 15u) / 16u * 16u;
-    fused_ = cfg.pos_id == 3 && cfg.dir_id == 0 && width_ == 64 && depth_ == 6;
+    std::copy(p.hg_off, p.hg_off + HG_LEVELS + 1, levels_.off);
+    const MlpInit init = mlp_initial_params(p, cfg.seed);
+    const FragMaps maps = make_frag_maps(p);
+    const std::vector<int32_t> dst = invert_frag_maps(maps.fwd, maps.inf(), maps.bwd, p.n_mlp, debug_switch("no_fused_opt"));
+    n_frag_fwd_ = maps.n_frag_fwd;
+    n_frag_bwd_ = maps.n_frag_bwd;
+    fused_opt_ = !dst.empty();
+    tcnn_dead_rows_[0] = tcnn_dead_rows_[1] = init.dead_rows;      // the EMA copy starts as the weights
+    tcnn_dead_rows_[2] = tcnn_dead_rows_[3] = std::vector<float>(init.dead_rows.size(), 0.0f);
 
-    uint32_t off = 0;
-    for (uint32_t l = 0; l <= depth_; l++) {
-        MlpLayer L;
-        L.in = l == 0 ? enc_dims_ : width_;
-        L.out = l == depth_ ? 3u : width_;
-        L.off = off;
-        off += L.in * L.out;
-        layers_.push_back(L);
-    }
-    n_mlp_ = off;
-    hash_ = cfg.pos_id == 0;
-    uint32_t n_grid = 0;
-    if (hash_) {      // per-level tables: dense while res^3 (rounded up to 8) fits, else 2^log2_hashmap_size entries
-        const uint32_t log2_size = cfg.hashgrid_log2_size ? cfg.hashgrid_log2_size : 19u;
-        if (log2_size < 4 || log2_size > 24) fail("hashgrid_log2_size must be in 4..24");
-        uint32_t o = 0;
-        for (uint32_t l = 0; l < HG_LEVELS; l++) {
-            const double dense = std::pow((double)(16u << l), 3.0);
-            uint32_t cnt = dense > 2147483647.0 ? 2147483647u : (uint32_t)dense;
-            cnt = (cnt + 7u) / 8u * 8u;
-            if (cnt > (1u << log2_size)) cnt = 1u << log2_size;
-            hg_off_[l] = o;
-            o += cnt;
-        }
-        hg_off_[HG_LEVELS] = o;
-        n_grid_entries_ = o;
-        n_grid = o * 2u;
-    }
-    n_params_ = n_mlp_ + n_grid;
-    // k_grid_opt2 updates four parameters (two entries) per 16-byte access.  Neither can fail: every matrix has a multiple of 16 rows or
-    // columns (widths 16..128, enc_dims_ padded to 16), every level a multiple of 8 or 2^k >= 16 entries.
-    if (n_mlp_ % 4u != 0u || n_grid_entries_ % 2u != 0u) fail("the table optimizer needs n_mlp % 4 == 0 and an even number of table entries");
-
-    // tiny-cuda-nn v1.6's initialisation (src/NeuralRadianceCache.cu:39 -> tcnn::create_from_config -> Trainer::initialize_params;
-    // recalled from upstream, the submodule is absent -- DESIGN.md section 2): pcg32{seed} on stream 1; the network's matrices first
-    // -- each Xavier-uniform under the bound sqrt(6 / (rows + columns)) of its STORED shape, element = next_float() * 2 * scale - scale
-    // in that order of operations, the output matrix stored with 16 rows (rows 3..15 feed the padded outputs nobody reads: drawn,
-    // kept for the tcnn-layout dump, never part of this model) --, then the table: generate_random_uniform's GPU order (thread i of
-    // ceil(n / 4) rounded up to 128 writes draw 4 i + j to element i + n_threads * j), value = fma(u, 2e-4, -1e-4).
-    std::vector<float> w(n_params_);
-    Pcg32 rng;
-    rng.seed(cfg.seed, 1);
-    for (int k = 0; k < 4; k++) tcnn_dead_rows_[k].assign((size_t)13 * width_, 0.0f);
-    for (uint32_t l = 0; l <= depth_; l++) {
-        const MlpLayer& L = layers_[l];
-        const uint32_t rows = l == depth_ ? 16u : L.out;
-        const float scale = 1.0f * sqrtf(6.0f / (float)(L.in + rows));
-        for (uint32_t i = 0; i < L.in * rows; i++) {
-            const float x = rng.nextf() * 2.0f * scale - scale;
-            if (i < L.in * L.out) w[L.off + i] = x;
-            else tcnn_dead_rows_[0][i - L.in * L.out] = x;
-        }
-    }
-    tcnn_dead_rows_[1] = tcnn_dead_rows_[0];      // the EMA copy starts as the weights
-    if (n_grid > 0) {
-        const size_t n_threads = (((size_t)n_grid + 3) / 4 + 127) / 128 * 128;
-        const float lower = -1e-4f, upper = 1e-4f;
-        for (size_t k = 0; k < 4 * n_threads; k++) {
-            const float u = rng.nextf();
-            const size_t idx = k / 4 + n_threads * (k % 4);
-            if (idx < n_grid) w[n_mlp_ + idx] = fmaf(u, upper - lower, lower);
-        }
-    }
-
-    const size_t pb = (size_t)n_params_ * sizeof(float);
+    const size_t pb = (size_t)p.n_params * sizeof(float), nf = maps.fwd.size(), nb = maps.bwd.size();
     d_w_.alloc(pb, "d_w_");
     d_ema_.alloc(pb, "d_ema_");
     d_m_.alloc(pb, "d_m_");
     d_v_.alloc(pb, "d_v_");
     // gradient vector and the {loss, pad} cell share one allocation so that the multi-GPU driver all-reduces both at once
     d_grad_.alloc(pb + 4 * sizeof(float), "d_grad_");
-    d_loss_ = d_grad_ + n_params_;
-    NRC_HIP(hipMemcpy(d_w_, w.data(), pb, hipMemcpyHostToDevice));
-    NRC_HIP(hipMemcpy(d_ema_, w.data(), pb, hipMemcpyHostToDevice));
+    d_loss_ = d_grad_ + p.n_params;
+    NRC_HIP(hipMemcpy(d_w_, init.w.data(), pb, hipMemcpyHostToDevice));
+    NRC_HIP(hipMemcpy(d_ema_, init.w.data(), pb, hipMemcpyHostToDevice));
     NRC_HIP(hipMemset(d_m_, 0, pb));
     NRC_HIP(hipMemset(d_v_, 0, pb));
     NRC_HIP(hipMemset(d_grad_, 0, pb + 4 * sizeof(float)));
 
-    // fragment-image gather tables: [frag][lane][8]; layer 0 [mt][s], hidden layer l [mt][s], output [s];
-    // backward image: hidden layer l (W^T) [mt over inputs][s over outputs], output layer [mt] (one k-step, 3 live rows)
-    const int D = (int)depth_, mt_n = (int)kw_ / 32, ksh = (int)kw_ / 16, ks0 = (int)enc_dims_ / 16, W = (int)width_;
-    const int E = (int)enc_dims_;
-    const int hid_base = mt_n * ks0, out_base = hid_base + (D - 1) * mt_n * ksh;
-    n_frag_fwd_ = (uint32_t)(out_base + ksh);
-    const int din_base = (D - 1) * mt_n * ksh + mt_n;      // W0^T fragments (rows = encoded dims 0..31) for dL/d(input)
-    n_frag_bwd_ = (uint32_t)(din_base + (hash_ ? ksh : 0));
-    std::vector<int32_t> sf((size_t)n_frag_fwd_ * 512, -1), sb((size_t)n_frag_bwd_ * 512, -1);
-    auto slot = [](int frag, int lane, int j) { return ((size_t)frag * 64 + lane) * 8 + j; };
-    for (int lane = 0; lane < 64; lane++) {
-        const int r = lane & 31, h = lane >> 5;
-        for (int j = 0; j < 8; j++) {
-            for (int mt = 0; mt < mt_n; mt++) {
-                const bool row_ok = 32 * mt + r < W;          // rows / columns beyond the true width stay -1 = zero (width 16)
-                for (int s = 0; s < ks0; s++) {
-                    const int k = fused_ ? fmap80(s, h, j) : 16 * s + 8 * h + j;
-                    if (row_ok) sf[slot(mt * ks0 + s, lane, j)] = (int32_t)(layers_[0].off + (32 * mt + r) * E + k);
-                }
-                for (int l = 1; l < D; l++)
-                    for (int s = 0; s < ksh; s++) {
-                        if (!row_ok || kperm(s, h, j) >= W) continue;
-                        sf[slot(hid_base + (l - 1) * mt_n * ksh + mt * ksh + s, lane, j)] =
-                            (int32_t)(layers_[l].off + (32 * mt + r) * W + kperm(s, h, j));
-                        sb[slot((l - 1) * mt_n * ksh + mt * ksh + s, lane, j)] =
-                            (int32_t)(layers_[l].off + kperm(s, h, j) * W + (32 * mt + r));
-                    }
-                const int k = 8 * h + j;
-                if (k < 3 && row_ok) sb[slot((D - 1) * mt_n * ksh + mt, lane, j)] = (int32_t)(layers_[D].off + k * W + (32 * mt + r));
-            }
-            for (int s = 0; s < ksh; s++) {
-                if (kperm(s, h, j) >= W) continue;
-                if (r < 3) sf[slot(out_base + s, lane, j)] = (int32_t)(layers_[D].off + r * W + kperm(s, h, j));
-                if (hash_) sb[slot(din_base + s, lane, j)] = (int32_t)(layers_[0].off + kperm(s, h, j) * E + r);
-            }
-        }
-    }
-    d_src_fwd_.alloc(sf.size() * 4, "d_src_fwd_");
-    d_src_bwd_.alloc(sb.size() * 4, "d_src_bwd_");
-    NRC_HIP(hipMemcpy(d_src_fwd_, sf.data(), sf.size() * 4, hipMemcpyHostToDevice));
-    // Generic models with the Frequency(12) + OneBlob(4) input (configs[4]'s 8x128): EMA inference encodes inside k_infer_gen as
-    // k_infer does, so its image takes layer 0's inputs in that encoder's order (fmap80); training keeps k_encode's natural order
-    enc80_generic_ = !fused_ && !hash_ && cfg.pos_id == 3 && cfg.dir_id == 0;
+    upload(d_src_fwd_, maps.fwd.data(), nf * 4, "d_src_fwd_");
     d_src_inf_ = d_src_fwd_;
-    if (enc80_generic_) {
-        std::vector<int32_t> si = sf;
-        for (int lane = 0; lane < 64; lane++)
-            for (int j = 0; j < 8; j++)
-                for (int mt = 0; mt < mt_n; mt++)
-                    for (int s = 0; s < ks0; s++)
-                        if (32 * mt + (lane & 31) < W)
-                            si[slot(mt * ks0 + s, lane, j)] = (int32_t)(layers_[0].off + (32 * mt + (lane & 31)) * E + fmap80(s, lane >> 5, j));
-        d_src_inf_own_.alloc(si.size() * 4, "d_src_inf_");
+    if (!maps.inf_own.empty()) {
+        upload(d_src_inf_own_, maps.inf_own.data(), nf * 4, "d_src_inf_");
         d_src_inf_ = d_src_inf_own_;
-        NRC_HIP(hipMemcpy(d_src_inf_, si.data(), si.size() * 4, hipMemcpyHostToDevice));
     }
-    NRC_HIP(hipMemcpy(d_src_bwd_, sb.data(), sb.size() * 4, hipMemcpyHostToDevice));
-    for (auto& p : d_pk_infer_) {
-        p.alloc(sf.size() * 2, "d_pk_infer_");
-        NRC_HIP(hipMemset(p, 0, sf.size() * 2));      // k_opt_pack never writes the padding slots
+    upload(d_src_bwd_, maps.bwd.data(), nb * 4, "d_src_bwd_");
+    for (auto& pk : d_pk_infer_) {
+        pk.alloc(nf * 2, "d_pk_infer_");
+        NRC_HIP(hipMemset(pk, 0, nf * 2));      // k_opt_pack never writes the padding slots
     }
-    // inverse maps for the one-launch optimizer step (k_opt_pack): parameter -> its slot in each image
-    fused_opt_ = !debug_switch("no_fused_opt");
-    if (fused_opt_) {
-        std::vector<int32_t> dst((size_t)3 * n_mlp_, -1);
-        auto invert = [&](const int32_t* src, size_t n_slots, int32_t* out) {
-            for (size_t j = 0; j < n_slots; j++) {
-                if (src[j] < 0) continue;
-                if ((uint32_t)src[j] >= n_mlp_ || out[src[j]] >= 0) { fused_opt_ = false; return; }      // not a one-to-one image
-                out[src[j]] = (int32_t)j;
-            }
-        };
-        std::vector<int32_t> si_host(sf.size());
-        NRC_HIP(hipMemcpy(si_host.data(), d_src_inf_, sf.size() * 4, hipMemcpyDeviceToHost));
-        invert(sf.data(), sf.size(), dst.data());
-        if (fused_opt_) invert(si_host.data(), si_host.size(), dst.data() + n_mlp_);
-        if (fused_opt_) invert(sb.data(), sb.size(), dst.data() + 2 * (size_t)n_mlp_);
-        if (fused_opt_) {
-            d_dst_.alloc(dst.size() * 4, "d_dst_");
-            NRC_HIP(hipMemcpy(d_dst_, dst.data(), dst.size() * 4, hipMemcpyHostToDevice));
-        }
-    }
-    d_pk_fwd_.alloc(sf.size() * 2, "d_pk_fwd_");
-    d_pk_bwd_.alloc(sb.size() * 2, "d_pk_bwd_");
-    if (hash_) {
-        d_t16_train_.alloc((size_t)n_grid_entries_ * 4, "d_t16_train_");
-        for (auto& p : d_t16_ema_) p.alloc((size_t)n_grid_entries_ * 4, "d_t16_ema_");
-        d_grad16_.alloc((size_t)n_grid_entries_ * 4, "d_grad16_");
+    if (fused_opt_) upload(d_dst_, dst.data(), dst.size() * 4, "d_dst_");
+    d_pk_fwd_.alloc(nf * 2, "d_pk_fwd_");
+    d_pk_bwd_.alloc(nb * 2, "d_pk_bwd_");
+    if (p.hash) {
+        d_t16_train_.alloc((size_t)p.n_grid_entries * 4, "d_t16_train_");
+        for (auto& t : d_t16_ema_) t.alloc((size_t)p.n_grid_entries * 4, "d_t16_ema_");
+        d_grad16_.alloc((size_t)p.n_grid_entries * 4, "d_grad16_");
     }
     repack(nullptr);
     NRC_HIP(hipStreamSynchronize(nullptr));
 }
+
 
 float* Mlp::buffer(int which)
 {
@@ -2621,24 +2446,6 @@ float* Mlp::buffer(int which)
     }
 }
 
-void Mlp::to_tcnn_layout(int which, const float* own, float* tcnn) const
-{
-    if (which < 0 || which > 4) fail("bad parameter buffer id");
-    const size_t n_out = (size_t)3 * width_, head = n_mlp_ - n_out, dead = (size_t)13 * width_;
-    std::memcpy(tcnn, own, (head + n_out) * sizeof(float));
-    if (which < 4) std::memcpy(tcnn + n_mlp_, tcnn_dead_rows_[which].data(), dead * sizeof(float));
-    else std::memset(tcnn + n_mlp_, 0, dead * sizeof(float));
-    std::memcpy(tcnn + n_mlp_ + dead, own + n_mlp_, (size_t)(n_params_ - n_mlp_) * sizeof(float));
-}
-
-void Mlp::from_tcnn_layout(int which, const float* tcnn, float* own)
-{
-    if (which < 0 || which > 4) fail("bad parameter buffer id");
-    const size_t dead = (size_t)13 * width_;
-    std::memcpy(own, tcnn, (size_t)n_mlp_ * sizeof(float));
-    if (which < 4) std::memcpy(tcnn_dead_rows_[which].data(), tcnn + n_mlp_, dead * sizeof(float));
-    std::memcpy(own + n_mlp_, tcnn + n_mlp_ + dead, (size_t)(n_params_ - n_mlp_) * sizeof(float));
-}
 
 // The inference (EMA) image and table are double-buffered: this writes the set inference is NOT reading and then makes it
 // current for every inference enqueued from now on.  An inference pass enqueued earlier keeps reading the other set, so the
@@ -2650,9 +2457,9 @@ void Mlp::repack(hipStream_t s)
     const int next = infer_set_ ^ 1;
     hipLaunchKernelGGL(k_pack, dim3(ceil_div(nmax, 256)), dim3(256), 0, s, d_w_, d_ema_, d_src_fwd_, d_src_inf_, nf, d_src_bwd_, nb,
                        (half_t*)d_pk_infer_[next], (half_t*)d_pk_fwd_, (half_t*)d_pk_bwd_);
-    if (hash_)
-        hipLaunchKernelGGL(k_pack_grid, dim3(ceil_div(n_grid_entries_, 256)), dim3(256), 0, s, d_w_ + n_mlp_, d_ema_ + n_mlp_,
-                           d_t16_train_, d_t16_ema_[next], n_grid_entries_);
+    if (plan_.hash)
+        hipLaunchKernelGGL(k_pack_grid, dim3(ceil_div(plan_.n_grid_entries, 256)), dim3(256), 0, s, d_w_ + plan_.n_mlp, d_ema_ + plan_.n_mlp,
+                           d_t16_train_, d_t16_ema_[next], plan_.n_grid_entries);
     NRC_HIP(hipGetLastError());
     infer_set_ = next;
 }
@@ -2665,15 +2472,14 @@ void Mlp::launch_features(const float* d_in, uint32_t n, bool use_ema, int slot,
 {
     ensure_features(n, slot);
     half_t* feat = (half_t*)d_feat_[slot];
-    if (!hash_) {
+    if (!plan_.hash) {
         launch_encode(cfg_.pos_id, cfg_.dir_id, s, d_in, feat, n, skip_zero);
         return;
     }
-    HashLevels lv;
-    for (uint32_t l = 0; l <= HG_LEVELS; l++) lv.off[l] = hg_off_[l];
+    const HashLevels& lv = levels_;
     const uint32_t* tab = use_ema ? d_t16_ema_[infer_set_] : d_t16_train_;
     if (slot == 0 && live_list != nullptr && skip_zero) {      // renderer inference with the frame's live-query list
-        const uint32_t n_slots = enc_dims_ / 2;
+        const uint32_t n_slots = plan_.enc_dims / 2;
         dim3 g((uint32_t)num_cus() * 2u, n_slots);
         uint32_t xc = 0;
         if (xcd8_ && n_slots % 8u == 0u) {      // a level's table is gathered from one XCD (see the kernel)
@@ -2686,7 +2492,7 @@ void Mlp::launch_features(const float* d_in, uint32_t n, bool use_ema, int slot,
         return;
     }
     if (slot == kInferSlot || slot == kSideSlot) {      // inference: level-major gathers and feature layout (k_encode_hash_lm / k_infer_gen<..., true>)
-        const dim3 g(ceil_div(n, 256), enc_dims_ / 2);
+        const dim3 g(ceil_div(n, 256), plan_.enc_dims / 2);
         const int sk = skip_zero ? 1 : 0;
         if (cfg_.dir_id == 0) hipLaunchKernelGGL(k_encode_hash_lm<0>, g, dim3(256), 0, s, d_in, tab, (uint32_t*)feat, n, lv, sk);
         else if (cfg_.dir_id == 1) hipLaunchKernelGGL(k_encode_hash_lm<1>, g, dim3(256), 0, s, d_in, tab, (uint32_t*)feat, n, lv, sk);
@@ -2736,7 +2542,7 @@ void Mlp::ensure_features(uint32_t n, int slot)
 {
     if (n <= feat_n_[slot]) return;
     if (d_feat_[slot]) NRC_HIP(hipDeviceSynchronize());      // a kernel on another stream may still read the old buffer
-    d_feat_[slot].alloc((size_t)n * enc_dims_ * 2, "d_feat_[slot]");
+    d_feat_[slot].alloc((size_t)n * plan_.enc_dims * 2, "d_feat_[slot]");
     feat_n_[slot] = n;
 }
 
@@ -2746,28 +2552,28 @@ void Mlp::infer(const float* d_in, float* d_out, uint32_t n, bool use_ema, hipSt
     if (n == 0) return;
     if (feat_slot != kInferSlot && feat_slot != kSideSlot) throw std::logic_error("SkyRenderer ERROR: bad inference feature slot");
     const uint4* img = (const uint4*)(use_ema ? d_pk_infer_[infer_set_] : d_pk_fwd_);
-    if (!fused_) {
+    if (!plan_.fused) {
         // EMA inference of a Frequency(12) + OneBlob(4) model encodes inside the MLP kernel (image in the encoder's input order);
         // everything else runs the encoding kernel first
-        const bool enc80 = enc80_generic_ && use_ema;
+        const bool enc80 = plan_.enc80_generic && use_ema;
         if (!enc80) launch_features(d_in, n, use_ema, feat_slot, s, skip_zero_queries, live_list, live_count);
         const float* skip_in = skip_zero_queries ? d_in : nullptr;
         const uint32_t* list = skip_zero_queries ? live_list : nullptr;      // renderer inference with the frame's live-query list (k_infer_gen)
         const half_t* feat = enc80 ? nullptr : (const half_t*)d_feat_[feat_slot];
-        const int ks0 = (int)enc_dims_ / 16;
+        const int ks0 = (int)plan_.enc_dims / 16;
         uint32_t blocks = ceil_div(ceil_div(n, 32), 8);
         auto launch = [&](auto kernel, uint32_t threads, size_t lds, uint32_t per_cu) {
             const uint32_t cap = (uint32_t)num_cus() * per_cu;
-            launch_last(kernel, dim3(blocks > cap ? cap : blocks), dim3(threads), (uint32_t)lds, s, feat, d_out, n, img, (int)depth_, ks0, skip_in, d_in,
+            launch_last(kernel, dim3(blocks > cap ? cap : blocks), dim3(threads), (uint32_t)lds, s, feat, d_out, n, img, (int)plan_.depth, ks0, skip_in, d_in,
                         list, list != nullptr ? live_count : nullptr);      // (the stage's last launch: takes the armed event along, nrc_common.hpp)
         };
-        if (kw_ == 32) {
+        if (plan_.kw == 32) {
             if (enc80) launch(k_infer_gen<32, 256, false, 2, true>, 256, 2 * 5 * 1024, 4);
-            else if (hash_) launch(k_infer_gen<32, 256, true>, 256, 2 * 5 * 1024, 4);
+            else if (plan_.hash) launch(k_infer_gen<32, 256, true>, 256, 2 * 5 * 1024, 4);
             else launch(k_infer_gen<32, 256, false>, 256, 2 * 5 * 1024, 4);
-        } else if (kw_ == 64) {           // 4 waves x 2 tiles = 256 samples per workgroup pass, 20 KB of LDS
+        } else if (plan_.kw == 64) {           // 4 waves x 2 tiles = 256 samples per workgroup pass, 20 KB of LDS
             if (enc80) launch(k_infer_gen<64, 256, false, 2, true>, 256, 2 * 10 * 1024, 4);
-            else if (hash_) launch(k_infer_gen<64, 256, true>, 256, 2 * 10 * 1024, 4);
+            else if (plan_.hash) launch(k_infer_gen<64, 256, true>, 256, 2 * 10 * 1024, 4);
             else launch(k_infer_gen<64, 256, false>, 256, 2 * 10 * 1024, 4);
         } else {
             // 8 waves x 1 tile = 256 samples per staged layer (32 KB), 64 KB of LDS.  One tile per wave and one 32-row block of a
@@ -2794,7 +2600,7 @@ void Mlp::infer(const float* d_in, float* d_out, uint32_t n, bool use_ema, hipSt
                 blocks = ceil_div(ceil_div(n, 32), T128 / 64);
                 constexpr uint32_t per_cu = T128 == 256 ? NRC_GEN128_WG4_PER_CU : 2;
                 if (enc80) launch(k_infer_gen<128, T128, false, 1, true>, T128, lds, per_cu);
-                else if (hash_) launch(k_infer_gen<128, T128, true, 1>, T128, lds, per_cu);
+                else if (plan_.hash) launch(k_infer_gen<128, T128, true, 1>, T128, lds, per_cu);
                 else launch(k_infer_gen<128, T128, false, 1>, T128, lds, per_cu);
             };
             if (skip_in != nullptr) launch128(std::integral_constant<int, 256>{});
@@ -2826,128 +2632,51 @@ void Mlp::infer(const float* d_in, float* d_out, uint32_t n, bool use_ema, hipSt
     NRC_HIP(hipGetLastError());
 }
 
-// the row-block tasks of k_wgrad2: one per (layer, 32-row block of its delta, group of up to four 32-column blocks of its input)
-void Mlp::build_wgrad_tasks()
-{
-    if (d_tasks_) return;
-    // Which weight-gradient kernel (and, in backward(), which generic fwd/bwd kernel): round 4's k_wgrad2 / k_train_gen2 are the faster
-    // ones alone at every width (8x128: 138 -> 64 us per step) and what the 128-wide frame needs (configs[4] 6 850 against 5 750 Msamples/s
-    // with round 3's pair); beside gen_rays the 64-wide models run better with round 3's k_wgrad / k_train_gen -- fewer, lighter workgroups
-    // (default preset + 0.7 %, HashGrid + 3.2 %, TriangleWave 64 + 2.5 %, A/B on one box).  The renderer's frame is what the library is
-    // for: round 3's kernels up to 64 neurons, round 4's for 128.  NRC_DEBUG=wgrad_old / NRC_DEBUG=train_gen_old = 0 | 1 override.
-    wgrad_old_ = debug_value("wgrad_old", kw_ <= 64 ? 1 : 0) != 0;
-    std::vector<WgradTask> tasks;
-    const uint32_t D = depth_;
-    for (uint32_t l = 0; l <= D; l++) {
-        const MlpLayer& L = layers_[l];
-        const uint32_t a_rows = l == D ? D * kw_ : l * kw_;                       // delta_l rows (kernel width: 32 for width 16)
-        const uint32_t b_rows = l == 0 ? 0 : enc_dims_ + (l - 1) * kw_;           // a_{l-1} rows (enc for l = 0)
-        for (uint32_t mt = 0; mt * 32 < L.out; mt++)
-            for (uint32_t n0 = 0; n0 * 32 < L.in; n0 += WGRAD2_NTL) {
-                WgradTask T;
-                const uint32_t tiles_left = (L.in - 32 * n0 + 31) / 32;
-                T.n_tiles = tiles_left < (uint32_t)WGRAD2_NTL ? tiles_left : (uint32_t)WGRAD2_NTL;
-                T.a_row0 = a_rows + 32 * mt;
-                T.b_row0 = b_rows + 32 * n0;
-                T.m_valid = L.out - 32 * mt < 32 ? L.out - 32 * mt : 32;
-                const uint32_t last0 = 32 * (n0 + T.n_tiles - 1);
-                T.n_valid_last = L.in - last0 < 32 ? L.in - last0 : 32;
-                T.param_off = L.off + 32 * mt * L.in + 32 * n0;
-                T.in_dim = L.in;
-                T.pad = 0;
-                tasks.push_back(T);
-            }
-    }
-    n_wgrad_tasks_ = (int)tasks.size();
-    d_tasks_.alloc(tasks.size() * sizeof(WgradTask), "d_tasks_");
-    NRC_HIP(hipMemcpy(d_tasks_, tasks.data(), tasks.size() * sizeof(WgradTask), hipMemcpyHostToDevice));
-}
-// samples per K-chunk of the weight-gradient launch: ~2 workgroups per CU, a multiple of 32 samples, at least 64
-uint32_t Mlp::wgrad_chunk(uint32_t n)
-{
-    if (wgrad_old_) return WGRAD_CHUNK;
-    const uint32_t wg_per_chunk = ceil_div((uint32_t)n_wgrad_tasks_, (uint32_t)WGRAD2_WAVES);
-    uint32_t chunks = std::max(1u, 2u * (uint32_t)num_cus() / std::max(1u, wg_per_chunk));
-    uint32_t c = ceil_div(ceil_div(n, chunks), 32u) * 32u;
-    return std::max(c, 64u);
-}
-
+// allocate for batches up to n; upload the weight-gradient lists (once) and the bin info of the table gradient (per growth)
 void Mlp::ensure_train_workspace(uint32_t n)
 {
     if (n <= ws_n_) return;
-    const size_t rows_a = enc_dims_ + (size_t)depth_ * kw_, rows_d = (size_t)depth_ * kw_ + 8;
+    const MlpPlan& p = plan_;
+    const size_t rows_a = p.enc_dims + (size_t)p.depth * p.kw, rows_d = (size_t)p.depth * p.kw + 8;
     d_acts_.alloc(rows_a * n * 2, "d_acts_");
     d_deltas_.alloc(rows_d * n * 2, "d_deltas_");
     NRC_HIP(hipMemset(d_deltas_, 0, rows_d * n * 2));
-    build_wgrad_tasks();
-    // (k_wgrad2: a smaller batch has a smaller chunk, never more chunks than the launch's target count)
-    const uint32_t max_chunks = wgrad_old_ ? ceil_div(n, WGRAD_CHUNK)
-                                           : std::max(ceil_div(n, wgrad_chunk(n)), std::max(1u, 2u * (uint32_t)num_cus() / std::max(1u, ceil_div((uint32_t)n_wgrad_tasks_, (uint32_t)WGRAD2_WAVES))));
-    d_slabs_.alloc((size_t)max_chunks * n_mlp_ * 4, "d_slabs_");
-    if (hash_) {
+    if (!d_tasks_) {
+        // Which weight-gradient kernel (and, in backward(), which generic fwd/bwd kernel): round 4's k_wgrad2 / k_train_gen2 are the faster
+        // ones alone at every width (8x128: 138 -> 64 us per step) and what the 128-wide frame needs (configs[4] 6 850 against 5 750 Msamples/s
+        // with round 3's pair); beside gen_rays the 64-wide models run better with round 3's k_wgrad / k_train_gen -- fewer, lighter workgroups
+        // (default preset + 0.7 %, HashGrid + 3.2 %, TriangleWave 64 + 2.5 %, A/B on one box).  The renderer's frame is what the library is
+        // for: round 3's kernels up to 64 neurons, round 4's for 128.  NRC_DEBUG=wgrad_old / NRC_DEBUG=train_gen_old = 0 | 1 override.
+        wgrad_old_ = debug_value("wgrad_old", p.kw <= 64 ? 1 : 0) != 0;
+        const WgradLists lists = make_wgrad_lists(p);
+        n_wgrad_tiles_ = (int)lists.tiles.size();
+        n_wgrad_tasks_ = (int)lists.tasks.size();
+        upload(d_tasks_, lists.tasks.data(), lists.tasks.size() * sizeof(WgradTask), "d_tasks_");
+        upload(d_tiles_, lists.tiles.data(), lists.tiles.size() * sizeof(WgradTile), "d_tiles_");
+    }
+    d_slabs_.alloc((size_t)wgrad_max_chunks(n, (uint32_t)n_wgrad_tasks_, wgrad_cus(), wgrad_old_) * p.n_mlp * 4, "d_slabs_");
+    if (p.hash) {
         d_denc_.alloc((size_t)n * 32 * 2, "d_denc_");
-        // bin lists of the table gradient (k_grid_scatter): levels of at least GB_MIN_BINS bins of GB_BIN entries; a level's lists hold twice
-        // what the level sends a bin on average (n * 8 / bins pairs); the rest goes into the fixed-point shadow
         d_grid_lists_.reset();
         d_grid_bin_entry0_.reset();
         d_grid_counters_.reset();
-        grid_bins_total_ = 0;
-        const bool no_bins = debug_switch("grid_no_bins");      // tests: every pair through the fixed-point shadow
-        std::vector<uint32_t> info;      // uint4 per bin: {first entry, pair offset of the list, capacity, 0}
-        size_t pairs = 0;
-        for (uint32_t l = 0; l < HG_LEVELS; l++) {
-            const uint32_t cnt = hg_off_[l + 1] - hg_off_[l];
-            const uint32_t bins = (cnt % GB_BIN == 0u) ? cnt / GB_BIN : 0u;
-            grid_bin_first_[l] = grid_bins_total_;
-            grid_bin_count_[l] = (bins >= GB_MIN_BINS && bins <= GB_MAX_BINS && !no_bins) ? bins : 0u;
-            grid_bin_cap_[l] = grid_bin_count_[l] ? std::max(1024u, (uint32_t)std::min<uint64_t>(2ull * n * 8ull / grid_bin_count_[l], 1u << 24)) : 0u;
-            grid_list0_[l] = (uint32_t)pairs;
-            for (uint32_t b = 0; b < grid_bin_count_[l]; b++) {
-                info.insert(info.end(), {hg_off_[l] + b * GB_BIN, (uint32_t)(pairs + (size_t)b * grid_bin_cap_[l]), grid_bin_cap_[l], 0u});
-            }
-            pairs += (size_t)grid_bin_count_[l] * grid_bin_cap_[l];
-            grid_bins_total_ += grid_bin_count_[l];
-        }
-        if (pairs > 0xffffffffull) fail("train batch too large for the table gradient's bin lists");
-        if (grid_bins_total_ != 0u) {
-            d_grid_lists_.alloc(pairs * 8, "d_grid_lists_");
-            d_grid_counters_.alloc((size_t)grid_bins_total_ * 4, "d_grid_counters_");
-            NRC_HIP(hipMemset(d_grid_counters_, 0, (size_t)grid_bins_total_ * 4));
-            d_grid_bin_entry0_.alloc(info.size() * 4, "d_grid_bin_info_");
-            NRC_HIP(hipMemcpy(d_grid_bin_entry0_, info.data(), info.size() * 4, hipMemcpyHostToDevice));
+        bins_ = make_grid_bin_plan(p.hg_off, n, debug_switch("grid_no_bins"));      // (tests: every pair through the fixed-point shadow)
+        if (bins_.bins_total != 0u) {
+            d_grid_lists_.alloc(bins_.pairs * 8, "d_grid_lists_");
+            d_grid_counters_.alloc((size_t)bins_.bins_total * 4, "d_grid_counters_");
+            NRC_HIP(hipMemset(d_grid_counters_, 0, (size_t)bins_.bins_total * 4));
+            upload(d_grid_bin_entry0_, bins_.info.data(), bins_.info.size() * 4, "d_grid_bin_info_");
         }
         // the fixed-point shadow of the table: two int64 per entry, all zero between two steps (k_grid_gather clears what it folds in)
         if (!d_grid_fix_) {
-            d_grid_fix_.alloc((size_t)n_grid_entries_ * 16, "d_grid_fix_");
-            NRC_HIP(hipMemset(d_grid_fix_, 0, (size_t)n_grid_entries_ * 16));
+            d_grid_fix_.alloc((size_t)p.n_grid_entries * 16, "d_grid_fix_");
+            NRC_HIP(hipMemset(d_grid_fix_, 0, (size_t)p.n_grid_entries * 16));
         }
     }
     d_loss_part_.alloc((size_t)(n / 32) * 4, "d_loss_part_");
     ws_n_ = n;
-    if (!d_tiles_) {
-        std::vector<WgradTile> tiles;
-        const uint32_t D = depth_;
-        for (uint32_t l = 0; l <= D; l++) {
-            const MlpLayer& L = layers_[l];
-            const uint32_t a_rows = l == D ? D * kw_ : l * kw_;                       // delta_l rows (kernel width: 32 for width 16)
-            const uint32_t b_rows = l == 0 ? 0 : enc_dims_ + (l - 1) * kw_;           // a_{l-1} rows (enc for l = 0)
-            for (uint32_t mt = 0; mt * 32 < L.out; mt++)
-                for (uint32_t nt = 0; nt * 32 < L.in; nt++) {
-                    WgradTile T;
-                    T.a_row0 = a_rows + 32 * mt;
-                    T.b_row0 = b_rows + 32 * nt;
-                    T.m_valid = L.out - 32 * mt < 32 ? L.out - 32 * mt : 32;
-                    T.n_valid = L.in - 32 * nt < 32 ? L.in - 32 * nt : 32;
-                    T.param_off = L.off + 32 * mt * L.in + 32 * nt;
-                    T.in_dim = L.in;
-                    tiles.push_back(T);
-                }
-        }
-        n_wgrad_tiles_ = (int)tiles.size();
-        d_tiles_.alloc(tiles.size() * sizeof(WgradTile), "d_tiles_");
-        NRC_HIP(hipMemcpy(d_tiles_, tiles.data(), tiles.size() * sizeof(WgradTile), hipMemcpyHostToDevice));
-    }
 }
+
 
 const void* Mlp::pre_encode(const float* d_in, uint32_t n, int parity, hipStream_t s)
 {
@@ -2964,13 +2693,13 @@ void Mlp::backward(const float* d_in, const float* d_target, uint32_t n, uint32_
     const uint32_t n_tiles = n / 32;
     constexpr int THREADS = 256;
     uint32_t blocks = ceil_div(n_tiles, THREADS / 64);
-    if (fused_) {
+    if (plan_.fused) {
         TrainArgs a;
         a.in = d_in;
         a.target = d_target;
         a.n = n;
         a.inv_n_total = (float)(1.0 / (3.0 * (double)n_norm));      // 3 * n_norm can exceed 32 bits
-        a.loss_id = loss_id_;
+        a.loss_id = plan_.loss_id;
         a.acts = (half_t*)d_acts_;
         a.deltas = (half_t*)d_deltas_;
         a.loss_part = d_loss_part_;
@@ -2978,26 +2707,26 @@ void Mlp::backward(const float* d_in, const float* d_target, uint32_t n, uint32_
         const size_t lds = (size_t)std::max(n_frag_fwd_, n_frag_bwd_) * 1024;      // one image at a time
         auto kernel = k_train_fwd_bwd_light<6, THREADS>;
         if (!attr_train_set_) {
-            NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            allow_dynamic_lds((int)lds, kernel);
             attr_train_set_ = true;
         }
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(THREADS), lds, s, a, (const uint4*)d_pk_fwd_, (const uint4*)d_pk_bwd_);
     } else {
         if (features_ready == nullptr) launch_features(d_in, n, false, 1, s, false);
-        if (hash_ && !grad16_clean_) NRC_HIP(hipMemsetAsync(d_grad16_, 0, (size_t)n_grid_entries_ * 4, s));      // (k_grid_opt2 leaves it clean)
+        if (plan_.hash && !grad16_clean_) NRC_HIP(hipMemsetAsync(d_grad16_, 0, (size_t)plan_.n_grid_entries * 4, s));      // (k_grid_opt2 leaves it clean)
         grad16_clean_ = false;
         TrainArgsGen a;
         a.feat = features_ready != nullptr ? (const half_t*)features_ready : (const half_t*)d_feat_[1];
         a.target = d_target;
         a.n = n;
         a.inv_n_total = (float)(1.0 / (3.0 * (double)n_norm));      // 3 * n_norm can exceed 32 bits
-        a.loss_id = loss_id_;
+        a.loss_id = plan_.loss_id;
         a.acts = (half_t*)d_acts_;
         a.deltas = (half_t*)d_deltas_;
         a.loss_part = d_loss_part_;
-        a.depth = (int)depth_;
-        a.ks0 = (int)enc_dims_ / 16;
-        a.d_enc = hash_ ? d_denc_.get() : nullptr;
+        a.depth = (int)plan_.depth;
+        a.ks0 = (int)plan_.enc_dims / 16;
+        a.d_enc = plan_.hash ? d_denc_.get() : nullptr;
         // a training batch is a few hundred 32-sample tiles (16 384 rays = 512): four-wave workgroups (128 of them) stream each
         // layer once per four tiles; large batches use eight waves, two workgroups per CU
         const bool small = n_tiles <= (uint32_t)num_cus() * 8u;
@@ -3005,116 +2734,84 @@ void Mlp::backward(const float* d_in, const float* d_target, uint32_t n, uint32_
         blocks = ceil_div(n_tiles, waves);
         const uint32_t cap = (uint32_t)num_cus() * 2u;
         if (blocks > cap) blocks = cap;
-        const int mtg = (int)kw_ / 32, ksg = (int)kw_ / 16;
-        // two weight stages + per wave: the k-group transposition scratch and one 64-bit ReLU mask per lane and layer
-        const size_t lds = (size_t)2 * mtg * (ksg > 5 ? ksg : 5) * 1024 + waves * (KG_SCRATCH + (size_t)depth_ * 512);
-        if (lds > 160 * 1024) fail("network too deep for the training kernel's LDS budget");
-        if (!attr_train_set_) {      // per instance = per device: the attribute belongs to the device's code object
-            const int cap_lds = 160 * 1024;
-            NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_gen<32, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, cap_lds));
-            NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_gen<32, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, cap_lds));
-            NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_gen<64, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, cap_lds));
-            NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_gen<64, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, cap_lds));
-            NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_gen<128, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, cap_lds));
-            NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_gen<128, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, cap_lds));
+        const size_t lds = train_gen_lds(plan_.kw, plan_.depth, waves);
+        if (!attr_train_set_) {
+            allow_dynamic_lds((int)TRAIN_GEN_LDS_CAP, &k_train_gen<32, 4>, &k_train_gen<32, 8>, &k_train_gen<64, 4>, &k_train_gen<64, 8>, &k_train_gen<128, 4>,
+                              &k_train_gen<128, 8>);
             attr_train_set_ = true;
         }
         const uint4 *fw = (const uint4*)d_pk_fwd_, *bw = (const uint4*)d_pk_bwd_;
         // round 4: rows split over the waves (k_train_gen2); NRC_DEBUG=train_gen_old=0|1 picks k_train_gen2 / k_train_gen, NRC_DEBUG=train_gen_nt|2 sets the tiles
         // per sample group
         // (the environment is read per call: a test compares the kernels inside one process)
-        const bool gen_old = debug_value("train_gen_old", kw_ <= 64 ? 1 : 0) != 0;      // (see build_wgrad_tasks)
+        const bool gen_old = debug_value("train_gen_old", plan_.kw <= 64 ? 1 : 0) != 0;      // (see ensure_train_workspace)
         const int gen_nt_env = (int)debug_value("train_gen_nt", 0);
         if (!gen_old) {
-            const uint32_t sgn = 4u / (uint32_t)mtg;                 // sample groups per workgroup
+            const uint32_t sgn = 4u / (plan_.kw / 32u);                   // sample groups per workgroup
             // (a 16 384-ray batch of an 8x128 net, stand-alone: 29.5 us with one tile per sample group, 39.8 with two; two halve the weight
             // traffic from L2 -- 33 KB per stage and sample group -- and take over where one tile would put more than four workgroups on a CU)
             const int nt = gen_nt_env == 1 || gen_nt_env == 2 ? gen_nt_env : (n_tiles > 4u * sgn * (uint32_t)num_cus() ? 2 : 1);
             uint32_t groups = ceil_div(n_tiles, sgn * (uint32_t)nt);
             if (groups > cap) groups = cap;
-            const size_t lds2 = (size_t)2 * sgn * nt * ksg * 1024 + 4 * KG_SCRATCH + (size_t)4 * depth_ * nt * 256;
-            if (lds2 > 160 * 1024) fail("network too deep for the training kernel's LDS budget");
+            const size_t lds2 = train_gen2_lds(plan_.kw, plan_.depth, sgn, nt);
             if (!attr_train2_set_) {
-                const int cap_lds = 160 * 1024;
-                NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_gen2<32, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, cap_lds));
-                NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_gen2<32, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, cap_lds));
-                NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_gen2<64, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, cap_lds));
-                NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_gen2<64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, cap_lds));
-                NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_gen2<128, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, cap_lds));
-                NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_train_gen2<128, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, cap_lds));
+                allow_dynamic_lds((int)TRAIN_GEN_LDS_CAP, &k_train_gen2<32, 1>, &k_train_gen2<32, 2>, &k_train_gen2<64, 1>, &k_train_gen2<64, 2>, &k_train_gen2<128, 1>,
+                                  &k_train_gen2<128, 2>);
                 attr_train2_set_ = true;
             }
-            if (kw_ == 32) {
+            if (plan_.kw == 32) {
                 if (nt == 1) hipLaunchKernelGGL((k_train_gen2<32, 1>), dim3(groups), dim3(256), lds2, s, a, fw, bw);
                 else hipLaunchKernelGGL((k_train_gen2<32, 2>), dim3(groups), dim3(256), lds2, s, a, fw, bw);
-            } else if (kw_ == 64) {
+            } else if (plan_.kw == 64) {
                 if (nt == 1) hipLaunchKernelGGL((k_train_gen2<64, 1>), dim3(groups), dim3(256), lds2, s, a, fw, bw);
                 else hipLaunchKernelGGL((k_train_gen2<64, 2>), dim3(groups), dim3(256), lds2, s, a, fw, bw);
             } else {
                 if (nt == 1) hipLaunchKernelGGL((k_train_gen2<128, 1>), dim3(groups), dim3(256), lds2, s, a, fw, bw);
                 else hipLaunchKernelGGL((k_train_gen2<128, 2>), dim3(groups), dim3(256), lds2, s, a, fw, bw);
             }
-        } else if (kw_ == 32) {
+        } else if (plan_.kw == 32) {
             if (small) hipLaunchKernelGGL((k_train_gen<32, 4>), dim3(blocks), dim3(256), lds, s, a, fw, bw);
             else hipLaunchKernelGGL((k_train_gen<32, 8>), dim3(blocks), dim3(512), lds, s, a, fw, bw);
-        } else if (kw_ == 64) {
+        } else if (plan_.kw == 64) {
             if (small) hipLaunchKernelGGL((k_train_gen<64, 4>), dim3(blocks), dim3(256), lds, s, a, fw, bw);
             else hipLaunchKernelGGL((k_train_gen<64, 8>), dim3(blocks), dim3(512), lds, s, a, fw, bw);
         } else {
             if (small) hipLaunchKernelGGL((k_train_gen<128, 4>), dim3(blocks), dim3(256), lds, s, a, fw, bw);
             else hipLaunchKernelGGL((k_train_gen<128, 8>), dim3(blocks), dim3(512), lds, s, a, fw, bw);
         }
-        if (hash_) {
-            HashLevels lv;
-            for (uint32_t l = 0; l <= HG_LEVELS; l++) lv.off[l] = hg_off_[l];
-            {
-                // bin lists + exact LDS sums for the large levels, the fixed-point shadow for the rest (k_grid_scatter / k_grid_gather)
-                GridBins gb;
-                LooseRanges loose;
-                loose.n = 0;
-                uint32_t loose_chunks = 0;
-                for (uint32_t l = 0; l < HG_LEVELS; l++) {
-                    gb.first[l] = grid_bin_first_[l]; gb.count[l] = grid_bin_count_[l]; gb.cap[l] = grid_bin_cap_[l]; gb.list0[l] = grid_list0_[l];
-                    if (grid_bin_count_[l] == 0u) {
-                        loose.first[loose.n] = hg_off_[l];
-                        loose.count[loose.n] = hg_off_[l + 1] - hg_off_[l];
-                        loose_chunks += ceil_div(loose.count[loose.n], GB_BIN);
-                        loose.n++;
-                    }
-                }
-                for (uint32_t r = loose.n; r < HG_LEVELS; r++) loose.first[r] = loose.count[r] = 0u;
-                if (!attr_gather_set_) {
-                    NRC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grid_gather), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(GB_BIN * 16u)));
-                    attr_gather_set_ = true;
-                }
-                const bool level_major = !xcd8_;
-                hipLaunchKernelGGL(k_grid_scatter, level_major ? dim3(ceil_div(n, 256), HG_LEVELS) : dim3(ceil_div(n, 256) * HG_LEVELS, 1), dim3(256), 0, s, d_in, d_denc_, d_grid_fix_, n, lv,
-                                   gb, d_grid_counters_, d_grid_lists_);
-                hipLaunchKernelGGL(k_grid_gather, dim3(grid_bins_total_ + loose_chunks), dim3(NRC_GB_GATHER_THREADS), GB_BIN * 16u, s, d_grad16_,
-                                   d_grid_bin_entry0_, grid_bins_total_, d_grid_counters_, d_grid_lists_, d_grid_fix_, loose);
+        if (plan_.hash) {
+            // bin lists + exact LDS sums for the large levels, the fixed-point shadow for the rest (k_grid_scatter / k_grid_gather)
+            if (!attr_gather_set_) {
+                allow_dynamic_lds((int)(GB_BIN * 16u), &k_grid_gather);
+                attr_gather_set_ = true;
             }
+            const bool level_major = !xcd8_;
+            hipLaunchKernelGGL(k_grid_scatter, level_major ? dim3(ceil_div(n, 256), HG_LEVELS) : dim3(ceil_div(n, 256) * HG_LEVELS, 1), dim3(256), 0, s, d_in, d_denc_, d_grid_fix_, n, levels_,
+                               bins_.bins, d_grid_counters_, d_grid_lists_);
+            hipLaunchKernelGGL(k_grid_gather, dim3(bins_.bins_total + bins_.loose_chunks), dim3(NRC_GB_GATHER_THREADS), GB_BIN * 16u, s, d_grad16_,
+                               d_grid_bin_entry0_, bins_.bins_total, d_grid_counters_, d_grid_lists_, d_grid_fix_, bins_.loose);
             // the fp32 copy in the gradient vector is for whoever reads the vector (exchange, hook, debug read-back): the
             // optimizer takes the table gradient from grad16 itself (k_grid_opt2)
             grid16_valid_ = fused_opt_;
             if (widen_grid_grad || !fused_opt_)
-                hipLaunchKernelGGL(k_grid_grad_f32, dim3(ceil_div(n_grid_entries_, 256)), dim3(256), 0, s, d_grad16_,
-                                   d_grad_ + n_mlp_, n_grid_entries_);
+                hipLaunchKernelGGL(k_grid_grad_f32, dim3(ceil_div(plan_.n_grid_entries, 256)), dim3(256), 0, s, d_grad16_,
+                                   d_grad_ + plan_.n_mlp, plan_.n_grid_entries);
         }
     }
     NRC_HIP(hipGetLastError());
-    const uint32_t chunk = wgrad_chunk(n);
+    const uint32_t chunk = wgrad_chunk(n, (uint32_t)n_wgrad_tasks_, wgrad_cus(), wgrad_old_);
     const uint32_t n_chunks = ceil_div(n, chunk);
     if (wgrad_old_)
         hipLaunchKernelGGL(k_wgrad, dim3(n_chunks), dim3(WGRAD_WAVES * 64), 0, s, (const half_t*)d_deltas_, (const half_t*)d_acts_, n,
-                           depth_ * kw_ + 8, enc_dims_ + depth_ * kw_, (const WgradTile*)d_tiles_, n_wgrad_tiles_, d_slabs_,
-                           n_mlp_);
+                           plan_.depth * plan_.kw + 8, plan_.enc_dims + plan_.depth * plan_.kw, (const WgradTile*)d_tiles_, n_wgrad_tiles_, d_slabs_,
+                           plan_.n_mlp);
     else
         hipLaunchKernelGGL(k_wgrad2, dim3(n_chunks, ceil_div((uint32_t)n_wgrad_tasks_, (uint32_t)WGRAD2_WAVES)), dim3(WGRAD2_WAVES * 64), 0, s,
-                           (const half_t*)d_deltas_, (const half_t*)d_acts_, n, chunk, depth_ * kw_ + 8, enc_dims_ + depth_ * kw_,
-                           (const WgradTask*)d_tasks_, n_wgrad_tasks_, d_slabs_, n_mlp_);
+                           (const half_t*)d_deltas_, (const half_t*)d_acts_, n, chunk, plan_.depth * plan_.kw + 8, plan_.enc_dims + plan_.depth * plan_.kw,
+                           (const WgradTask*)d_tasks_, n_wgrad_tasks_, d_slabs_, plan_.n_mlp);
     NRC_HIP(hipGetLastError());
     auto reduce = [&](auto... ga) {      // (nothing, or the scan's GuardArgs)
-        hipLaunchKernelGGL(k_reduce_grads<decltype(ga)...>, dim3(ceil_div(n_mlp_, 64)), dim3(256), 0, s, d_slabs_, n_chunks, n_mlp_,
+        hipLaunchKernelGGL(k_reduce_grads<decltype(ga)...>, dim3(ceil_div(plan_.n_mlp, 64)), dim3(256), 0, s, d_slabs_, n_chunks, plan_.n_mlp,
                            d_grad_, d_loss_part_, n_tiles, d_loss_, ga...);
     };
     if (guard_on_) reduce(guard_scan_args());
@@ -3151,29 +2848,29 @@ void Mlp::guard_stats(uint32_t* skipped, uint32_t* last_step) const
 uint32_t Mlp::grid_list_capacity(uint32_t n) const
 {
     const unsigned long long touched = (unsigned long long)n * HG_LEVELS * 8ull;      // one entry per (sample, level, corner) at most
-    return (uint32_t)std::min<unsigned long long>(touched, n_grid_entries_);
+    return (uint32_t)std::min<unsigned long long>(touched, plan_.n_grid_entries);
 }
 
 // the table gradient of the last backward() as a list (see k_grid_pack); d_list: grid_list_words(cap) words
 void Mlp::grid_grad_pack(uint32_t* d_list, uint32_t cap, hipStream_t s)
 {
-    if (!hash_) fail("grid_grad_pack: this model has no trainable encoding");
+    if (!plan_.hash) fail("grid_grad_pack: this model has no trainable encoding");
     NRC_HIP(hipMemsetAsync(d_list, 0xff, grid_list_words(cap) * 4, s));        // entry 0xffffffff: padding
     NRC_HIP(hipMemsetAsync(d_list, 0, 8, s));
-    hipLaunchKernelGGL(k_grid_pack, dim3(ceil_div(n_grid_entries_, 4096)), dim3(256), 0, s, d_grad16_,
-                       n_grid_entries_, d_list, cap);
+    hipLaunchKernelGGL(k_grid_pack, dim3(ceil_div(plan_.n_grid_entries, 4096)), dim3(256), 0, s, d_grad16_,
+                       plan_.n_grid_entries, d_list, cap);
     NRC_HIP(hipGetLastError());
 }
 
 // the gradient vector's table part := sum of n_lists lists (grid_list_words(cap) words apart), added in list order
 void Mlp::grid_grad_apply(const uint32_t* d_lists, uint32_t n_lists, uint32_t cap, hipStream_t s)
 {
-    if (!hash_) fail("grid_grad_apply: this model has no trainable encoding");
+    if (!plan_.hash) fail("grid_grad_apply: this model has no trainable encoding");
     grid16_valid_ = false;      // the optimizer reads the summed fp32 table gradient
-    NRC_HIP(hipMemsetAsync(d_grad_ + n_mlp_, 0, (size_t)n_grid_entries_ * 8, s));
+    NRC_HIP(hipMemsetAsync(d_grad_ + plan_.n_mlp, 0, (size_t)plan_.n_grid_entries * 8, s));
     for (uint32_t r = 0; r < n_lists; r++)
         hipLaunchKernelGGL(k_grid_apply, dim3(ceil_div(cap, 256)), dim3(256), 0, s, d_lists + (size_t)r * grid_list_words(cap), cap,
-                           d_grad_ + n_mlp_, n_grid_entries_);
+                           d_grad_ + plan_.n_mlp, plan_.n_grid_entries);
     NRC_HIP(hipGetLastError());
 }
 
@@ -3208,7 +2905,7 @@ bool Mlp::optimizer_step(hipStream_t s, uint32_t loss_seq, unsigned long long* l
     const AdamArgs a = adam_args_of(cfg_, step);
     if (guard_on_) {
         if (!guard_scanned_) {
-            hipLaunchKernelGGL(k_guard_scan, dim3(ceil_div(n_mlp_, 256)), dim3(256), 0, s, (const float*)d_grad_, n_mlp_, (const float*)d_loss_,
+            hipLaunchKernelGGL(k_guard_scan, dim3(ceil_div(plan_.n_mlp, 256)), dim3(256), 0, s, (const float*)d_grad_, plan_.n_mlp, (const float*)d_loss_,
                                guard_scan_args());
             NRC_HIP(hipGetLastError());
         }
@@ -3219,31 +2916,31 @@ bool Mlp::optimizer_step(hipStream_t s, uint32_t loss_seq, unsigned long long* l
     // ga: nothing, or this step's GuardArgs
     auto enqueue = [&](auto... ga) {
         if (!fused_opt_) {
-            if (sgd_) hipLaunchKernelGGL(k_sgd_ema<decltype(ga)...>, dim3(ceil_div(n_params_, 256)), b, 0, s, d_w_, d_ema_, d_grad_, n_params_, lr, a, ga...);
-            else hipLaunchKernelGGL(k_adam_ema<decltype(ga)...>, dim3(ceil_div(n_params_, 256)), b, 0, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, n_params_, n_mlp_, a, ga...);
+            if (plan_.sgd) hipLaunchKernelGGL(k_sgd_ema<decltype(ga)...>, dim3(ceil_div(plan_.n_params, 256)), b, 0, s, d_w_, d_ema_, d_grad_, plan_.n_params, lr, a, ga...);
+            else hipLaunchKernelGGL(k_adam_ema<decltype(ga)...>, dim3(ceil_div(plan_.n_params, 256)), b, 0, s, d_w_, d_ema_, d_m_, d_v_, d_grad_, plan_.n_params, plan_.n_mlp, a, ga...);
             NRC_HIP(hipGetLastError());
             repack(s);
             return false;
         }
         const int next = infer_set_ ^ 1;
-        const PackDst d{d_dst_, d_dst_ + n_mlp_, d_dst_ + 2 * (size_t)n_mlp_, (half_t*)d_pk_fwd_, (half_t*)d_pk_infer_[next], (half_t*)d_pk_bwd_};
+        const PackDst d{d_dst_, d_dst_ + plan_.n_mlp, d_dst_ + 2 * (size_t)plan_.n_mlp, (half_t*)d_pk_fwd_, (half_t*)d_pk_infer_[next], (half_t*)d_pk_bwd_};
         const float* loss = d_loss_;
-        with_flag(sgd_, [&](auto sgd) {
+        with_flag(plan_.sgd, [&](auto sgd) {
             constexpr bool SGD = decltype(sgd)::value;
             // (the step's last launch takes the armed event along -- launch_last, nrc_common.hpp: k_opt_pack, or the table's optimizer behind it)
             const auto pack = k_opt_pack<SGD, decltype(ga)...>;
             auto launch = [&](auto... args) {
-                if (hash_) hipLaunchKernelGGL(pack, dim3(ceil_div(n_mlp_, 256)), b, 0, s, args...);
-                else launch_last(pack, dim3(ceil_div(n_mlp_, 256)), b, 0u, s, args...);
+                if (plan_.hash) hipLaunchKernelGGL(pack, dim3(ceil_div(plan_.n_mlp, 256)), b, 0, s, args...);
+                else launch_last(pack, dim3(ceil_div(plan_.n_mlp, 256)), b, 0u, s, args...);
             };
-            launch(d_w_.get(), d_ema_.get(), d_m_.get(), d_v_.get(), d_grad_.get(), n_mlp_, lr, a, d, loss, loss_seq, loss_cell, ga...);
-            if (!hash_) return;
+            launch(d_w_.get(), d_ema_.get(), d_m_.get(), d_v_.get(), d_grad_.get(), plan_.n_mlp, lr, a, d, loss, loss_seq, loss_cell, ga...);
+            if (!plan_.hash) return;
             uint32_t *tt = d_t16_train_, *te = d_t16_ema_[next], *g16 = d_grad16_;
-            const uint32_t np = n_grid_entries_ / 2u;
+            const uint32_t np = plan_.n_grid_entries / 2u;
             if (grid16_valid_) grad16_clean_ = true;      // k_grid_opt2<., true> clears the entries it reads, on a bad step too
             with_flag(grid16_valid_, [&](auto from16) {
                 launch_last(k_grid_opt2<SGD, decltype(from16)::value, decltype(ga)...>, dim3(ceil_div(np, 256)), b, 0u, s, d_w_.get(), d_ema_.get(), d_m_.get(), d_v_.get(), d_grad_.get(),
-                            g16, n_mlp_, np, lr, a, tt, te, ga...);
+                            g16, plan_.n_mlp, np, lr, a, tt, te, ga...);
             });
         });
         NRC_HIP(hipGetLastError());

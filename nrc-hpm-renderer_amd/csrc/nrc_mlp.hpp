@@ -6,13 +6,9 @@
 #include <vector>
 
 #include "nrc_common.hpp"
+#include "nrc_mlp_plan.hpp"      // the device-free half: MlpPlan and everything computed from it (tests/test_mlp_plan_host.py)
 
 namespace nrc {
-
-struct MlpLayer {
-    uint32_t out, in;
-    uint32_t off;   // offset into the canonical fp32 parameter vector ([out][in] row-major)
-};
 
 // The non-finite guard (include/nrc_hpm.h, nrc_cache_set_nonfinite_policy).  A pass that reads the final gradient stores `stamp` into
 // words[0] when a word of it, or the loss, is not finite; the optimizer kernels of the same step compare words[0] with `stamp` and turn
@@ -62,7 +58,7 @@ public:
     // sizes kSideSlot's feature buffer for n EMA queries now (a buffer that grows later synchronises the device)
     void reserve_side_slot(uint32_t n) { if (!encodes_in_kernel()) ensure_features(n, kSideSlot); }
     // EMA inference encodes the raw queries inside the MLP kernel (no feature buffer sized by the launch)
-    bool encodes_in_kernel() const { return fused_ || enc80_generic_; }
+    bool encodes_in_kernel() const { return plan_.fused || plan_.enc80_generic; }
     // forward (training weights) + loss + backward -> gradient vector (x loss_scale) and loss cell
     // widen_grid_grad (models with a trainable table): also write the table gradient into the fp32 gradient vector -- needed only
     // by readers of the vector (dense exchange, gradient hook, debug read-back); the optimizer reads the packed fp16 table itself
@@ -73,7 +69,7 @@ public:
     // before the training stream is free may encode them elsewhere (the renderer: on the train-ray stream, behind the rays).  Two
     // buffers of their own, by the caller's parity (not the one backward() encodes into: a step that encodes for itself may still be
     // reading that one); returns the features of the n samples at d_in.
-    bool can_pre_encode() const { return !fused_ && !hash_; }
+    bool can_pre_encode() const { return !plan_.fused && !plan_.hash; }
     const void* pre_encode(const float* d_in, uint32_t n, int parity, hipStream_t s);
     // the gradient vector was written from outside (exchange result, hook, nrc_cache_set_params): it is what the optimizer reads
     void grad_vector_is_source() { grid16_valid_ = false; }
@@ -83,23 +79,21 @@ public:
     bool optimizer_step(hipStream_t s, uint32_t loss_seq = 0, unsigned long long* loss_cell = nullptr);
     void repack(hipStream_t s);
 
-    uint32_t n_params() const { return n_params_; }
-    uint32_t enc_dims() const { return enc_dims_; }
+    uint32_t n_params() const { return plan_.n_params; }
+    uint32_t enc_dims() const { return plan_.enc_dims; }
     float* grad_ptr() { return d_grad_; }
     float* loss_ptr() { return d_loss_; }
     float* buffer(int which);    // 0 w, 1 ema, 2 m, 3 v, 4 grad
-    // tiny-cuda-nn's own parameter layout (params_full_precision of its Trainer): the same matrices in the same order with the output
-    // matrix stored 16 x width (rows 3..15 feed the padded outputs nobody reads), then the table.  tcnn_param_count() = n_params() +
-    // 13 * width.  to / from convert a host vector of buffer `which` (0..3; the dead rows of 4, the gradient, are zero); the dead
-    // rows are kept on the host as they were initialised / last set, so that a dump read back is the dump
-    uint32_t tcnn_param_count() const { return n_params_ + 13u * width_; }
-    void to_tcnn_layout(int which, const float* own, float* tcnn) const;
-    void from_tcnn_layout(int which, const float* tcnn, float* own);
+    // tiny-cuda-nn's own parameter layout (nrc_mlp_plan.hpp).  to / from convert a host vector of buffer `which` (0..3; the dead rows of
+    // 4, the gradient, are zero); the dead rows are kept on the host as they were initialised / last set, so that a dump read back is the dump
+    uint32_t tcnn_param_count() const { return nrc::tcnn_param_count(plan_); }
+    void to_tcnn_layout(int which, const float* own, float* tcnn) const { nrc::to_tcnn_layout(plan_, dead_rows(which), own, tcnn); }
+    void from_tcnn_layout(int which, const float* tcnn, float* own) { nrc::from_tcnn_layout(plan_, dead_rows(which), tcnn, own); }
     // sparse exchange of the HashGrid table gradient (nrc_mlp.hip, k_grid_pack): the gradient vector is
     // [n_mlp_params() matrix gradients][2 per table entry][2-word loss cell]
-    bool has_grid() const { return hash_; }
-    uint32_t n_mlp_params() const { return n_mlp_; }
-    uint32_t grid_entries() const { return n_grid_entries_; }
+    bool has_grid() const { return plan_.hash; }
+    uint32_t n_mlp_params() const { return plan_.n_mlp; }
+    uint32_t grid_entries() const { return plan_.n_grid_entries; }
     uint32_t grid_list_capacity(uint32_t n_batch) const;
     static size_t grid_list_words(uint32_t cap) { return 2 + 2 * (size_t)cap; }
     void grid_grad_pack(uint32_t* d_list, uint32_t cap, hipStream_t s);
@@ -135,45 +129,41 @@ private:
                          const uint32_t* live_count = nullptr);
 
     nrc_config cfg_;
-    uint32_t width_, depth_, enc_dims_, n_params_;
-    uint32_t kw_ = 0;            // width the kernels run at: max(width_, 32)
-    uint32_t loss_id_;
-    bool sgd_ = false;           // nested optimizer: Adam (default) or SGD
-    bool fused_ = false;         // north-star model (Frequency+OneBlob, 6x64): fully fused kernels; otherwise the generic path
-    std::vector<MlpLayer> layers_;
+    const MlpPlan plan_;         // shapes, offsets and kernel family of the model (validated: make_mlp_plan)
     DevBuf<void> d_feat_[5];     // generic path: fp16 features [n][enc_dims]; [0] inference, [1] training (encoded by backward), [2] [3] training (pre_encode, by parity), [4] side inference (kSideSlot)
     uint32_t feat_n_[5] = {0, 0, 0, 0, 0};
     int infer_set_ = 0;          // which of the double-buffered inference (EMA) image / table sets is current
-    uint32_t n_mlp_ = 0;         // matrix parameters; (posID 0) the hash-grid table [entry][2] follows them in every vector
-    bool hash_ = false;
     bool xcd8_ = true;           // the device has eight XCDs: the level-per-XCD launch mappings of the HashGrid kernels apply
-    uint32_t hg_off_[17] = {0};  // per-level entry offsets
-    uint32_t n_grid_entries_ = 0;
+    HashLevels levels_ = {};     // plan_.hg_off as the HashGrid kernels take it
     DevBuf<uint32_t> d_t16_train_, d_t16_ema_[2];   // half2-per-entry gather copies of the table
     DevBuf<_Float16> d_denc_;    // fp16 [n][32] dL/d(grid features)
     DevBuf<uint32_t> d_grad16_;  // half2 per table entry: target of the packed gradient atomics
-    // bin lists of the table gradient (k_grid_scatter / k_grid_gather): (entry, value) pairs per bin of 4 096 entries, pair counters, per-bin
+    // bin lists of the table gradient (k_grid_scatter / k_grid_gather): (entry, value) pairs per bin of GB_BIN = 2 048 entries, pair counters, per-bin
     // {first entry, list offset, capacity}; d_grid_fix_: the table's fixed-point shadow (two int64 per entry) for what bypasses the lists
     DevBuf<uint2> d_grid_lists_;
     DevBuf<uint32_t> d_grid_counters_;
     DevBuf<uint4> d_grid_bin_entry0_;
     DevBuf<long long> d_grid_fix_;
-    uint32_t grid_bin_first_[16] = {}, grid_bin_count_[16] = {}, grid_bin_cap_[16] = {}, grid_list0_[16] = {}, grid_bins_total_ = 0;
+    GridBinPlan bins_;           // of the current workspace (rebuilt when it grows)
     bool attr_gather_set_ = false;
 
     DevBuf<float> d_w_, d_ema_, d_m_, d_v_, d_grad_;
     float* d_loss_ = nullptr;            // inside d_grad_, behind the parameters
     std::vector<float> tcnn_dead_rows_[4];      // rows 3..15 of tiny-cuda-nn's 16 x width output matrix, per buffer 0..3
+    float* dead_rows(int which) const
+    {
+        if (which < 0 || which > 4) fail("bad parameter buffer id");
+        return which < 4 ? const_cast<float*>(tcnn_dead_rows_[which].data()) : nullptr;
+    }
     // fp16 MFMA A-operand fragment images ([frag][lane][8 halfs]): inference (EMA), training forward, training dgrad (W^T)
     DevBuf<void> d_pk_infer_[2], d_pk_fwd_, d_pk_bwd_;
     DevBuf<int32_t> d_src_fwd_, d_src_bwd_;   // packed slot -> canonical index (-1 = zero)
-    DevBuf<int32_t> d_dst_;              // [3][n_mlp_] parameter -> slot in the forward / EMA inference / backward image (k_opt_pack)
+    DevBuf<int32_t> d_dst_;              // [3][n_mlp] parameter -> slot in the forward / EMA inference / backward image (k_opt_pack)
     bool fused_opt_ = false;
     bool grad16_clean_ = false;          // d_grad16_ is all zero (the optimizer cleared what the last backward() touched)
     bool grid16_valid_ = false;          // the packed fp16 table gradient of the last backward() is what the optimizer should read
-    int32_t* d_src_inf_ = nullptr;       // the same for the EMA inference image (= d_src_fwd_ unless enc80_generic_)
+    int32_t* d_src_inf_ = nullptr;       // the same for the EMA inference image (= d_src_fwd_ unless enc80_generic)
     DevBuf<int32_t> d_src_inf_own_;      // what d_src_inf_ points at when it is not d_src_fwd_
-    bool enc80_generic_ = false;         // generic model whose EMA inference encodes Frequency(12)+OneBlob(4) inside k_infer_gen
     uint32_t n_frag_fwd_ = 0, n_frag_bwd_ = 0;
 
     // training workspace
@@ -187,8 +177,7 @@ private:
     DevBuf<void> d_tasks_;       // WgradTask[] (row-block tasks of k_wgrad2)
     int n_wgrad_tasks_ = 0;
     bool wgrad_old_ = false;     // round 3's k_wgrad (up to 64 neurons; NRC_DEBUG=wgrad_old=0|1)
-    void build_wgrad_tasks();
-    uint32_t wgrad_chunk(uint32_t n);
+    uint32_t wgrad_cus() { return wgrad_old_ ? 0u : (uint32_t)num_cus(); }      // (k_wgrad's chunk does not depend on the device)
 };
 
 }  // namespace nrc

@@ -715,7 +715,7 @@ def test_hashgrid_model_matches_oracle(api, orc, torch_gpu, dir_id, width, depth
 
 @pytest.mark.parametrize("log2", [19, 16, 12], ids=["2^19", "2^16", "2^12"])
 def test_table_gradient_is_exact_whatever_path_its_pairs_take(api, orc, torch_gpu, monkeypatch, log2):
-    """k_grid_scatter + k_grid_gather: the pairs of the levels with at least 8 bins of 4 096 entries go to per-bin lists and are summed in
+    """k_grid_scatter + k_grid_gather: the pairs of the levels with at least 8 bins of 2 048 entries go to per-bin lists and are summed in
     LDS, the coarse levels and what overflows a list are added into the table's fixed-point shadow -- every sum in 64-bit fixed point,
     i.e. EXACT, and rounded to fp16 once.  So the gradient does not depend on which path a pair takes (NRC_DEBUG=grid_no_bins: everything
     through the shadow) nor on the order of arrival: bit-identical between the two builds of the path and from run to run, on a full
@@ -751,6 +751,38 @@ def test_table_gradient_is_exact_whatever_path_its_pairs_take(api, orc, torch_gp
         got = c.GetParams(4)[nm:] / 128.0
         c.Destroy()
         assert rel(got, np.array(onn.buffer(4))[nm:]) < 2e-2
+
+
+@pytest.mark.parametrize("model,batches", [(dict(pos_id=2, nn_width=64, nn_depth=2), (2048, 32, 4096, 32)),
+                                           (dict(pos_id=3, nn_width=128, nn_depth=2), (2048, 32, 4096, 32)),
+                                           (dict(pos_id=0, dir_id=0, nn_width=64, nn_depth=2, hashgrid_log2_size=14), (2048, 256, 4096, 256))],
+                         ids=["2x64", "2x128", "hashgrid-2^14"])
+def test_a_workspace_that_grew_gives_the_gradient_of_a_fresh_one(api, torch_gpu, model, batches):
+    """The training workspace keeps what it was sized for -- the slabs of the split-K weight gradient, the task and tile lists, the bin plan
+    of the table gradient -- from one Backward to the next and is rebuilt only when a batch is larger than any before.  One cache runs the
+    batches in turn (grow, reuse for a smaller batch, grow again, reuse); after each call its gradient vector equals, bit for bit, that of
+    a fresh cache given the same batch alone.  HashGrid: half of each batch is spread over the volume, half sits in one corner, so a fresh
+    256-sample cache has 1 024-pair bin lists that overflow into the shadow where the grown one's 4 096-pair lists do not."""
+    rng = np.random.default_rng(23)
+    n_max = max(batches)
+    xq = queries(n_max, seed=12, nan_frac=0.0)
+    if model["pos_id"] == 0:
+        xq[:, :3] -= 31.0
+        xq[1::2, :3] *= 0.02
+    x = torch_gpu.from_numpy(xq).cuda()
+    t = torch_gpu.from_numpy(rng.random((n_max, 3), dtype=np.float32)).cuda()
+    grown = api.NeuralRadianceCache(api.AppConfig(**model))
+    for n in batches:
+        xn, tn = x[:n].contiguous(), t[:n].contiguous()
+        grown.Backward(xn, tn)
+        got = grown.GetParams(4).copy()
+        fresh = api.NeuralRadianceCache(api.AppConfig(**model))
+        fresh.Backward(xn, tn)
+        want = fresh.GetParams(4)
+        fresh.Destroy()
+        assert np.isfinite(want).all() and np.abs(want).max() > 0.0
+        assert np.array_equal(got, want), n
+    grown.Destroy()
 
 
 def test_hashgrid_training_is_bitwise_reproducible(api, torch_gpu):
