@@ -615,7 +615,9 @@ def test_live_query_list_changes_no_pixel(api, sc, cloud16, torch_gpu, model, mo
     """renderer inference builds its 32-query tiles from the frame's live-query list (k_gen_rays appends the query index of every
     pixel that scattered; k_infer, k_infer_gen, k_encode_hash_list) instead of computing every tile of four pixel rows that holds a
     live query: results are per query, so framebuffer, loss and parameters after 6 trained frames equal the list-free path
-    (NRC_DEBUG=no_live_list) bit for bit, and so does the radiance of every scattered pixel of the last frame"""
+    (NRC_DEBUG=no_live_list) bit for bit, and so does the radiance of every scattered pixel of the last frame.
+    (256x160 is at most 40 960 queries: one round of every inference kernel and less than one stride of the list encoder.  Frames past a
+    round, against the dense kernel per live pixel: test_gpu_renderer_inference_rounds.py)"""
     W, H = 256, 160
     scene = sc.make_scene(cloud16, scene_id=4)
     frs = sc.frame_randoms(6, seed=29)
